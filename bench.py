@@ -1,10 +1,17 @@
 #!/usr/bin/env python3
 """bench.py - Davidson iterations/s + achieved A*V HBM GB/s vs roofline (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Several GPUs: the timed workload only, unless --all-legs (see its help).
+A plain run sets the timed workload up, runs W warm-up and K timed solves and prints the result line: the contract's fields,
+`config`, `eigenvalues` and the in-solve `roofline` (from the HIP events of the timed solves; no run of its own).  --full adds
+every other measurement listed below (microbenchmarks, the other configurations, the CPU baseline).  Several GPUs with --full:
+the timed workload and its measurements only, unless --all-legs (see its help).
+
+--dump-outputs DIR: after the timed solves, what the last of them returned to its caller - DIR/eigenvalues.npy (the `lowest`
+eigenvalues, float64) and DIR/iterations.npy (its iteration count, float64) - so that two builds can be compared output for
+output; the inputs are generated from fixed seeds and are the same in every run with the same arguments.
 
 A "step" is one complete `generalized_eigensolver` solve (Fortran driver loop on the HIP engine) of the
 largest BASELINE.json configuration that fits one GPU: configs[2] = N=200000 dense fp64, lowest=16, DPR,
@@ -15,7 +22,7 @@ new basis block and reduce-scatter the partial products with RCCL inside libdavi
 control plane (unique-id broadcast, barriers, max-over-ranks of the time).  value = Davidson iterations
 per second over the K timed solves (strong scaling: the problem is the same for every N).
 
-Objects in the JSON line besides the contract's fields:
+Objects in the JSON line of a --full run besides the contract's fields:
   roofline       the dominant kernel of the timed region (the block matvec as the solve launches it: 32 / 64
                  columns per launch - bound by the fp64 matrix pipe), HIP-event timed inside the solves; its hbm_* keys
                  (and the nested `hbm` object) carry the NORTH-STAR measurement - A*V at N=200000, k=8 on the same resident
@@ -98,7 +105,15 @@ def parse():
                     help="exercise the launch plumbing (rendezvous, id broadcast, barrier, max over ranks) without a GPU")
     ap.add_argument("--cpu-n", type=int, default=0, help="order for the CPU baseline (0 = same as --small-n)")
     ap.add_argument("--cpu-n2", type=int, default=40000, help="second, larger order for the CPU baseline (0 = none)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed workload: the microbenchmarks, roofline and scaling figures, the other configurations and "
+                         "the CPU baseline (off: set up, warm up, time --steps solves, print the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed solve returned (eigenvalues, iteration count) as DIR/<name>.npy, float64")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 CPU_CHILD = r"""
@@ -430,6 +445,7 @@ def main():
 
     import fortran_davidson_amd as fd
     engines_made = [0]
+    last_iters = [0]          # iteration count of the latest solve timed_solves ran (what --dump-outputs writes)
 
     def make_engine(n, lowest, max_dim=None, storage="full", gev=False):
         eng = fd.DavidsonEngine(n, lowest, max_dim, gev=gev, device=device, rank=rank, nranks=world, storage=storage)
@@ -466,6 +482,7 @@ def main():
         for _ in range(reps):
             lam, _, it = eng.solve(method, 1000, tol, want_vectors=False)
             its += it
+        last_iters[0] = it
         eng.c.synchronize(); barrier()
         return max_over_ranks(time.perf_counter() - t0), its, lam
 
@@ -497,7 +514,7 @@ def main():
         except Exception as exc:       # noqa: BLE001
             return {"error": repr(exc)[:200]}
 
-    hbm_measured = measured_stream() if rank == 0 or world > 1 else None
+    hbm_measured = measured_stream() if args.full and (rank == 0 or world > 1) else None
     stream_gbps = max(hbm_measured.get("copy_GBps", 0.0), hbm_measured.get("triad_GBps", 0.0)) if hbm_measured else 0.0
     read_gbps = hbm_measured.get("read_GBps", 0.0) if hbm_measured else 0.0
 
@@ -535,6 +552,11 @@ def main():
     elapsed, total_iters, lam = timed_solves(eng, "DPR", args.steps, args.tol)
     st = eng.c.stats()
     value = total_iters / elapsed
+    if args.dump_outputs and rank == 0:
+        # every rank returns the same eigenvalues (the small eigenproblem is solved identically on each)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "eigenvalues.npy"), np.asarray(lam, dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "iterations.npy"), np.array([last_iters[0]], dtype=np.float64))
 
     # roofline of the dominant kernel over the timed region (HIP events on the engine's stream, inside the solves)
     launches = max(int(st.apply_launches), 1)
@@ -565,6 +587,46 @@ def main():
                 "apply_ms_kernel_only_per_solve": round(st.apply_kernel_ms / args.steps, 3),
                 "in_solve_GBps_end_to_end": round(hbm_in_solve, 1),
                 "note": "per rank, HIP events in the timed solves; 32 / 64 columns per launch: MFMA roof; hbm_*: A*V at N x 8"}
+    roofline.update({
+        # what of a solve is not the roofline kernel: the rest of the applies (pack + fixed-order reduction) and the rest of the solve
+        "ms_per_solve": round(elapsed / args.steps * 1e3, 3),
+        "non_kernel_ms_per_solve": round(elapsed / args.steps * 1e3 - st.apply_kernel_ms / args.steps, 3),
+        "apply_non_kernel_ms_per_solve": round((st.apply_ms - st.apply_kernel_ms) / args.steps, 3)})
+
+    def emit(objects):
+        """rank 0 prints the one JSON result line: the contract's fields, the workload, `roofline`, then `objects`"""
+        if rank != 0:
+            return
+        # the driver's record keeps the first ~20 scalar keys of `roofline` and cuts strings at ~120 characters: what a reader needs to
+        # recompute both fractions comes first, the long texts last
+        first = ["bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source", "avg_launch_ms", "launches", "ms_per_solve", "non_kernel_ms_per_solve",
+                 "hbm_N", "hbm_k", "hbm_algorithmic_bytes", "hbm_ms_end_to_end", "hbm_GBps_end_to_end", "hbm_frac", "hbm_frac_kernel_only",
+                 "hbm_traffic", "hbm_frac_of_measured_read", "hbm_k16_frac", "apply_non_kernel_ms_per_solve", "flops_per_launch",
+                 "algorithmic_bytes_per_launch", "columns_per_launch", "kernel"]
+        last = ["note", "traffic_provenance"]
+        ordered = {**{k_: roofline[k_] for k_ in first if k_ in roofline},
+                   **{k_: v_ for k_, v_ in roofline.items() if k_ not in first and k_ not in last},
+                   **{k_: roofline[k_] for k_ in last if k_ in roofline}}
+        line = {"metric": "Davidson iterations/sec (dense DPR solve, matrix resident in HBM) + A*V HBM GB/s vs roofline",
+                "value": round(value, 4), "unit": "iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong",
+                "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+                "config": {"workload": f"N={n} dense fp64 lowest={lowest} DPR max_dim_sub={max_dim} tol={args.tol} sparsity={args.sparsity} seed=1 storage={storage}",
+                           "N": n, "lowest": lowest, "max_dim_sub": max_dim, "storage": storage, "sparsity": args.sparsity, "seed": 1,
+                           "iters_per_solve": total_iters // args.steps, "parallelism": (f"block rows of the lower triangle over {world} GPUs, row slabs of the panels" if storage == "symmetric" else f"row-slab x{world}") if world > 1 else "single GPU",
+                           "generate_seconds": round(t_gen, 2), "storage_detail": storage_words},
+                "eigenvalues": [float(x) for x in lam[:3]], "roofline": ordered}
+        line.update(objects)
+        if "cpu_baseline" not in line:
+            line["cpu_baseline"] = None
+        print(json.dumps(line))
+
+    if not args.full:
+        eng.close()
+        emit({})
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # north-star microbenchmark: A*V at k = 8 (16, 32) on the same resident matrix, end to end and kernel only
     apply_k = apply_rooflines(eng, (8, 16, 32), 10 if n >= 100000 else 20)
@@ -587,11 +649,7 @@ def main():
         "hbm_traffic": tr_k8[0],
         "hbm_k16_ms_end_to_end": a16["ms_end_to_end"], "hbm_k16_ms_kernel_only": a16["ms_kernel_only"],
         "hbm_k16_algorithmic_bytes": a16["algorithmic_bytes"], "hbm_k16_GBps_end_to_end": a16["GBps_end_to_end"],
-        "hbm_k16_frac": a16["frac_of_8TBps_end_to_end"], "hbm_k16_traffic": tr_k16[0],
-        # what of a solve is not the roofline kernel: the rest of the applies (pack + fixed-order reduction) and the rest of the solve
-        "ms_per_solve": round(elapsed / args.steps * 1e3, 3),
-        "non_kernel_ms_per_solve": round(elapsed / args.steps * 1e3 - st.apply_kernel_ms / args.steps, 3),
-        "apply_non_kernel_ms_per_solve": round((st.apply_ms - st.apply_kernel_ms) / args.steps, 3)})
+        "hbm_k16_frac": a16["frac_of_8TBps_end_to_end"], "hbm_k16_traffic": tr_k16[0]})
 
     extras = {}
     # one solve at timing level 2: Gram / panel phases (and, several ranks, every collective) by HIP events - inputs of the scaling model
@@ -1065,31 +1123,7 @@ def main():
                 else:
                     extras["cpu_baseline"] = raw
 
-    if rank == 0:
-        # the driver's record keeps the first ~20 scalar keys of `roofline` and cuts strings at ~120 characters: what a reader needs to
-        # recompute both fractions comes first, the long texts last
-        first = ["bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source", "avg_launch_ms", "launches", "ms_per_solve", "non_kernel_ms_per_solve",
-                 "hbm_N", "hbm_k", "hbm_algorithmic_bytes", "hbm_ms_end_to_end", "hbm_GBps_end_to_end", "hbm_frac", "hbm_frac_kernel_only",
-                 "hbm_traffic", "hbm_frac_of_measured_read", "hbm_k16_frac", "apply_non_kernel_ms_per_solve", "flops_per_launch",
-                 "algorithmic_bytes_per_launch", "columns_per_launch", "kernel"]
-        last = ["note", "traffic_provenance"]
-        roofline = {**{k_: roofline[k_] for k_ in first if k_ in roofline},
-                    **{k_: v_ for k_, v_ in roofline.items() if k_ not in first and k_ not in last},
-                    **{k_: roofline[k_] for k_ in last if k_ in roofline}}
-        line = {"metric": "Davidson iterations/sec (dense DPR solve, matrix resident in HBM) + A*V HBM GB/s vs roofline",
-                "value": round(value, 4), "unit": "iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong",
-                "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-                "config": {"workload": f"N={n} dense fp64 lowest={lowest} DPR max_dim_sub={max_dim} tol={args.tol} sparsity={args.sparsity} seed=1 storage={storage}",
-                           "N": n, "lowest": lowest, "max_dim_sub": max_dim, "storage": storage, "sparsity": args.sparsity, "seed": 1,
-                           "iters_per_solve": total_iters // args.steps, "parallelism": (f"block rows of the lower triangle over {world} GPUs, row slabs of the panels" if storage == "symmetric" else f"row-slab x{world}") if world > 1 else "single GPU",
-                           "generate_seconds": round(t_gen, 2), "storage_detail": storage_words},
-                "eigenvalues": [float(x) for x in lam[:3]],
-                "roofline": roofline, "apply": apply_k, "hbm_measured": hbm_measured}
-        line.update(extras)
-        if "cpu_baseline" not in line:
-            line["cpu_baseline"] = None
-        print(json.dumps(line))
+    emit({"apply": apply_k, "hbm_measured": hbm_measured, **extras})
     if world > 1:
         dist.destroy_process_group()
 

@@ -56,3 +56,9 @@ def test_control_plane_of_the_multi_rank_launch():
                          capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert res.returncode == 0, (res.stdout + res.stderr)[-2000:]
     assert '"control_plane": "ok"' in res.stdout
+
+
+def test_steps_and_warmup_are_checked_before_any_work():
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *bad], capture_output=True, text=True, timeout=120)
+        assert res.returncode == 2 and "--steps must be at least 1" in res.stderr, res.stderr[-2000:]

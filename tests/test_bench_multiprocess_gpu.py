@@ -45,7 +45,7 @@ def test_bench_multi_rank_flow_matches_single_rank(nproc, storage):
     # row slabs / the lower block triangle dealt out over the ranks: all-gather + reduce-scatter per sweep);
     # the configs[1] / configs[3] / configs[4] legs at small orders
     extra = ["--steps", "2", "--warmup", "1", "--order", "6000", "--storage", storage, "--small-n", "3000", "--gjd-n", "2000",
-             "--free-n", "4000", "--harness-n", "0", "--no-cpu-baseline", "--no-dropin", "--all-legs"]
+             "--free-n", "4000", "--harness-n", "0", "--no-cpu-baseline", "--no-dropin", "--all-legs", "--full"]
     if storage not in _ONE_RANK:                # the one-rank line of a storage serves both rank counts
         _ONE_RANK[storage] = run_bench(1, extra)
     one = _ONE_RANK[storage]
@@ -72,7 +72,7 @@ def test_bench_multi_rank_flow_matches_single_rank(nproc, storage):
 def test_bench_single_gpu_default_shape_of_the_line():
     """The one-GPU flow with symmetric tiles at a reduced order: every object the contract names is there."""
     line = run_bench(1, ["--steps", "2", "--warmup", "1", "--order", "8000", "--small-n", "3000", "--gjd-n", "3000",
-                         "--free-n", "6000", "--harness-n", "6000", "--harness-n2", "9000", "--no-cpu-baseline"])
+                         "--free-n", "6000", "--harness-n", "6000", "--harness-n2", "9000", "--no-cpu-baseline", "--full"])
     assert line["config"]["storage"] == "symmetric" and line["config"]["N"] == 8000
     assert len(line["config"]["workload"]) < 120 and "sparsity" in line["config"]["workload"] and "storage=symmetric" in line["config"]["workload"]
     for key in ("roofline", "apply", "configs3_gjd", "configs4_free", "configs4_free_harness", "small", "dropin", "opt_in_policy", "scaling_model"):
@@ -102,7 +102,7 @@ def test_bench_multi_rank_flow_with_the_chunked_pipeline_of_wide_blocks():
     """the same launch with the pipeline several GPUs run by default for blocks wider than 32 columns (DAV_SYM_OVERLAP=1 over the
     shared-memory transport: its collectives on the engine's stream, everything else as over RCCL; two-block-row schedule forced
     at this small order): lowest = 16 makes the 64-column expansion; same eigenvalues and iteration count as one rank"""
-    extra = ["--steps", "1", "--warmup", "1", "--order", "6000", "--lowest", "16", "--storage", "symmetric", "--headline-only"]
+    extra = ["--steps", "1", "--warmup", "1", "--order", "6000", "--lowest", "16", "--storage", "symmetric", "--headline-only", "--full"]
     env = {"DAV_SYM_R": "2", "DAV_SYM_OVERLAP": "1"}
     one = run_bench(1, extra, env)
     for nproc in (2, 3):
@@ -110,3 +110,24 @@ def test_bench_multi_rank_flow_with_the_chunked_pipeline_of_wide_blocks():
         assert many["n_gpus"] == nproc and many["config"]["iters_per_solve"] == one["config"]["iters_per_solve"]
         assert np.abs(np.array(many["eigenvalues"]) - np.array(one["eigenvalues"])).max() < 1e-10
         assert many["comm"]["collectives_per_solve"] > 0 and many["roofline"]["comm_world_size"] == nproc
+
+
+def test_plain_run_times_the_steps_and_dumps_what_the_last_one_returned(tmp_path):
+    """Without --full the run is the headline alone: the contract's fields and the in-solve roofline, none of the measurements that
+    take runs of their own.  --dump-outputs writes what the last timed solve returned, the same in a second run of the same
+    arguments and on two ranks."""
+    extra = ["--steps", "3", "--warmup", "1", "--order", "6000", "--storage", "symmetric"]
+    one = run_bench(1, extra + ["--dump-outputs", str(tmp_path / "one")])
+    assert one["steps"] == 3 and one["warmup"] == 1 and one["ms_per_step"] > 0 and one["value"] > 0
+    assert one["unit"] == "iterations/s" and one["higher_is_better"] is True and one["dtype"] == "f64"
+    assert one["roofline"]["launches"] > 0 and abs(one["roofline"]["ms_per_solve"] - one["ms_per_step"]) < 1e-9
+    assert not set(one) & {"apply", "hbm_measured", "scaling_model", "opt_in_policy", "small", "configs3_gjd", "configs4_free", "dropin", "comm"}
+    lam, its = np.load(tmp_path / "one" / "eigenvalues.npy"), np.load(tmp_path / "one" / "iterations.npy")
+    assert lam.dtype == its.dtype == np.float64 and lam.shape == (16,) and its.shape == (1,)
+    assert np.array_equal(lam[:3], one["eigenvalues"]) and its[0] == one["config"]["iters_per_solve"]
+    run_bench(1, extra + ["--dump-outputs", str(tmp_path / "again")])
+    assert np.array_equal(np.load(tmp_path / "again" / "eigenvalues.npy"), lam)
+    two = run_bench(2, extra + ["--dump-outputs", str(tmp_path / "two")])
+    assert two["n_gpus"] == 2 and "comm" not in two
+    assert np.abs(np.load(tmp_path / "two" / "eigenvalues.npy") - lam).max() < 1e-10
+    assert np.array_equal(np.load(tmp_path / "two" / "iterations.npy"), its)

@@ -45,7 +45,7 @@ def run_bench(nproc, extra, env_extra=None, expect_ok=True, timeout=600):
     return json.loads(lines[0])
 
 
-HEAD = ["--steps", "2", "--warmup", "1", "--order", "6000", "--headline-only"]
+HEAD = ["--steps", "2", "--warmup", "1", "--order", "6000", "--headline-only", "--full"]
 _ONE_RANK = {}
 
 
@@ -74,7 +74,7 @@ def test_the_engine_picks_the_way_of_its_wide_blocks_collectives_itself():
     the trial runs, validates all three ways (the second stream bitwise), the solve continues on the chosen one to the one-rank
     eigenvalues; a way whose trial result is spoiled (DAV_COLL_TRIAL_CORRUPT: one entry on rank 0) is left out and the run still
     ends correctly; a way forced through the environment (DAV_SYM_OVERLAP / DAV_COLL_DIRECT, or DAV_COLL_SELECT=0) skips the trial."""
-    extra = ["--steps", "1", "--warmup", "1", "--order", "6000", "--lowest", "16", "--storage", "symmetric", "--headline-only"]
+    extra = ["--steps", "1", "--warmup", "1", "--order", "6000", "--lowest", "16", "--storage", "symmetric", "--headline-only", "--full"]
     one = run_bench(1, extra, {"DAV_SYM_R": "2"})
     names = ("program order", "direct exchange", "second stream")
 
@@ -110,7 +110,7 @@ def test_matrix_free_and_generalized_legs_over_a_real_communicator():
     (generalized, GJD, the generated second operator partly resident: its passes agreed on by an all-reduce), configs[4] shape
     (matrix-free, symmetric generation)."""
     extra = ["--steps", "1", "--warmup", "1", "--order", "6000", "--storage", "symmetric", "--small-n", "3000", "--gjd-n", "2000", "--free-n", "4000",
-             "--restart-sparsity", "0", "--harness-n", "0", "--no-cpu-baseline", "--no-dropin", "--all-legs"]
+             "--restart-sparsity", "0", "--harness-n", "0", "--no-cpu-baseline", "--no-dropin", "--all-legs", "--full"]
     one, two = run_bench(1, extra), run_bench(2, extra)
     for key in ("small", "configs3_gjd", "configs4_free"):
         a, b = one[key], two[key]
@@ -140,7 +140,7 @@ def test_configs2_at_full_order_over_a_real_four_rank_communicator():
     box allows six processes on a card, so eight ranks run as threads over the loopback transport instead - tests/test_full_size_gpu.py):
     the iteration count and the eigenvalues of the one-rank run, 10 collectives per solve, 153.6 MB gathered and 204.8 MB
     reduce-scattered per rank and solve through RCCL itself."""
-    line = run_bench(4, ["--steps", "1", "--warmup", "1", "--headline-only"], timeout=900)
+    line = run_bench(4, ["--steps", "1", "--warmup", "1", "--headline-only", "--full"], timeout=900)
     c = line["comm"]
     assert line["n_gpus"] == 4 and c["ranks_reported_by_rccl"] == 4 and line["config"]["N"] == 200000 and line["config"]["storage"] == "symmetric"
     assert line["config"]["iters_per_solve"] == 3
