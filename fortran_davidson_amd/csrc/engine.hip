@@ -569,6 +569,7 @@ extern "C" int dav_destroy(dav_handle_t e) {
     pool_free(e->op[w].e_table);
     pool_free(e->op[w].l2_table);
     pool_free(e->op[w].dadd_table);
+    csr_release(e, e->op[w]);
   }
   lt.lap("operators");
   if (e->stream) { (void)hipStreamSynchronize(e->stream); pool_stream_put(e->stream, e->device); }

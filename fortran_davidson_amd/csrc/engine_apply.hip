@@ -489,6 +489,41 @@ int apply_ptr(E* e, int which, const double* src, int k, double* dst, bool timed
     HIPCHK(hipGetLastError());
     return 0;
   }
+  if (o.kind == DAV_KIND_CSR) {
+    // CSR rows of this rank (k_spmm.hip): the operand packed - and gathered over the ranks - as for the row slabs, then one launch of
+    // the wave-per-item kernel per 64 columns (the matrix is read once per 64 columns) and the chunk sums of the long rows.  Always fp64
+    // (inner sweeps too: there is no fp32 copy of a CSR operator).
+    for (int c = 0; c < k; c += 64) {
+      const int kk = std::min(64, k - c), groups = (kk + 15) / 16, gp = groups == 3 ? 4 : groups;
+      int slot = -1, kslot = -1;
+      const double bytes = 12.0 * (double)o.csr_nnz + 8.0 * (double)(e->nloc + 1) + 8.0 * (double)e->n * kk + 8.0 * (double)e->nloc * kk;
+      if (timed) CHK(timed_begin(e, which == DAV_OP_A ? 0 : 2, bytes, &slot));
+      launch_pack_xt(e->stream, src + (int64_t)c * e->ldp, e->ldp, e->nloc, e->nslab, kk, e->xt, e->xt_group_stride, e->row0);
+      if (has_comm(e)) {
+        CollGroup grp(e);
+        CHK(grp.begin(5, 8.0 * (double)e->nslab * 16 * groups * e->nranks));
+        for (int g = 0; g < groups; ++g) {
+          double* base = e->xt + g * e->xt_group_stride;
+          CHK(coll_allgather(e, base + e->row0 * 16, base, (size_t)e->nslab * 16));
+        }
+        CHK(grp.end("all-gather of the new block", e->stream));
+      }
+      double* out = dst + (int64_t)c * e->ldp;
+      if (timed && which == DAV_OP_A) CHK(timed_begin(e, 4, 2.0 * (double)o.csr_nnz * kk, &kslot));
+      launch_spmm_csr(e->stream, o.csr_items, o.csr_nitems, o.csr_rp, o.csr_col, o.csr_val, e->xt, e->xt_group_stride, gp, kk, o.csr_part, out,
+                      e->ldp);
+      launch_spmm_csr_finish(e->stream, o.csr_longs, o.csr_nlong, o.csr_part, kk, out, e->ldp);
+      CHK(timed_end(e, kslot));
+      launch_zero_pad_rows(e->stream, out, e->ldp, e->nloc, e->nloc_pad, kk);
+      CHK(timed_end(e, slot));
+      if (which == DAV_OP_A) {
+        e->st.applies += 1;
+        e->st.apply_cols += kk;
+      }
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   if ((o.kind == DAV_KIND_DENSE || o.kind == DAV_KIND_HASHED || o.kind == DAV_KIND_HARNESS) && o.storage == 1) {
     // A generated second operator whose tiles (partly) fit next to everything else is kept resident for its longest block rows
     // (configs[3]: B = the unit-diagonal generator next to a stored A): those rows run the stored kernels - half the time per
@@ -637,6 +672,13 @@ extern "C" int dav_bench_apply2(dav_handle_t e, int which, int k, int reps, doub
   e->timing_level = saved_level;
   *avg_ms = total / reps;
   *kernel_ms = ktotal / reps;
+  if (e->op[which].kind == DAV_KIND_CSR) {     // the CSR byte model of apply_ptr (include/davidson_hip.h: dav_stats)
+    const OpDesc& o = e->op[which];
+    *bytes = 12.0 * (double)o.csr_nnz + 8.0 * (double)(e->nloc + 1) + 8.0 * (double)e->n * k + 8.0 * (double)e->nloc * k;
+    *flops = 2.0 * (double)o.csr_nnz * k;
+    e->st = saved;
+    return 0;
+  }
   const bool sym = e->op[which].storage == 1;
   // per rank: the stored bytes and the flops of the symmetric sweep are dealt out over the ranks like its tiles
   *bytes = (sym ? (e->op[which].kind == DAV_KIND_DENSE ? 8.0 * 0.5 * (double)e->n * ((double)e->n + 1.0) / e->nranks : 0.0)

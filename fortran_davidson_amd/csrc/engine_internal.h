@@ -145,6 +145,15 @@ struct OpDesc {
   // DAV_KIND_DEVICE: the caller's own block apply on device memory (dav_set_operator_device)
   dav_device_apply_fn dev_fn = nullptr;
   void* dev_ctx = nullptr;
+  // DAV_KIND_CSR (dav_set_operator_csr): this rank's rows in canonical form and the work list of the block product (k_spmm.hip)
+  int64_t* csr_rp = nullptr;        // device: nloc + 1 row offsets from 0 (int64: a rank may hold more than 2^31 entries)
+  int32_t* csr_col = nullptr;       // device: global column of each entry
+  double* csr_val = nullptr;        // device: value of each entry
+  CsrItem* csr_items = nullptr;     // device: one item per wave (runs of whole rows, chunks of long rows)
+  CsrLong* csr_longs = nullptr;     // device: the rows longer than CSR_CHUNK and their partial slots
+  double* csr_part = nullptr;       // device: 64 doubles per chunk of a long row
+  int csr_nitems = 0, csr_nlong = 0;
+  int64_t csr_nnz = 0;              // entries of this rank's rows
 };
 
 struct SmallBuf {            // device small matrix + pinned staging
@@ -420,6 +429,7 @@ int ingest_acquire(E* e, double** buf, int64_t* cap_rows);
 int ingest_commit(E* e, int64_t row0, int64_t nrows);
 void ingest_wanted(E* e, int64_t* first, int64_t* count);
 OpParams op_params(const OpDesc& o);
+void csr_release(E* e, OpDesc& o);
 // ---- engine_apply.hip ------------------------------------------------------------------------------------
 bool inner_f32_tiles(E* e, OpDesc& o);
 bool sym_wide_enabled(const E* e);

@@ -201,6 +201,7 @@ int sym_ensure_slabs(E* e, size_t doubles) {
 int alloc_dense(E* e, int which) {
   OpDesc& o = e->op[which];
   sym_resident_release(o);
+  csr_release(e, o);
   o.res_decided = false;
   o.a32_valid = false;       // new contents: the fp32 copy is rebuilt when the next inner sweep asks for it
   o.a32_refused = false;
@@ -496,6 +497,7 @@ extern "C" int dav_set_operator_hashed(dav_handle_t e, int which, uint64_t seed,
   OpDesc& o = e->op[which];
   HIPCHK(hipStreamSynchronize(e->stream));      // sweeps in flight may still read the resident tiles of the previous definition
   sym_resident_release(o);
+  csr_release(e, o);
   o.res_decided = false;
   o.kind = DAV_KIND_HASHED; o.seed = seed; o.sparsity = sparsity; o.use_diag = use_diag_val; o.diag_val = diag_val;
   // storage mode "symmetric" (single rank) also applies to the generated operator: every entry of the lower
@@ -513,6 +515,7 @@ extern "C" int dav_set_operator_harness(dav_handle_t e, int which, const double*
   OpDesc& o = e->op[which];
   HIPCHK(hipStreamSynchronize(e->stream));
   sym_resident_release(o);
+  csr_release(e, o);
   o.res_decided = false;
   o.kind = DAV_KIND_HARNESS; o.trig = which == DAV_OP_A ? 0 : 1;
   o.storage = e->storage == 1 ? 1 : 0;      // symmetric mode: each entry generated once
@@ -560,6 +563,7 @@ extern "C" int dav_set_operator_identity(dav_handle_t e, int which) {
   OpDesc& o = e->op[which];
   HIPCHK(hipStreamSynchronize(e->stream));
   sym_resident_release(o);
+  csr_release(e, o);
   o.res_decided = false;
   o.kind = DAV_KIND_IDENTITY;
   launch_diag_free(e->stream, op_params(o), e->row0, e->nloc, o.diag);
@@ -573,6 +577,7 @@ extern "C" int dav_set_operator_host(dav_handle_t e, int which, const double* di
   OpDesc& o = e->op[which];
   HIPCHK(hipStreamSynchronize(e->stream));
   sym_resident_release(o);
+  csr_release(e, o);
   o.res_decided = false;
   o.kind = DAV_KIND_HOST;
   if (e->nloc > 0)
@@ -590,6 +595,162 @@ extern "C" int dav_set_operator_device(dav_handle_t e, int which, dav_device_app
   o.kind = DAV_KIND_DEVICE;
   o.dev_fn = fn;
   o.dev_ctx = ctx;
+  return 0;
+}
+
+// ---- a symmetric matrix in CSR form (dav_set_operator_csr) ---------------------------------------------------------------------------
+void csr_release(E* e, OpDesc& o) {
+  if (!o.csr_rp && !o.csr_col && !o.csr_val && !o.csr_items && !o.csr_longs && !o.csr_part) return;
+  (void)hipStreamSynchronize(e->stream);         // applies in flight may still read the arrays
+  pool_free(o.csr_rp); pool_free(o.csr_col); pool_free(o.csr_val);
+  pool_free(o.csr_items); pool_free(o.csr_longs); pool_free(o.csr_part);
+  o.csr_rp = nullptr; o.csr_col = nullptr; o.csr_val = nullptr;
+  o.csr_items = nullptr; o.csr_longs = nullptr; o.csr_part = nullptr;
+  o.csr_nitems = o.csr_nlong = 0;
+  o.csr_nnz = 0;
+}
+
+// Work list of the block product over the canonical local rows rp[0..nloc]: runs of at most CSR_ROWS whole rows with at most CSR_CHUNK
+// entries together, and every row longer than CSR_CHUNK cut into chunks at multiples of CSR_CHUNK from its first entry (one item and
+// one partial slot each; CsrLong lists the slots of the row).  The cut depends on the row alone, so the sums do not depend on the ranks.
+static void csr_build_items(const std::vector<int64_t>& rp, std::vector<CsrItem>& items, std::vector<CsrLong>& longs, int* nslots) {
+  const int64_t nloc = (int64_t)rp.size() - 1;
+  CsrItem cur{0, 0, 0, 0, -1, 0};
+  int slots = 0;
+  auto flush = [&]() { if (cur.nrows > 0) items.push_back(cur); cur.nrows = 0; };
+  for (int64_t i = 0; i < nloc; ++i) {
+    const int64_t a = rp[(size_t)i], b = rp[(size_t)i + 1];
+    if (b - a > CSR_CHUNK) {
+      flush();
+      const int first = slots;
+      for (int64_t q = a; q < b; q += CSR_CHUNK) items.push_back({q, std::min(b, q + CSR_CHUNK), (int32_t)i, 1, slots++, 0});
+      longs.push_back({(int32_t)i, first, slots - first, 0});
+      continue;
+    }
+    if (cur.nrows > 0 && (cur.nrows == CSR_ROWS || b - cur.p0 > CSR_CHUNK)) flush();
+    if (cur.nrows == 0) { cur.p0 = a; cur.row = (int32_t)i; }
+    cur.p1 = b;
+    cur.nrows += 1;
+  }
+  flush();
+  *nslots = slots;
+}
+
+extern "C" int dav_set_operator_csr(dav_handle_t e, int which, const int64_t* row_ptr, const int32_t* col_idx, const double* vals,
+                                    int index_base, int triangle) {
+  if (!e) return fail("dav_set_operator_csr: null engine");
+  if (which < 0 || which > 1) return fail("dav_set_operator_csr: bad operator id");
+  CHK(bind(e));
+  OpDesc& o = e->op[which];
+  // a call that fails leaves the operator unset (the engine stays usable: set it again)
+  auto refuse = [&](const std::string& msg) {
+    csr_release(e, o);
+    o.kind = DAV_KIND_NONE;
+    e->diag_host[which].clear();
+    if (which == DAV_OP_A) e->basis_order.clear();
+    return fail("dav_set_operator_csr: " + msg);
+  };
+  const int64_t n = e->n;
+  // ---- validation of the caller's global arrays: before anything is allocated or launched
+  if (n >= ((int64_t)1 << 31)) return refuse("n = " + std::to_string(n) + " must be below 2^31 (int32 column indices)");
+  if (index_base != 0 && index_base != 1) return refuse("index_base must be 0 or 1");
+  if (triangle != DAV_CSR_FULL && triangle != DAV_CSR_LOWER) return refuse("triangle must be DAV_CSR_FULL or DAV_CSR_LOWER");
+  if (!row_ptr) return refuse("null row_ptr");
+  if (row_ptr[0] != index_base) return refuse("row_ptr[0] = " + std::to_string(row_ptr[0]) + " must equal the index base " + std::to_string(index_base));
+  for (int64_t i = 0; i < n; ++i)
+    if (row_ptr[i + 1] < row_ptr[i]) return refuse("row_ptr decreases at row " + std::to_string(i + index_base));
+  const int64_t nnz = row_ptr[n] - index_base;
+  if (nnz > 0 && (!col_idx || !vals)) return refuse("null col_idx or vals");
+  const bool lower = triangle == DAV_CSR_LOWER;
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t p = row_ptr[i] - index_base; p < row_ptr[i + 1] - index_base; ++p) {
+      const int64_t j = (int64_t)col_idx[p] - index_base;
+      if (j < 0 || j >= n)
+        return refuse("column index " + std::to_string(col_idx[p]) + " out of range at entry " + std::to_string(p + index_base) + " (row " +
+                      std::to_string(i + index_base) + ")");
+      if (lower && j > i)
+        return refuse("entry (" + std::to_string(i + index_base) + ", " + std::to_string(col_idx[p]) + ") lies above the diagonal of a "
+                      "DAV_CSR_LOWER matrix");
+    }
+  // ---- canonical rows of this rank: own entries in input order, then (DAV_CSR_LOWER) the mirrored strict lower entries in the order of
+  // their source rows; stable sort by column (duplicates stay separate terms, in that order)
+  const int64_t r0 = e->row0, nloc = e->nloc;
+  auto local = [&](int64_t i) { return i >= r0 && i < r0 + nloc; };
+  std::vector<int64_t> rp((size_t)nloc + 1, 0);
+  for (int64_t i = r0; i < r0 + nloc; ++i) rp[(size_t)(i - r0) + 1] = row_ptr[i + 1] - row_ptr[i];
+  if (lower)
+    for (int64_t i = 0; i < n; ++i)
+      for (int64_t p = row_ptr[i] - index_base; p < row_ptr[i + 1] - index_base; ++p) {
+        const int64_t j = (int64_t)col_idx[p] - index_base;
+        if (j < i && local(j)) rp[(size_t)(j - r0) + 1] += 1;
+      }
+  for (int64_t i = 0; i < nloc; ++i) rp[(size_t)i + 1] += rp[(size_t)i];
+  const int64_t lnnz = rp[(size_t)nloc];
+  std::vector<int32_t> lcol((size_t)lnnz);
+  std::vector<double> lval((size_t)lnnz);
+  std::vector<int64_t> pos(rp.begin(), rp.end() - 1);
+  for (int64_t i = r0; i < r0 + nloc; ++i)
+    for (int64_t p = row_ptr[i] - index_base; p < row_ptr[i + 1] - index_base; ++p) {
+      const size_t q = (size_t)pos[(size_t)(i - r0)]++;
+      lcol[q] = (int32_t)(col_idx[p] - index_base);
+      lval[q] = vals[p];
+    }
+  if (lower)
+    for (int64_t i = 0; i < n; ++i)
+      for (int64_t p = row_ptr[i] - index_base; p < row_ptr[i + 1] - index_base; ++p) {
+        const int64_t j = (int64_t)col_idx[p] - index_base;
+        if (j < i && local(j)) {
+          const size_t q = (size_t)pos[(size_t)(j - r0)]++;
+          lcol[q] = (int32_t)i;
+          lval[q] = vals[p];
+        }
+      }
+  std::vector<std::pair<int32_t, double>> row;
+  for (int64_t i = 0; i < nloc; ++i) {
+    const size_t a = (size_t)rp[(size_t)i], b = (size_t)rp[(size_t)i + 1];
+    if (std::is_sorted(lcol.begin() + a, lcol.begin() + b)) continue;
+    row.clear();
+    for (size_t q = a; q < b; ++q) row.push_back({lcol[q], lval[q]});
+    std::stable_sort(row.begin(), row.end(), [](const std::pair<int32_t, double>& x, const std::pair<int32_t, double>& y) { return x.first < y.first; });
+    for (size_t q = a; q < b; ++q) { lcol[q] = row[q - a].first; lval[q] = row[q - a].second; }
+  }
+  // the diagonal of the whole matrix, from the global arrays: duplicates summed in input order, a missing entry counts as 0
+  std::vector<double> diag((size_t)n, 0.0);
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t p = row_ptr[i] - index_base; p < row_ptr[i + 1] - index_base; ++p)
+      if ((int64_t)col_idx[p] - index_base == i) diag[(size_t)i] += vals[p];
+  std::vector<CsrItem> items;
+  std::vector<CsrLong> longs;
+  int nslots = 0;
+  csr_build_items(rp, items, longs, &nslots);
+  // ---- device copies (the engine's allocator; released when the operator is set again and at dav_destroy)
+  HIPCHK(hipStreamSynchronize(e->stream));
+  sym_resident_release(o);
+  csr_release(e, o);
+  o.kind = DAV_KIND_NONE;
+  auto upload = [&](auto** dst, const auto* src, size_t count) -> int {
+    const size_t bytes = sizeof(**dst) * std::max<size_t>(count, 1);
+    if (pool_malloc(dst, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      *dst = nullptr;
+      return 1;
+    }
+    if (src && count > 0 && hipMemcpy(*dst, src, sizeof(**dst) * count, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return 1; }
+    return 0;
+  };
+  if (upload(&o.csr_rp, rp.data(), rp.size()) || upload(&o.csr_col, lcol.data(), lcol.size()) || upload(&o.csr_val, lval.data(), lval.size()) ||
+      upload(&o.csr_items, items.data(), items.size()) || upload(&o.csr_longs, longs.data(), longs.size()) ||
+      upload(&o.csr_part, (const double*)nullptr, (size_t)nslots * 64))
+    return refuse("device memory for " + std::to_string(lnnz) + " entries of this rank (" + std::to_string((12 * lnnz + 8 * nloc) >> 20) +
+                  " MiB) could not be allocated");
+  o.csr_nitems = (int)items.size();
+  o.csr_nlong = (int)longs.size();
+  o.csr_nnz = lnnz;
+  o.storage = 0;
+  if (nloc > 0) HIPCHK(hipMemcpy(o.diag, diag.data() + r0, sizeof(double) * nloc, hipMemcpyHostToDevice));
+  e->diag_host[which].swap(diag);
+  if (which == DAV_OP_A) e->basis_order.clear();
+  o.kind = DAV_KIND_CSR;
   return 0;
 }
 

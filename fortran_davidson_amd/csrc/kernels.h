@@ -176,6 +176,20 @@ void launch_gather_columns_sym(hipStream_t st, const double* tiles, const int64_
 void launch_chunk_to_panel(hipStream_t st, const double* src, int64_t lds, int64_t nloc, int64_t nrows_pad, int k, double* dst, int64_t ldd,
                            bool accumulate = false);
 
+// ---- K1c: CSR block product (k_spmm.hip) ----------------------------------------------------------------------------------------------
+// Y[rows of this rank, 0:kk] = A_csr * X.  Work list built on the host (engine_operators.hip: csr_build_items), one WAVE per item: a run
+// of at most CSR_ROWS consecutive whole rows with at most CSR_CHUNK entries together (slot < 0: written to the panel), or one chunk
+// of CSR_CHUNK entries of a longer row (slot >= 0: the partial row goes to part[slot][0:64]; launch_spmm_csr_finish adds a row's
+// chunks in chunk order).  Every row's sum depends only on its canonical entries, CSR_CHUNK and the launch's column groups.
+constexpr int CSR_ROWS = 16;
+constexpr int64_t CSR_CHUNK = 1024;   // fixed for every matrix and rank count (multiple of 4 * unroll): the chunk boundaries of a long row
+struct CsrItem { int64_t p0, p1; int32_t row, nrows, slot, pad; };
+struct CsrLong { int32_t row, first, count, pad; };   // a row longer than CSR_CHUNK: its partials are slots [first, first + count)
+// groups = column groups of 16 read per launch (1, 2 or 4); rows [0, nloc) of dst are written, padding rows are not touched
+void launch_spmm_csr(hipStream_t st, const CsrItem* items, int nitems, const int64_t* rp, const int32_t* col, const double* val,
+                     const double* xt, int64_t xt_gstride, int groups, int kk, double* part, double* dst, int64_t ldd);
+void launch_spmm_csr_finish(hipStream_t st, const CsrLong* longs, int nlong, const double* part, int kk, double* dst, int64_t ldd);
+
 // ---- device-side Rayleigh-Ritz (k_smalleig.hip): all eigenpairs of H y = theta y / H y = theta S y, order m <= 128 ------
 size_t small_eig_work_doubles(int m);
 bool launch_small_eig(hipStream_t st, const double* H, int64_t ldh, const double* S, int64_t lds, int m, bool gev, double* theta,

@@ -36,11 +36,62 @@ class Stats(C.Structure):
                 ("b_stored_launches", C.c_int64), ("b_generated_launches", C.c_int64)]
 
 
-ABI_VERSION = 108      # DAV_HIP_ABI_VERSION of include/davidson_hip.h this module mirrors
+ABI_VERSION = 109      # DAV_HIP_ABI_VERSION of include/davidson_hip.h this module mirrors
 
 
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+CSR_FULL, CSR_LOWER = 0, 1
+
+
+def csr_arrays(indptr, indices=None, data=None, n=None):
+    """(indptr int64, indices int32, data float64) of a CSR matrix given as three arrays or as one object with .tocsr() (a scipy
+    sparse matrix; scipy itself is never imported here).  Checks only what keeps the C call inside the arrays: n + 1 offsets, at least
+    indptr[-1] - indptr[0] entries."""
+    if hasattr(indptr, "tocsr"):
+        m = indptr.tocsr()
+        indptr, indices, data = m.indptr, m.indices, m.data
+    if indices is None or data is None:
+        raise DavidsonHipError("CSR input: indptr, indices and data are all needed (or one object with .tocsr())")
+    rp = np.ascontiguousarray(indptr, dtype=np.int64)
+    ci = np.ascontiguousarray(indices)
+    if ci.size and (ci.min() < -2**31 or ci.max() >= 2**31):
+        raise DavidsonHipError("CSR input: column indices do not fit int32")
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    vv = np.ascontiguousarray(data, dtype=np.float64)
+    if rp.ndim != 1 or (n is not None and rp.size != n + 1) or rp.size < 2:
+        raise DavidsonHipError(f"CSR input: indptr must hold n + 1 = {'?' if n is None else n + 1} offsets, it holds {rp.size}")
+    nnz = int(rp[-1] - rp[0])
+    if nnz < 0 or ci.size < nnz or vv.size < nnz:
+        raise DavidsonHipError(f"CSR input: indptr says {nnz} entries, indices / data hold {ci.size} / {vv.size}")
+    return rp, ci, vv
+
+
+def check_csr(indptr, indices, data, n, base=0, lower=False):
+    """Everything dav_set_operator_csr validates, checked in Python (ValueError) - for the Fortran doors, which stop the process on an
+    engine error.  Returns the arrays as csr_arrays does."""
+    try:
+        rp, ci, vv = csr_arrays(indptr, indices, data, n)
+    except DavidsonHipError as exc:
+        raise ValueError(str(exc)) from None
+    if base not in (0, 1):
+        raise ValueError("CSR input: index base must be 0 or 1")
+    if rp[0] != base:
+        raise ValueError(f"CSR input: indptr[0] = {rp[0]} must equal the index base {base}")
+    if np.any(np.diff(rp) < 0):
+        raise ValueError(f"CSR input: indptr decreases at row {int(np.argmax(np.diff(rp) < 0)) + base}")
+    nnz = int(rp[-1] - base)
+    cols = ci[:nnz].astype(np.int64) - base
+    if nnz and (cols.min() < 0 or cols.max() >= n):
+        raise ValueError(f"CSR input: column index out of range [{base}, {n + base})")
+    if lower and nnz:
+        rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(rp))
+        if np.any(cols > rows):
+            p = int(np.argmax(cols > rows))
+            raise ValueError(f"CSR input: entry ({rows[p] + base}, {cols[p] + base}) lies above the diagonal with lower=True")
+    return rp, ci, vv
 
 
 def _f(a):
@@ -193,6 +244,16 @@ class CEngine:
         self._device_ops = getattr(self, "_device_ops", {})
         self._device_ops[which] = (fn, ctx)                # keep the callback alive as long as the engine
         self._chk(self.lib.dav_set_operator_device(self.h, C.c_int(which), C.cast(fn, C.c_void_p), C.c_void_p(ctx if isinstance(ctx, int) else C.cast(ctx, C.c_void_p).value), _dp(d)))
+
+    def set_operator_csr(self, which, indptr, indices=None, data=None, base=0, lower=False):
+        """dav_set_operator_csr: a symmetric matrix in CSR form (the global arrays; indptr / indices numbered from `base`), every nonzero
+        (lower=False) or only the entries with column <= row (lower=True).  Three numpy arrays, or one object with .tocsr().  The
+        engine validates the input (DavidsonHipError) and leaves the operator unset when it refuses it."""
+        rp, ci, vv = csr_arrays(indptr, indices, data, self.n)
+        ci_p = ci.ctypes.data_as(C.POINTER(C.c_int32)) if ci.size else (C.c_int32 * 1)()
+        vv_p = _dp(vv) if vv.size else (C.c_double * 1)()
+        self._chk(self.lib.dav_set_operator_csr(self.h, C.c_int(which), rp.ctypes.data_as(C.POINTER(C.c_int64)), ci_p, vv_p, C.c_int(base),
+                                                C.c_int(CSR_LOWER if lower else CSR_FULL)))
 
     def get_diagonal(self, which):
         d = np.zeros(self.n)

@@ -7,6 +7,7 @@ module davidson_c_api
   use davidson, only: generalized_eigensolver
   use davidson_device
   use davidson_free, only: free_matmul
+  use davidson_sparse, only: csr_matrix, engine_set_sparse
   use lapack_wrapper
   use array_utils
   implicit none
@@ -56,6 +57,52 @@ contains
     end if
     iters = it
   end subroutine fd_dense_solve
+
+  !> A csr_matrix from C arrays (row_ptr: n + 1 int64 offsets, col_idx: int32) numbered from `base` (0 or 1): renumbered from 1
+  function csr_from_c(n, row_ptr, col_idx, vals, base, lower) result(a)
+    integer(c_int), intent(in) :: n, base, lower
+    integer(c_int64_t), intent(in) :: row_ptr(n + 1)
+    integer(c_int32_t), intent(in) :: col_idx(*)
+    real(c_double), intent(in) :: vals(*)
+    type(csr_matrix) :: a
+    integer(c_int64_t) :: nnz
+    nnz = row_ptr(n + 1) - base
+    a%n = n
+    a%row_ptr = row_ptr + (1 - base)
+    a%col_idx = col_idx(1:nnz) + int(1 - base, c_int32_t)
+    a%values = vals(1:nnz)
+    a%lower = lower /= 0
+  end function csr_from_c
+
+  !> generalized_eigensolver(a_csr, ...) - sparse specific.  max_dim < 0: argument absent; has_b: B given (same base and triangle).
+  subroutine fd_sparse_solve(n, rp, col, vals, has_b, rpb, colb, valsb, base, lower, lowest, method, max_it, tol, max_dim, evals, &
+       evecs, iters) bind(C, name="fd_sparse_solve")
+    integer(c_int), value :: n, has_b, base, lower, lowest, method, max_it, max_dim
+    integer(c_int64_t), intent(in) :: rp(n + 1), rpb(*)
+    integer(c_int32_t), intent(in) :: col(*), colb(*)
+    real(c_double), intent(in) :: vals(*), valsb(*)
+    real(c_double), value :: tol
+    real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
+    integer(c_int), intent(out) :: iters
+    type(csr_matrix) :: a, b
+    integer :: it
+    a = csr_from_c(n, rp, col, vals, base, lower)
+    if (has_b /= 0) then
+       b = csr_from_c(n, rpb, colb, valsb, base, lower)
+       if (max_dim >= 0) then
+          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, max_dim, b)
+       else
+          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, second_matrix=b)
+       end if
+    else
+       if (max_dim >= 0) then
+          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, max_dim)
+       else
+          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it)
+       end if
+    end if
+    iters = it
+  end subroutine fd_sparse_solve
 
   function apply_cb_a(input_vect) result(output_vect)
     real(dp), dimension(:, :), intent(in) :: input_vect
@@ -183,6 +230,18 @@ contains
     call c_f_pointer(c_loc(a), mat, [eng%n, eng%n])
     call engine_set_dense(eng, int(which), mat)
   end subroutine fd_engine_set_dense
+
+  !> engine_set_sparse(eng, which, a) with a csr_matrix from C arrays numbered from `base`
+  subroutine fd_engine_set_sparse(p, which, n, rp, col, vals, base, lower) bind(C, name="fd_engine_set_sparse")
+    type(c_ptr), value :: p
+    integer(c_int), value :: which, n, base, lower
+    integer(c_int64_t), intent(in) :: rp(n + 1)
+    integer(c_int32_t), intent(in) :: col(*)
+    real(c_double), intent(in) :: vals(*)
+    type(davidson_engine), pointer :: eng
+    call c_f_pointer(p, eng)
+    call engine_set_sparse(eng, int(which), csr_from_c(n, rp, col, vals, base, lower))
+  end subroutine fd_engine_set_sparse
 
   !> kind 0: dense generated in HBM, 1: hashed matrix-free operator, 2: harness operator, 3: identity
   subroutine fd_engine_set_operator(p, which, kind, seed, sparsity, use_diag_val, diag_val) &

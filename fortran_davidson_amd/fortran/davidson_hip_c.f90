@@ -11,6 +11,8 @@ module davidson_hip_c
   integer(c_int), parameter :: DAV_METHOD_DPR = 0, DAV_METHOD_GJD = 1, DAV_METHOD_NONE = 2
   !> dav_panel_unit_column: "the engine keeps no such entry of the start order" (not an error)
   integer(c_int), parameter :: DAV_NO_SUCH_ENTRY = 2
+  !> dav_set_operator_csr: every nonzero given / only j <= i given (the engine mirrors the strict lower part)
+  integer(c_int), parameter :: DAV_CSR_FULL = 0, DAV_CSR_LOWER = 1
 
   type, bind(C) :: dav_stats
      integer(c_int64_t) :: n, nloc
@@ -30,7 +32,7 @@ module davidson_hip_c
   end type dav_stats
   !> DAV_HIP_ABI_VERSION of include/davidson_hip.h these interfaces were written against: engine_create checks that the
   !> loaded libdavidson_hip.so reports the same number (the layout of dav_stats grew in 101, 102 and 104)
-  integer(c_int), parameter :: DAV_HIP_ABI_VERSION = 108
+  integer(c_int), parameter :: DAV_HIP_ABI_VERSION = 109
 
   interface
      function dav_last_error() bind(C, name="dav_last_error") result(p)
@@ -165,6 +167,18 @@ module davidson_hip_c
        type(c_funptr), value :: fn
        type(c_ptr), value :: ctx
        real(c_double), intent(in) :: diag(*)
+       integer(c_int) :: ierr
+     end function
+     !> a symmetric matrix in CSR form, global host arrays (ABI 109); index_base 1 = Fortran numbering of rows and columns
+     function dav_set_operator_csr(h, which, row_ptr, col_idx, vals, index_base, triangle) bind(C, name="dav_set_operator_csr") &
+          result(ierr)
+       import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+       type(c_ptr), value :: h
+       integer(c_int), value :: which
+       integer(c_int64_t), intent(in) :: row_ptr(*)
+       integer(c_int32_t), intent(in) :: col_idx(*)
+       real(c_double), intent(in) :: vals(*)
+       integer(c_int), value :: index_base, triangle
        integer(c_int) :: ierr
      end function
      function dav_set_operator_host(h, which, diag) bind(C, name="dav_set_operator_host") result(ierr)

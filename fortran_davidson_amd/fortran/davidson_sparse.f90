@@ -1,0 +1,76 @@
+!> Sparse operators: a symmetric real matrix in CSR (compressed sparse row) form, 1-based as Fortran numbers rows and columns, and
+!> engine_set_sparse, which hands it to a device-resident problem (dav_set_operator_csr, include/davidson_hip.h).  The solve of a
+!> csr_matrix is the specific generalized_eigensolver_sparse of the generic generalized_eigensolver (module davidson).
+module davidson_sparse
+  use, intrinsic :: iso_c_binding
+  use numeric_kinds, only: dp
+  use davidson_hip_c
+  use davidson_engine_setup, only: davidson_engine
+  implicit none
+  private
+  public :: csr_matrix, engine_set_sparse
+
+  !> A symmetric real matrix of order n in CSR form, 1-based: the entries of row i are col_idx / values(row_ptr(i) : row_ptr(i+1) - 1).
+  !> lower = .true.: only the entries with column <= row are given (the engine mirrors the strict lower part); .false.: every nonzero
+  !> is given, and the matrix being symmetric is the caller's promise, as for a dense matrix.
+  type :: csr_matrix
+     integer :: n = 0
+     integer(c_int64_t), allocatable :: row_ptr(:)
+     integer(c_int32_t), allocatable :: col_idx(:)
+     real(dp), allocatable :: values(:)
+     logical :: lower = .false.
+  end type csr_matrix
+
+  !> csr_matrix(n, row_ptr, col_idx, values [, lower]) from default-kind integer arrays, 1-based
+  interface csr_matrix
+     module procedure new_csr_matrix
+  end interface csr_matrix
+
+contains
+
+  function new_csr_matrix(n, row_ptr, col_idx, values, lower) result(a)
+    integer, intent(in) :: n
+    integer, intent(in) :: row_ptr(:), col_idx(:)
+    real(dp), intent(in) :: values(:)
+    logical, intent(in), optional :: lower
+    type(csr_matrix) :: a
+    if (size(row_ptr) /= n + 1) then
+       print *, "csr_matrix: row_ptr must hold n + 1 = ", n + 1, " offsets, not ", size(row_ptr)
+       error stop
+    end if
+    if (size(col_idx) < row_ptr(n + 1) - 1 .or. size(values) < row_ptr(n + 1) - 1) then
+       print *, "csr_matrix: row_ptr(n + 1) - 1 = ", row_ptr(n + 1) - 1, " entries, but col_idx / values hold ", size(col_idx), &
+            " / ", size(values)
+       error stop
+    end if
+    a%n = n
+    a%row_ptr = int(row_ptr, c_int64_t)
+    a%col_idx = int(col_idx, c_int32_t)
+    a%values = values
+    if (present(lower)) a%lower = lower
+  end function new_csr_matrix
+
+  !> Operator A (which = 1) or B (which = 2) of the engine from a csr_matrix: the engine keeps the rows of its slab in HBM and applies
+  !> them with its own CSR kernel.  The matrix is not referenced after the call.
+  subroutine engine_set_sparse(eng, which, a)
+    type(davidson_engine), intent(inout) :: eng
+    integer, intent(in) :: which
+    type(csr_matrix), intent(in) :: a
+    real(dp) :: nothing(1)
+    if (a%n /= eng%n .or. .not. allocated(a%row_ptr)) then
+       print *, "engine_set_sparse: the matrix must be of order ", eng%n
+       error stop
+    end if
+    if (size(a%values) > 0) then
+       call check_dav(dav_set_operator_csr(eng%h, int(which - 1, c_int), a%row_ptr, a%col_idx, a%values, 1_c_int, &
+            merge(DAV_CSR_LOWER, DAV_CSR_FULL, a%lower)), "dav_set_operator_csr")
+    else
+       nothing = 0.0_dp
+       call check_dav(dav_set_operator_csr(eng%h, int(which - 1, c_int), a%row_ptr, [0_c_int32_t], nothing, 1_c_int, &
+            merge(DAV_CSR_LOWER, DAV_CSR_FULL, a%lower)), "dav_set_operator_csr")
+    end if
+    ! a stored matrix: the dense driver's sticky convergence flags, as for engine_set_dense
+    if (which == 1) eng%free_semantics = .false.
+  end subroutine engine_set_sparse
+
+end module davidson_sparse

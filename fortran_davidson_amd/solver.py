@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import fortran_lib
-from .engine_c import CEngine
+from .engine_c import CEngine, check_csr
 
 _METHOD = {"DPR": 0, "GJD": 1}
 _CB = C.CFUNCTYPE(None, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
@@ -46,6 +46,48 @@ def generalized_eigensolver(matrix, lowest, method, max_iterations, tolerance, m
     lib.fd_dense_solve(C.c_int(n), _dp(a), C.c_int(0 if second_matrix is None else 1), _dp(b), C.c_int(lowest),
                        C.c_int(_METHOD.get(method, 2)), C.c_int(max_iterations), C.c_double(tolerance),
                        C.c_int(-1 if max_dim_sub is None else max_dim_sub), _dp(evals), _dp(evecs), C.byref(iters))
+    return evals, evecs, iters.value
+
+
+def _i64(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _i32(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32)) if a.size else (C.c_int32 * 1)()
+
+
+def _sparse_input(a, n=None, lower=False):
+    """(n, indptr, indices, data) of a CSR operator given as a tuple (indptr, indices, data) or an object with .tocsr(), 0-based,
+    validated here (ValueError) - the Fortran door stops the process on an engine error"""
+    if hasattr(a, "tocsr"):
+        m = a.tocsr()
+        a = (m.indptr, m.indices, m.data)
+    indptr, indices, data = a
+    n = len(indptr) - 1 if n is None else n
+    rp, ci, vv = check_csr(indptr, indices, data, n, 0, lower)
+    return n, rp, ci, vv if vv.size else np.zeros(1)
+
+
+def generalized_eigensolver_sparse(indptr, indices, data, lowest, method, max_iterations, tolerance, max_dim_sub=None, second=None,
+                                   lower=False):
+    """`call generalized_eigensolver(a_csr, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters [, max_dim_sub]
+    [, b_csr])` (the csr_matrix specific of module davidson) with A in CSR form, 0-based: three arrays, or `indptr` an object with
+    .tocsr() and indices = data = None.  `second`: B the same way - a tuple (indptr, indices, data) or an object with .tocsr().
+    lower=True: only the entries with column <= row are given, for A and B.  Returns (eigenvalues, eigenvectors, iters)."""
+    a = indptr if indices is None and data is None else (indptr, indices, data)
+    n, rp, ci, vv = _sparse_input(a, None, lower)
+    if second is not None:
+        _, rpb, cib, vvb = _sparse_input(second, n, lower)
+    else:
+        rpb, cib, vvb = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int32), np.zeros(1)
+    evals = np.zeros(lowest)
+    evecs = np.zeros((n, lowest), order="F")
+    iters = C.c_int(-1)
+    fortran_lib().fd_sparse_solve(C.c_int(n), _i64(rp), _i32(ci), _dp(vv), C.c_int(0 if second is None else 1), _i64(rpb), _i32(cib),
+                                  _dp(vvb), C.c_int(0), C.c_int(1 if lower else 0), C.c_int(lowest), C.c_int(_METHOD.get(method, 2)),
+                                  C.c_int(max_iterations), C.c_double(tolerance), C.c_int(-1 if max_dim_sub is None else max_dim_sub),
+                                  _dp(evals), _dp(evecs), C.byref(iters))
     return evals, evecs, iters.value
 
 
@@ -108,6 +150,14 @@ class DavidsonEngine:
         a = _f(matrix)
         assert a.shape == (self.n, self.n)
         self.lib.fd_engine_set_dense(self.p, C.c_int(which), _dp(a))
+
+    def set_sparse(self, which, indptr, indices=None, data=None, lower=False):
+        """Operator A (which=1) or B (which=2) as a symmetric matrix in CSR form, 0-based (Fortran: engine_set_sparse): three arrays,
+        or `indptr` an object with .tocsr().  lower=True: only the entries with column <= row are given."""
+        a = indptr if indices is None and data is None else (indptr, indices, data)
+        _, rp, ci, vv = _sparse_input(a, self.n, lower)
+        self.lib.fd_engine_set_sparse(self.p, C.c_int(which), C.c_int(self.n), _i64(rp), _i32(ci), _dp(vv), C.c_int(0),
+                                      C.c_int(1 if lower else 0))
 
     def set_correction_policy(self, policy):
         """"all" = the reference's policy (default); "unconverged" = opt-in: correct only the wanted pairs

@@ -54,13 +54,15 @@ typedef struct dav_stats {
   double apply_ms;         /* device time of the A*X block applies END TO END (HIP events): operand   */
                            /* packing + (all-gather) + block-matvec kernel + partial-sum reduction   */
   double apply_bytes;      /* algorithmic bytes of those applies: 8*S + 16*N*k each, S = nloc*N      */
-                           /* (full row slab) or N(N+1)/2 (symmetric-tiled)                          */
+                           /* (full row slab) or N(N+1)/2 (symmetric-tiled); a CSR operator:         */
+                           /* 12*nnz_loc + 8*(nloc+1) + 8*N*k + 8*nloc*k (entries, row offsets,      */
+                           /* the gathered block read once, the rank's rows written)                 */
   double last_apply_ms;    /* duration of the most recent A apply (end to end)                      */
   double last_apply_bytes;
   double gram_ms, panel_ms, comm_ms;
   double apply_kernel_ms;  /* the block-matvec kernel alone inside apply_ms (same launches)          */
   double apply_flops;      /* 2*nloc*N*k per apply and rank (2*N*N*k / nranks with symmetric tiles:  */
-                           /* every stored entry is used twice)                                      */
+                           /* every stored entry is used twice; 2*nnz_loc*k with a CSR operator)     */
   int64_t apply_launches;  /* launches of the block-matvec kernel (an apply of > 32 / 64 columns is  */
                            /* several launches)                                                      */
   int64_t restarts;        /* collapse restarts (dav_restart / dav_rr_restart) so far                */
@@ -83,9 +85,9 @@ typedef struct dav_stats {
 } dav_stats;
 
 /* ABI version of this header.  dav_version() of the loaded library must return the same number: a     */
-/* caller built against another layout of the statistics structure (it grew in 101 and 102; 103 added dav_device_memory, 104 dav_agree_next, 105 dav_free_buffers, 106 dav_set_operator_device, 107 DAV_NO_SUCH_ENTRY, 108 dav_comm_path) must not    */
+/* caller built against another layout of the statistics structure (it grew in 101 and 102; 103 added dav_device_memory, 104 dav_agree_next, 105 dav_free_buffers, 106 dav_set_operator_device, 107 DAV_NO_SUCH_ENTRY, 108 dav_comm_path, 109 dav_set_operator_csr) must not    */
 /* use the unsized call - the sized one, which copies at most `bytes` bytes, is safe across versions.   */
-#define DAV_HIP_ABI_VERSION 108
+#define DAV_HIP_ABI_VERSION 109
 const char* dav_last_error(void);
 int dav_version(void);
 
@@ -199,6 +201,23 @@ int dav_set_operator_host(dav_handle_t h, int which, const double* diag);
 typedef int (*dav_device_apply_fn)(void* ctx, void* hip_stream, int64_t n, int64_t row0, int64_t nloc, int k, const double* x_dev, int64_t ldx,
                                    double* y_dev, int64_t ldy);
 int dav_set_operator_device(dav_handle_t h, int which, dav_device_apply_fn fn, void* ctx, const double* diag);
+/* A symmetric real matrix in CSR (compressed sparse row) form (ABI 109).  Host pointers to the GLOBAL matrix - every rank passes the same
+ * arrays, as with dav_set_dense_host, and keeps the rows of its slab [row0, row0 + nloc) - with row_ptr[0..n] (int64: more than 2^31
+ * entries are allowed), col_idx and vals of the row_ptr[n] - index_base entries; index_base = 1 is the Fortran convention and applies to
+ * both row_ptr and col_idx.  DAV_CSR_FULL: every nonzero of the matrix is given - its symmetry is the CALLER'S PROMISE, as for a dense
+ * matrix, and is not checked; DAV_CSR_LOWER: only entries with j <= i are given and the engine mirrors the strict lower part.  The input
+ * is validated before anything is allocated or launched: row_ptr starts at the base and never decreases, every column lies in range, no
+ * entry lies above the diagonal with DAV_CSR_LOWER, n < 2^31; a call that fails returns non-zero (dav_last_error says why) and leaves the
+ * operator UNSET - the engine stays usable and takes a later valid call.  Within a row the entries are sorted by column (stable; with
+ * DAV_CSR_LOWER after the mirrored entries have joined their rows); duplicate entries stay separate terms of the sum.  The diagonal
+ * (duplicates summed, a missing entry counts as 0) is taken from the arrays on the host, for dav_init_basis, the DPR preconditioner and
+ * dav_get_diagonal.  Device storage per rank: int64 row offsets, int32 columns, fp64 values, released when the operator is set again and
+ * at dav_destroy.  The block product is the engine's own kernel and bitwise reproducible: the same bits for every rank count and every
+ * repetition (not necessarily for another block width).  The sweeps inside the GJD correction solve stay fp64 on a CSR operator
+ * (dav_set_inner_precision(32) does not apply to it).  The caller's arrays are not referenced after the call returns. */
+enum { DAV_CSR_FULL = 0, DAV_CSR_LOWER = 1 };
+int dav_set_operator_csr(dav_handle_t h, int which, const int64_t* row_ptr /* n+1 */, const int32_t* col_idx, const double* vals,
+                         int index_base /* 0 or 1 */, int triangle);
 int dav_get_diagonal(dav_handle_t h, int which, double* diag_out /* n, global */);
 
 /* ---- the per-iteration hot path ---------------------------------------------------------------- */
