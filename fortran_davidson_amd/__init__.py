@@ -12,7 +12,8 @@ This Python package is only the harness side (tests, bench, multi-GPU launch plu
 the Fortran API through ctypes.  There is no CPU fallback anywhere: importing works without a GPU,
 any compute call without one raises.
 """
-from .solver import (DavidsonEngine, generalized_eigensolver, generalized_eigensolver_sparse, generate_diagonal_dominant,  # noqa: F401
+from .solver import (DavidsonEngine, generalized_eigensolver, generalized_eigensolver_bsr, generalized_eigensolver_sparse,  # noqa: F401
+                     generate_diagonal_dominant,
                      lapack_generalized_eigensolver, lapack_qr, lapack_sort, generate_preconditioner,
                      lapack_matmul, lapack_solver, norm)
 from .engine_c import CEngine, DavidsonHipError, free_buffers  # noqa: F401

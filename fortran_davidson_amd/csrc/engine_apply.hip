@@ -524,6 +524,42 @@ int apply_ptr(E* e, int which, const double* src, int k, double* dst, bool timed
     HIPCHK(hipGetLastError());
     return 0;
   }
+  if (o.kind == DAV_KIND_BSR) {
+    // BSR block rows touching this rank's slab (k_bsrmm.hip): the same packed, gathered operand as CSR, then one launch of the
+    // matrix-core kernel per 64 columns and the chunk sums of the long block rows.  Always fp64, as CSR.
+    for (int c = 0; c < k; c += 64) {
+      const int kk = std::min(64, k - c), groups = (kk + 15) / 16, gp = groups == 3 ? 4 : groups;
+      int slot = -1, kslot = -1;
+      const double bb = (double)o.bsr_b * o.bsr_b;
+      const double bytes = 8.0 * bb * (double)o.bsr_nnzb + 4.0 * (double)o.bsr_nnzb + 8.0 * (double)(o.bsr_nbl + 1) + 8.0 * (double)e->n * kk +
+                           8.0 * (double)e->nloc * kk;
+      if (timed) CHK(timed_begin(e, which == DAV_OP_A ? 0 : 2, bytes, &slot));
+      launch_pack_xt(e->stream, src + (int64_t)c * e->ldp, e->ldp, e->nloc, e->nslab, kk, e->xt, e->xt_group_stride, e->row0);
+      if (has_comm(e)) {
+        CollGroup grp(e);
+        CHK(grp.begin(5, 8.0 * (double)e->nslab * 16 * groups * e->nranks));
+        for (int g = 0; g < groups; ++g) {
+          double* base = e->xt + g * e->xt_group_stride;
+          CHK(coll_allgather(e, base + e->row0 * 16, base, (size_t)e->nslab * 16));
+        }
+        CHK(grp.end("all-gather of the new block", e->stream));
+      }
+      double* out = dst + (int64_t)c * e->ldp;
+      if (timed && which == DAV_OP_A) CHK(timed_begin(e, 4, 2.0 * bb * (double)o.bsr_nnzb * kk, &kslot));
+      launch_spmm_bsr(e->stream, o.bsr_items, o.bsr_nitems, o.bsr_b, o.bsr_rp, o.bsr_col, o.bsr_val, e->xt, e->xt_group_stride, gp, kk,
+                      o.bsr_part, out, e->ldp, o.bsr_grow0, e->nloc);
+      launch_spmm_bsr_finish(e->stream, o.bsr_longs, o.bsr_nlong, o.bsr_part, o.bsr_b, kk, out, e->ldp, o.bsr_grow0, e->nloc);
+      CHK(timed_end(e, kslot));
+      launch_zero_pad_rows(e->stream, out, e->ldp, e->nloc, e->nloc_pad, kk);
+      CHK(timed_end(e, slot));
+      if (which == DAV_OP_A) {
+        e->st.applies += 1;
+        e->st.apply_cols += kk;
+      }
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   if ((o.kind == DAV_KIND_DENSE || o.kind == DAV_KIND_HASHED || o.kind == DAV_KIND_HARNESS) && o.storage == 1) {
     // A generated second operator whose tiles (partly) fit next to everything else is kept resident for its longest block rows
     // (configs[3]: B = the unit-diagonal generator next to a stored A): those rows run the stored kernels - half the time per
@@ -676,6 +712,15 @@ extern "C" int dav_bench_apply2(dav_handle_t e, int which, int k, int reps, doub
     const OpDesc& o = e->op[which];
     *bytes = 12.0 * (double)o.csr_nnz + 8.0 * (double)(e->nloc + 1) + 8.0 * (double)e->n * k + 8.0 * (double)e->nloc * k;
     *flops = 2.0 * (double)o.csr_nnz * k;
+    e->st = saved;
+    return 0;
+  }
+  if (e->op[which].kind == DAV_KIND_BSR) {     // the BSR byte model of apply_ptr
+    const OpDesc& o = e->op[which];
+    const double bb = (double)o.bsr_b * o.bsr_b;
+    *bytes = 8.0 * bb * (double)o.bsr_nnzb + 4.0 * (double)o.bsr_nnzb + 8.0 * (double)(o.bsr_nbl + 1) + 8.0 * (double)e->n * k +
+             8.0 * (double)e->nloc * k;
+    *flops = 2.0 * bb * (double)o.bsr_nnzb * k;
     e->st = saved;
     return 0;
   }

@@ -154,6 +154,16 @@ struct OpDesc {
   double* csr_part = nullptr;       // device: 64 doubles per chunk of a long row
   int csr_nitems = 0, csr_nlong = 0;
   int64_t csr_nnz = 0;              // entries of this rank's rows
+  // DAV_KIND_BSR (dav_set_operator_bsr): the block rows touching this rank's slab in canonical form, blocks column-major (k_bsrmm.hip)
+  int64_t* bsr_rp = nullptr;        // device: nbl + 1 block offsets from 0 over the local block rows
+  int32_t* bsr_col = nullptr;       // device: global block column of each block
+  double* bsr_val = nullptr;        // device: b * b values of each block, column-major
+  CsrItem* bsr_items = nullptr;     // device: one item per wave (runs of whole block rows, chunks of long block rows)
+  CsrLong* bsr_longs = nullptr;     // device: the block rows longer than BSR_CHUNK and their partial slots
+  double* bsr_part = nullptr;       // device: 16 x 64 doubles per chunk of a long block row
+  int bsr_nitems = 0, bsr_nlong = 0, bsr_b = 0;
+  int64_t bsr_nnzb = 0, bsr_nbl = 0;  // blocks and block rows of this rank
+  int64_t bsr_grow0 = 0;            // local row of the first row of local block row 0 (<= 0)
 };
 
 struct SmallBuf {            // device small matrix + pinned staging
@@ -430,6 +440,7 @@ int ingest_commit(E* e, int64_t row0, int64_t nrows);
 void ingest_wanted(E* e, int64_t* first, int64_t* count);
 OpParams op_params(const OpDesc& o);
 void csr_release(E* e, OpDesc& o);
+void bsr_release(E* e, OpDesc& o);
 // ---- engine_apply.hip ------------------------------------------------------------------------------------
 bool inner_f32_tiles(E* e, OpDesc& o);
 bool sym_wide_enabled(const E* e);

@@ -599,7 +599,9 @@ extern "C" int dav_set_operator_device(dav_handle_t e, int which, dav_device_app
 }
 
 // ---- a symmetric matrix in CSR form (dav_set_operator_csr) ---------------------------------------------------------------------------
+// (the arrays of a BSR operator too: every path that sets an operator releases both kinds)
 void csr_release(E* e, OpDesc& o) {
+  bsr_release(e, o);
   if (!o.csr_rp && !o.csr_col && !o.csr_val && !o.csr_items && !o.csr_longs && !o.csr_part) return;
   (void)hipStreamSynchronize(e->stream);         // applies in flight may still read the arrays
   pool_free(o.csr_rp); pool_free(o.csr_col); pool_free(o.csr_val);
@@ -608,6 +610,17 @@ void csr_release(E* e, OpDesc& o) {
   o.csr_items = nullptr; o.csr_longs = nullptr; o.csr_part = nullptr;
   o.csr_nitems = o.csr_nlong = 0;
   o.csr_nnz = 0;
+}
+
+void bsr_release(E* e, OpDesc& o) {
+  if (!o.bsr_rp && !o.bsr_col && !o.bsr_val && !o.bsr_items && !o.bsr_longs && !o.bsr_part) return;
+  (void)hipStreamSynchronize(e->stream);
+  pool_free(o.bsr_rp); pool_free(o.bsr_col); pool_free(o.bsr_val);
+  pool_free(o.bsr_items); pool_free(o.bsr_longs); pool_free(o.bsr_part);
+  o.bsr_rp = nullptr; o.bsr_col = nullptr; o.bsr_val = nullptr;
+  o.bsr_items = nullptr; o.bsr_longs = nullptr; o.bsr_part = nullptr;
+  o.bsr_nitems = o.bsr_nlong = o.bsr_b = 0;
+  o.bsr_nnzb = o.bsr_nbl = o.bsr_grow0 = 0;
 }
 
 // Work list of the block product over the canonical local rows rp[0..nloc]: runs of at most CSR_ROWS whole rows with at most CSR_CHUNK
@@ -751,6 +764,180 @@ extern "C" int dav_set_operator_csr(dav_handle_t e, int which, const int64_t* ro
   e->diag_host[which].swap(diag);
   if (which == DAV_OP_A) e->basis_order.clear();
   o.kind = DAV_KIND_CSR;
+  return 0;
+}
+
+// ---- a symmetric matrix in BSR form (dav_set_operator_bsr) ---------------------------------------------------------------------------
+// Work list of the block product over the canonical local block rows rp[0..nbl]: runs of whole block rows of at most BSR_ROWS matrix rows
+// and BSR_CHUNK blocks together, every block row longer than BSR_CHUNK cut into chunks at multiples of BSR_CHUNK from its first block.
+static void bsr_build_items(const std::vector<int64_t>& rp, int b, std::vector<CsrItem>& items, std::vector<CsrLong>& longs, int* nslots) {
+  const int64_t nbl = (int64_t)rp.size() - 1;
+  const int max_rows = std::max(1, BSR_ROWS / b);
+  CsrItem cur{0, 0, 0, 0, -1, 0};
+  int slots = 0;
+  auto flush = [&]() { if (cur.nrows > 0) items.push_back(cur); cur.nrows = 0; };
+  for (int64_t i = 0; i < nbl; ++i) {
+    const int64_t a = rp[(size_t)i], e = rp[(size_t)i + 1];
+    if (e - a > BSR_CHUNK) {
+      flush();
+      const int first = slots;
+      for (int64_t q = a; q < e; q += BSR_CHUNK) items.push_back({q, std::min(e, q + BSR_CHUNK), (int32_t)i, 1, slots++, 0});
+      longs.push_back({(int32_t)i, first, slots - first, 0});
+      continue;
+    }
+    if (cur.nrows > 0 && (cur.nrows == max_rows || e - cur.p0 > BSR_CHUNK)) flush();
+    if (cur.nrows == 0) { cur.p0 = a; cur.row = (int32_t)i; }
+    cur.p1 = e;
+    cur.nrows += 1;
+  }
+  flush();
+  *nslots = slots;
+}
+
+extern "C" int dav_set_operator_bsr(dav_handle_t e, int which, int block_size, const int64_t* block_row_ptr, const int32_t* block_col_idx,
+                                    const double* vals, int index_base, int triangle, int block_layout) {
+  if (!e) return fail("dav_set_operator_bsr: null engine");
+  if (which < 0 || which > 1) return fail("dav_set_operator_bsr: bad operator id");
+  CHK(bind(e));
+  OpDesc& o = e->op[which];
+  // a call that fails leaves the operator unset (the engine stays usable: set it again)
+  auto refuse = [&](const std::string& msg) {
+    csr_release(e, o);
+    o.kind = DAV_KIND_NONE;
+    e->diag_host[which].clear();
+    if (which == DAV_OP_A) e->basis_order.clear();
+    return fail("dav_set_operator_bsr: " + msg);
+  };
+  const int64_t n = e->n;
+  const int b = block_size;
+  // ---- validation of the caller's global arrays: before anything is allocated or launched
+  if (b < 1 || b > 16) return refuse("block_size = " + std::to_string(b) + " must lie in 1..16");
+  if (n % b != 0) return refuse("n = " + std::to_string(n) + " is not a multiple of block_size = " + std::to_string(b));
+  const int64_t nb = n / b;
+  if (nb >= ((int64_t)1 << 31)) return refuse("n / block_size must be below 2^31 (int32 block columns)");
+  if (index_base != 0 && index_base != 1) return refuse("index_base must be 0 or 1");
+  if (triangle != DAV_CSR_FULL && triangle != DAV_CSR_LOWER) return refuse("triangle must be DAV_CSR_FULL or DAV_CSR_LOWER");
+  if (block_layout != DAV_BSR_ROW_MAJOR && block_layout != DAV_BSR_COL_MAJOR) return refuse("block_layout must be DAV_BSR_ROW_MAJOR or DAV_BSR_COL_MAJOR");
+  if (!block_row_ptr) return refuse("null block_row_ptr");
+  const int64_t* rpg = block_row_ptr;
+  if (rpg[0] != index_base) return refuse("block_row_ptr[0] = " + std::to_string(rpg[0]) + " must equal the index base " + std::to_string(index_base));
+  for (int64_t I = 0; I < nb; ++I)
+    if (rpg[I + 1] < rpg[I]) return refuse("block_row_ptr decreases at block row " + std::to_string(I + index_base));
+  const int64_t nnzb = rpg[nb] - index_base;
+  if (nnzb > 0 && (!block_col_idx || !vals)) return refuse("null block_col_idx or vals");
+  const bool lower = triangle == DAV_CSR_LOWER;
+  for (int64_t I = 0; I < nb; ++I)
+    for (int64_t p = rpg[I] - index_base; p < rpg[I + 1] - index_base; ++p) {
+      const int64_t J = (int64_t)block_col_idx[p] - index_base;
+      if (J < 0 || J >= nb)
+        return refuse("block column " + std::to_string(block_col_idx[p]) + " out of range at block " + std::to_string(p + index_base) +
+                      " (block row " + std::to_string(I + index_base) + ")");
+      if (lower && J > I)
+        return refuse("block (" + std::to_string(I + index_base) + ", " + std::to_string(block_col_idx[p]) + ") lies above the diagonal of a "
+                      "DAV_CSR_LOWER matrix");
+    }
+  // entry (m, k) of input block p in the caller's layout
+  const int64_t bb = (int64_t)b * b;
+  const bool rowmaj = block_layout == DAV_BSR_ROW_MAJOR;
+  auto entry = [&](int64_t p, int m, int k) { return vals[p * bb + (rowmaj ? (int64_t)m * b + k : (int64_t)k * b + m)]; };
+  // ---- canonical block rows touching this rank's slab [row0, row0 + nloc): own blocks in input order, then (DAV_CSR_LOWER) the mirrored
+  // strict lower blocks in the order of their source block rows; stable sort by block column (duplicates stay separate terms)
+  const int64_t r0 = e->row0, nloc = e->nloc;
+  const int64_t ib0 = nloc > 0 ? r0 / b : 0, ib1 = nloc > 0 ? (r0 + nloc + b - 1) / b : 0, nbl = ib1 - ib0;
+  auto local = [&](int64_t I) { return I >= ib0 && I < ib1; };
+  std::vector<int64_t> rp((size_t)nbl + 1, 0);
+  for (int64_t I = ib0; I < ib1; ++I) rp[(size_t)(I - ib0) + 1] = rpg[I + 1] - rpg[I];
+  if (lower)
+    for (int64_t I = 0; I < nb; ++I)
+      for (int64_t p = rpg[I] - index_base; p < rpg[I + 1] - index_base; ++p) {
+        const int64_t J = (int64_t)block_col_idx[p] - index_base;
+        if (J < I && local(J)) rp[(size_t)(J - ib0) + 1] += 1;
+      }
+  for (int64_t i = 0; i < nbl; ++i) rp[(size_t)i + 1] += rp[(size_t)i];
+  const int64_t lnnzb = rp[(size_t)nbl];
+  // source of each canonical block: input block p, transposed or not
+  std::vector<int32_t> lcol((size_t)lnnzb);
+  std::vector<std::pair<int64_t, bool>> src((size_t)lnnzb);
+  std::vector<int64_t> pos(rp.begin(), rp.end() - 1);
+  for (int64_t I = ib0; I < ib1; ++I)
+    for (int64_t p = rpg[I] - index_base; p < rpg[I + 1] - index_base; ++p) {
+      const size_t q = (size_t)pos[(size_t)(I - ib0)]++;
+      lcol[q] = (int32_t)(block_col_idx[p] - index_base);
+      src[q] = {p, false};
+    }
+  if (lower)
+    for (int64_t I = 0; I < nb; ++I)
+      for (int64_t p = rpg[I] - index_base; p < rpg[I + 1] - index_base; ++p) {
+        const int64_t J = (int64_t)block_col_idx[p] - index_base;
+        if (J < I && local(J)) {
+          const size_t q = (size_t)pos[(size_t)(J - ib0)]++;
+          lcol[q] = (int32_t)I;
+          src[q] = {p, true};
+        }
+      }
+  std::vector<size_t> perm;
+  for (int64_t i = 0; i < nbl; ++i) {
+    const size_t a = (size_t)rp[(size_t)i], z = (size_t)rp[(size_t)i + 1];
+    if (std::is_sorted(lcol.begin() + a, lcol.begin() + z)) continue;
+    perm.resize(z - a);
+    for (size_t q = a; q < z; ++q) perm[q - a] = q;
+    std::stable_sort(perm.begin(), perm.end(), [&](size_t x, size_t y) { return lcol[x] < lcol[y]; });
+    std::vector<int32_t> c2(z - a);
+    std::vector<std::pair<int64_t, bool>> s2(z - a);
+    for (size_t q = 0; q < z - a; ++q) { c2[q] = lcol[perm[q]]; s2[q] = src[perm[q]]; }
+    std::copy(c2.begin(), c2.end(), lcol.begin() + a);
+    std::copy(s2.begin(), s2.end(), src.begin() + a);
+  }
+  // values column-major per block: lval[q * b * b + k * b + m] = A_q[m][k] (a mirrored block is the transpose of its source)
+  std::vector<double> lval((size_t)(lnnzb * bb));
+  for (int64_t q = 0; q < lnnzb; ++q) {
+    double* d = lval.data() + q * bb;
+    const int64_t p = src[(size_t)q].first;
+    const bool tr = src[(size_t)q].second;
+    for (int k = 0; k < b; ++k)
+      for (int m = 0; m < b; ++m) d[(int64_t)k * b + m] = tr ? entry(p, k, m) : entry(p, m, k);
+  }
+  // the diagonal of the whole matrix, from the diagonal blocks of the global arrays (duplicates summed in input order)
+  std::vector<double> diag((size_t)n, 0.0);
+  for (int64_t I = 0; I < nb; ++I)
+    for (int64_t p = rpg[I] - index_base; p < rpg[I + 1] - index_base; ++p)
+      if ((int64_t)block_col_idx[p] - index_base == I)
+        for (int m = 0; m < b; ++m) diag[(size_t)(I * b + m)] += entry(p, m, m);
+  std::vector<CsrItem> items;
+  std::vector<CsrLong> longs;
+  int nslots = 0;
+  bsr_build_items(rp, b, items, longs, &nslots);
+  // ---- device copies (the engine's allocator; released when the operator is set again and at dav_destroy)
+  HIPCHK(hipStreamSynchronize(e->stream));
+  sym_resident_release(o);
+  csr_release(e, o);
+  o.kind = DAV_KIND_NONE;
+  auto upload = [&](auto** dst, const auto* s, size_t count) -> int {
+    const size_t bytes = sizeof(**dst) * std::max<size_t>(count, 1);
+    if (pool_malloc(dst, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      *dst = nullptr;
+      return 1;
+    }
+    if (s && count > 0 && hipMemcpy(*dst, s, sizeof(**dst) * count, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return 1; }
+    return 0;
+  };
+  if (upload(&o.bsr_rp, rp.data(), rp.size()) || upload(&o.bsr_col, lcol.data(), lcol.size()) || upload(&o.bsr_val, lval.data(), lval.size()) ||
+      upload(&o.bsr_items, items.data(), items.size()) || upload(&o.bsr_longs, longs.data(), longs.size()) ||
+      upload(&o.bsr_part, (const double*)nullptr, (size_t)nslots * 1024))
+    return refuse("device memory for " + std::to_string(lnnzb) + " blocks of this rank (" + std::to_string((lnnzb * (8 * bb + 4)) >> 20) +
+                  " MiB) could not be allocated");
+  o.bsr_nitems = (int)items.size();
+  o.bsr_nlong = (int)longs.size();
+  o.bsr_b = b;
+  o.bsr_nnzb = lnnzb;
+  o.bsr_nbl = nbl;
+  o.bsr_grow0 = ib0 * b - r0;
+  o.storage = 0;
+  if (nloc > 0) HIPCHK(hipMemcpy(o.diag, diag.data() + r0, sizeof(double) * nloc, hipMemcpyHostToDevice));
+  e->diag_host[which].swap(diag);
+  if (which == DAV_OP_A) e->basis_order.clear();
+  o.kind = DAV_KIND_BSR;
   return 0;
 }
 

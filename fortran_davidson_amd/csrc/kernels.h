@@ -190,6 +190,20 @@ void launch_spmm_csr(hipStream_t st, const CsrItem* items, int nitems, const int
                      const double* xt, int64_t xt_gstride, int groups, int kk, double* part, double* dst, int64_t ldd);
 void launch_spmm_csr_finish(hipStream_t st, const CsrLong* longs, int nlong, const double* part, int kk, double* dst, int64_t ldd);
 
+// ---- K1d: BSR block product on the matrix cores (k_bsrmm.hip) ------------------------------------------------------------------------
+// Y[rows of this rank, 0:kk] = A_bsr * X, uniform block size 1 <= b <= 16, blocks column-major on the device.  Work list built on the
+// host (engine_operators.hip: bsr_build_items) in the CSR item types over LOCAL block rows: a run of whole block rows of at most BSR_ROWS
+// matrix rows and BSR_CHUNK blocks together (slot < 0), or one chunk of BSR_CHUNK blocks of a longer block row (slot >= 0: the partial
+// block row goes to part[slot][16][64]; launch_spmm_bsr_finish adds a block row's chunks in chunk order).  The rows written are the
+// local rows [0, nloc) of the block rows; the first row of local block row 0 is local row grow0 (<= 0).
+constexpr int BSR_ROWS = 16;
+constexpr int64_t BSR_CHUNK = 128;    // blocks; fixed for every matrix and rank count: the chunk boundaries of a long block row
+void launch_spmm_bsr(hipStream_t st, const CsrItem* items, int nitems, int bs, const int64_t* rp, const int32_t* col, const double* val,
+                     const double* xt, int64_t xt_gstride, int groups, int kk, double* part, double* dst, int64_t ldd, int64_t grow0,
+                     int64_t nloc);
+void launch_spmm_bsr_finish(hipStream_t st, const CsrLong* longs, int nlong, const double* part, int bs, int kk, double* dst, int64_t ldd,
+                            int64_t grow0, int64_t nloc);
+
 // ---- device-side Rayleigh-Ritz (k_smalleig.hip): all eigenpairs of H y = theta y / H y = theta S y, order m <= 128 ------
 size_t small_eig_work_doubles(int m);
 bool launch_small_eig(hipStream_t st, const double* H, int64_t ldh, const double* S, int64_t lds, int m, bool gev, double* theta,

@@ -94,6 +94,69 @@ def check_csr(indptr, indices, data, n, base=0, lower=False):
     return rp, ci, vv
 
 
+BSR_ROW_MAJOR, BSR_COL_MAJOR = 0, 1
+
+
+def bsr_arrays(indptr, indices=None, data=None, n=None, layout=BSR_ROW_MAJOR):
+    """(b, indptr int64, indices int32, data float64 of shape (nnzb, b, b)) of a BSR matrix given as three arrays - data (nnzb, b, b),
+    each block in `layout` order (row-major: data[p, m, k] = A_p[m, k]) - or as one object with .indptr, .indices, .data and .blocksize
+    (a scipy bsr_matrix, duck-typed; scipy is never imported here).  Checks only what keeps the C call inside the arrays."""
+    if hasattr(indptr, "blocksize"):
+        m = indptr
+        indptr, indices, data = m.indptr, m.indices, m.data
+        if tuple(m.blocksize)[0] != tuple(m.blocksize)[-1]:
+            raise DavidsonHipError(f"BSR input: blocks must be square, blocksize = {tuple(m.blocksize)}")
+    if indices is None or data is None:
+        raise DavidsonHipError("BSR input: indptr, indices and data are all needed (or one object with .blocksize)")
+    vv = np.ascontiguousarray(data, dtype=np.float64)
+    if vv.ndim != 3 or vv.shape[1] != vv.shape[2]:
+        raise DavidsonHipError(f"BSR input: data must have shape (nnzb, b, b), it has {vv.shape}")
+    b = int(vv.shape[1])
+    rp = np.ascontiguousarray(indptr, dtype=np.int64)
+    ci = np.ascontiguousarray(indices)
+    if ci.size and (ci.min() < -2**31 or ci.max() >= 2**31):
+        raise DavidsonHipError("BSR input: block column indices do not fit int32")
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    if b < 1 or b > 16:
+        raise DavidsonHipError(f"BSR input: block size {b} must lie in 1..16")
+    if n is not None and n % b:
+        raise DavidsonHipError(f"BSR input: n = {n} is not a multiple of the block size {b}")
+    if rp.ndim != 1 or (n is not None and rp.size != n // b + 1) or rp.size < 2:
+        raise DavidsonHipError(f"BSR input: indptr must hold n / b + 1 = {'?' if n is None else n // b + 1} offsets, it holds {rp.size}")
+    nnzb = int(rp[-1] - rp[0])
+    if nnzb < 0 or ci.size < nnzb or vv.shape[0] < nnzb:
+        raise DavidsonHipError(f"BSR input: indptr says {nnzb} blocks, indices / data hold {ci.size} / {vv.shape[0]}")
+    if layout not in (BSR_ROW_MAJOR, BSR_COL_MAJOR):
+        raise DavidsonHipError("BSR input: layout must be BSR_ROW_MAJOR (0) or BSR_COL_MAJOR (1)")
+    return b, rp, ci, vv
+
+
+def check_bsr(indptr, indices, data, n, base=0, lower=False, layout=BSR_ROW_MAJOR):
+    """Everything dav_set_operator_bsr validates, checked in Python (ValueError) - for the Fortran doors, which stop the process on an
+    engine error.  Returns (b, indptr, indices, data) as bsr_arrays does."""
+    try:
+        b, rp, ci, vv = bsr_arrays(indptr, indices, data, n, layout)
+    except DavidsonHipError as exc:
+        raise ValueError(str(exc)) from None
+    nb = n // b
+    if base not in (0, 1):
+        raise ValueError("BSR input: index base must be 0 or 1")
+    if rp[0] != base:
+        raise ValueError(f"BSR input: indptr[0] = {rp[0]} must equal the index base {base}")
+    if np.any(np.diff(rp) < 0):
+        raise ValueError(f"BSR input: indptr decreases at block row {int(np.argmax(np.diff(rp) < 0)) + base}")
+    nnzb = int(rp[-1] - base)
+    cols = ci[:nnzb].astype(np.int64) - base
+    if nnzb and (cols.min() < 0 or cols.max() >= nb):
+        raise ValueError(f"BSR input: block column index out of range [{base}, {nb + base})")
+    if lower and nnzb:
+        rows = np.repeat(np.arange(nb, dtype=np.int64), np.diff(rp))
+        if np.any(cols > rows):
+            p = int(np.argmax(cols > rows))
+            raise ValueError(f"BSR input: block ({rows[p] + base}, {cols[p] + base}) lies above the diagonal with lower=True")
+    return b, rp, ci, vv
+
+
 def _f(a):
     return np.asfortranarray(a, dtype=np.float64)
 
@@ -254,6 +317,18 @@ class CEngine:
         vv_p = _dp(vv) if vv.size else (C.c_double * 1)()
         self._chk(self.lib.dav_set_operator_csr(self.h, C.c_int(which), rp.ctypes.data_as(C.POINTER(C.c_int64)), ci_p, vv_p, C.c_int(base),
                                                 C.c_int(CSR_LOWER if lower else CSR_FULL)))
+
+    def set_operator_bsr(self, which, indptr, indices=None, data=None, base=0, lower=False, layout=BSR_ROW_MAJOR):
+        """dav_set_operator_bsr: a symmetric matrix in BSR form with square blocks (the global arrays; indptr / indices count block
+        rows / columns from `base`), every nonzero block (lower=False) or only the blocks with block column <= block row (lower=True).
+        Three numpy arrays - data of shape (nnzb, b, b), row-major blocks unless layout=BSR_COL_MAJOR - or one object with .indptr,
+        .indices, .data and .blocksize (a scipy bsr_matrix).  The engine validates the input (DavidsonHipError) and leaves the operator
+        unset when it refuses it."""
+        b, rp, ci, vv = bsr_arrays(indptr, indices, data, self.n, layout)
+        ci_p = ci.ctypes.data_as(C.POINTER(C.c_int32)) if ci.size else (C.c_int32 * 1)()
+        vv_p = _dp(vv) if vv.size else (C.c_double * 1)()
+        self._chk(self.lib.dav_set_operator_bsr(self.h, C.c_int(which), C.c_int(b), rp.ctypes.data_as(C.POINTER(C.c_int64)), ci_p, vv_p,
+                                                C.c_int(base), C.c_int(CSR_LOWER if lower else CSR_FULL), C.c_int(layout)))
 
     def get_diagonal(self, which):
         d = np.zeros(self.n)

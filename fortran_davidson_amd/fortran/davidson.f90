@@ -1087,7 +1087,7 @@ module davidson_csr
   use davidson_sparse
   implicit none
   private
-  public :: generalized_eigensolver_sparse
+  public :: generalized_eigensolver_sparse, generalized_eigensolver_bsr
 
 contains
 
@@ -1119,6 +1119,34 @@ contains
     call engine_destroy(eng)
   end subroutine generalized_eigensolver_sparse
 
+  !> Block-sparse front-end: the same argument list with bsr_matrix operators (module davidson_sparse).  The matrices go to HBM as
+  !> blocks, are solved there with the engine's matrix-core BSR kernel and are released before returning.
+  subroutine generalized_eigensolver_bsr(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix)
+    integer, intent(in) :: lowest
+    type(bsr_matrix), intent(in) :: matrix
+    type(bsr_matrix), intent(in), optional :: second_matrix
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    real(dp), dimension(:, :), intent(out) :: eigenvectors
+    integer, intent(in) :: max_iterations
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), intent(in) :: tolerance
+    character(len=*), intent(in) :: method
+    integer, intent(out) :: iters
+
+    type(davidson_engine) :: eng
+    integer :: max_dim
+
+    max_dim = 10 * lowest
+    if (present(max_dim_sub)) max_dim = max_dim_sub
+    call engine_create(eng, matrix%n, lowest, max_dim, present(second_matrix), env_device())
+    call engine_set_sparse(eng, 1, matrix)
+    if (present(second_matrix)) call engine_set_sparse(eng, 2, second_matrix)
+    call generalized_eigensolver_device(eng, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+         tolerance, iters, max_dim)
+    call engine_destroy(eng)
+  end subroutine generalized_eigensolver_bsr
+
 end module davidson_csr
 
 
@@ -1127,19 +1155,20 @@ module davidson
   use davidson_dense, only: generalized_eigensolver_dense
   use davidson_free, only: generalized_eigensolver_free
   use davidson_device, only: generalized_eigensolver_device, davidson_free_buffers
-  use davidson_sparse, only: csr_matrix
-  use davidson_csr, only: generalized_eigensolver_sparse
+  use davidson_sparse, only: csr_matrix, bsr_matrix
+  use davidson_csr, only: generalized_eigensolver_sparse, generalized_eigensolver_bsr
   implicit none
   private
-  public :: generalized_eigensolver, davidson_free_buffers, csr_matrix
+  public :: generalized_eigensolver, davidson_free_buffers, csr_matrix, bsr_matrix
 
   !> Generic of the reference (src/davidson.f90:601-625), resolved by the first argument: a matrix,
-  !> a block-apply procedure, (new) a device-resident `davidson_engine`, or (new) a sparse `csr_matrix`.
+  !> a block-apply procedure, (new) a device-resident `davidson_engine`, or (new) a sparse `csr_matrix` / `bsr_matrix`.
   interface generalized_eigensolver
      procedure generalized_eigensolver_dense
      procedure generalized_eigensolver_free
      procedure generalized_eigensolver_device
      procedure generalized_eigensolver_sparse
+     procedure generalized_eigensolver_bsr
   end interface generalized_eigensolver
 
 end module davidson

@@ -7,7 +7,7 @@ module davidson_c_api
   use davidson, only: generalized_eigensolver
   use davidson_device
   use davidson_free, only: free_matmul
-  use davidson_sparse, only: csr_matrix, engine_set_sparse
+  use davidson_sparse, only: csr_matrix, bsr_matrix, engine_set_sparse
   use lapack_wrapper
   use array_utils
   implicit none
@@ -103,6 +103,55 @@ contains
     end if
     iters = it
   end subroutine fd_sparse_solve
+
+  !> A bsr_matrix from C arrays (row_ptr: n / b + 1 int64 offsets, col_idx: int32 block columns, vals: b * b values per block in
+  !> Fortran order values(m, k, p)) numbered from `base` (0 or 1): renumbered from 1
+  function bsr_from_c(n, b, row_ptr, col_idx, vals, base, lower) result(a)
+    integer(c_int), intent(in) :: n, b, base, lower
+    integer(c_int64_t), intent(in) :: row_ptr(n / b + 1)
+    integer(c_int32_t), intent(in) :: col_idx(*)
+    real(c_double), intent(in) :: vals(b, b, *)
+    type(bsr_matrix) :: a
+    integer(c_int64_t) :: nnzb
+    nnzb = row_ptr(n / b + 1) - base
+    a%n = n
+    a%block_size = b
+    a%row_ptr = row_ptr + (1 - base)
+    a%col_idx = col_idx(1:nnzb) + int(1 - base, c_int32_t)
+    a%values = vals(:, :, 1:nnzb)
+    a%lower = lower /= 0
+  end function bsr_from_c
+
+  !> generalized_eigensolver(a_bsr, ...) - block-sparse specific.  max_dim < 0: argument absent; has_b: B given (same block size, base
+  !> and triangle).
+  subroutine fd_bsr_solve(n, b, rp, col, vals, has_b, rpb, colb, valsb, base, lower, lowest, method, max_it, tol, max_dim, evals, &
+       evecs, iters) bind(C, name="fd_bsr_solve")
+    integer(c_int), value :: n, b, has_b, base, lower, lowest, method, max_it, max_dim
+    integer(c_int64_t), intent(in) :: rp(*), rpb(*)
+    integer(c_int32_t), intent(in) :: col(*), colb(*)
+    real(c_double), intent(in) :: vals(*), valsb(*)
+    real(c_double), value :: tol
+    real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
+    integer(c_int), intent(out) :: iters
+    type(bsr_matrix) :: a, bm
+    integer :: it
+    a = bsr_from_c(n, b, rp, col, vals, base, lower)
+    if (has_b /= 0) then
+       bm = bsr_from_c(n, b, rpb, colb, valsb, base, lower)
+       if (max_dim >= 0) then
+          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, max_dim, bm)
+       else
+          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, second_matrix=bm)
+       end if
+    else
+       if (max_dim >= 0) then
+          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, max_dim)
+       else
+          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it)
+       end if
+    end if
+    iters = it
+  end subroutine fd_bsr_solve
 
   function apply_cb_a(input_vect) result(output_vect)
     real(dp), dimension(:, :), intent(in) :: input_vect
@@ -242,6 +291,18 @@ contains
     call c_f_pointer(p, eng)
     call engine_set_sparse(eng, int(which), csr_from_c(n, rp, col, vals, base, lower))
   end subroutine fd_engine_set_sparse
+
+  !> engine_set_sparse(eng, which, a) with a bsr_matrix from C arrays numbered from `base` (values in Fortran order, as bsr_from_c)
+  subroutine fd_engine_set_block_sparse(p, which, n, b, rp, col, vals, base, lower) bind(C, name="fd_engine_set_block_sparse")
+    type(c_ptr), value :: p
+    integer(c_int), value :: which, n, b, base, lower
+    integer(c_int64_t), intent(in) :: rp(*)
+    integer(c_int32_t), intent(in) :: col(*)
+    real(c_double), intent(in) :: vals(*)
+    type(davidson_engine), pointer :: eng
+    call c_f_pointer(p, eng)
+    call engine_set_sparse(eng, int(which), bsr_from_c(n, b, rp, col, vals, base, lower))
+  end subroutine fd_engine_set_block_sparse
 
   !> kind 0: dense generated in HBM, 1: hashed matrix-free operator, 2: harness operator, 3: identity
   subroutine fd_engine_set_operator(p, which, kind, seed, sparsity, use_diag_val, diag_val) &

@@ -13,6 +13,8 @@ module davidson_hip_c
   integer(c_int), parameter :: DAV_NO_SUCH_ENTRY = 2
   !> dav_set_operator_csr: every nonzero given / only j <= i given (the engine mirrors the strict lower part)
   integer(c_int), parameter :: DAV_CSR_FULL = 0, DAV_CSR_LOWER = 1
+  !> dav_set_operator_bsr: order of the b * b values of one block (C / scipy row-major, Fortran values(b, b, nnzb) column-major)
+  integer(c_int), parameter :: DAV_BSR_ROW_MAJOR = 0, DAV_BSR_COL_MAJOR = 1
 
   type, bind(C) :: dav_stats
      integer(c_int64_t) :: n, nloc
@@ -179,6 +181,19 @@ module davidson_hip_c
        integer(c_int32_t), intent(in) :: col_idx(*)
        real(c_double), intent(in) :: vals(*)
        integer(c_int), value :: index_base, triangle
+       integer(c_int) :: ierr
+     end function
+     !> a symmetric matrix in BSR form, uniform block size 1..16, global host arrays (additive in ABI 109); index_base 1 = Fortran
+     !> numbering of block rows and columns
+     function dav_set_operator_bsr(h, which, block_size, block_row_ptr, block_col_idx, vals, index_base, triangle, block_layout) &
+          bind(C, name="dav_set_operator_bsr") result(ierr)
+       import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+       type(c_ptr), value :: h
+       integer(c_int), value :: which, block_size
+       integer(c_int64_t), intent(in) :: block_row_ptr(*)
+       integer(c_int32_t), intent(in) :: block_col_idx(*)
+       real(c_double), intent(in) :: vals(*)
+       integer(c_int), value :: index_base, triangle, block_layout
        integer(c_int) :: ierr
      end function
      function dav_set_operator_host(h, which, diag) bind(C, name="dav_set_operator_host") result(ierr)

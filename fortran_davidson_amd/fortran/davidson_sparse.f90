@@ -1,6 +1,7 @@
-!> Sparse operators: a symmetric real matrix in CSR (compressed sparse row) form, 1-based as Fortran numbers rows and columns, and
-!> engine_set_sparse, which hands it to a device-resident problem (dav_set_operator_csr, include/davidson_hip.h).  The solve of a
-!> csr_matrix is the specific generalized_eigensolver_sparse of the generic generalized_eigensolver (module davidson).
+!> Sparse operators: a symmetric real matrix in CSR (compressed sparse row) or BSR (block sparse row) form, 1-based as Fortran numbers
+!> rows and columns, and engine_set_sparse, which hands either to a device-resident problem (dav_set_operator_csr / dav_set_operator_bsr,
+!> include/davidson_hip.h).  The solves of a csr_matrix / bsr_matrix are the specifics generalized_eigensolver_sparse /
+!> generalized_eigensolver_bsr of the generic generalized_eigensolver (module davidson).
 module davidson_sparse
   use, intrinsic :: iso_c_binding
   use numeric_kinds, only: dp
@@ -8,7 +9,7 @@ module davidson_sparse
   use davidson_engine_setup, only: davidson_engine
   implicit none
   private
-  public :: csr_matrix, engine_set_sparse
+  public :: csr_matrix, bsr_matrix, engine_set_sparse
 
   !> A symmetric real matrix of order n in CSR form, 1-based: the entries of row i are col_idx / values(row_ptr(i) : row_ptr(i+1) - 1).
   !> lower = .true.: only the entries with column <= row are given (the engine mirrors the strict lower part); .false.: every nonzero
@@ -25,6 +26,30 @@ module davidson_sparse
   interface csr_matrix
      module procedure new_csr_matrix
   end interface csr_matrix
+
+  !> A symmetric real matrix of order n in BSR form with square blocks of a uniform size block_size = b (1..16, n a multiple of b),
+  !> 1-based: the blocks of block row I are col_idx / values(:, :, row_ptr(I) : row_ptr(I+1) - 1), values(m, k, p) the entry (m, k) of
+  !> block p.  lower = .true.: only the blocks with block column <= block row are given (a diagonal block in full; the engine mirrors
+  !> the strict lower blocks); .false.: every nonzero block is given, and the symmetry is the caller's promise.
+  type :: bsr_matrix
+     integer :: n = 0
+     integer :: block_size = 0
+     integer(c_int64_t), allocatable :: row_ptr(:)
+     integer(c_int32_t), allocatable :: col_idx(:)
+     real(dp), allocatable :: values(:, :, :)
+     logical :: lower = .false.
+  end type bsr_matrix
+
+  !> bsr_matrix(n, b, row_ptr, col_idx, values [, lower]) from default-kind integer arrays, 1-based
+  interface bsr_matrix
+     module procedure new_bsr_matrix
+  end interface bsr_matrix
+
+  !> engine_set_sparse(eng, which, a) with a csr_matrix or a bsr_matrix
+  interface engine_set_sparse
+     module procedure engine_set_sparse_csr
+     module procedure engine_set_sparse_bsr
+  end interface engine_set_sparse
 
 contains
 
@@ -52,7 +77,7 @@ contains
 
   !> Operator A (which = 1) or B (which = 2) of the engine from a csr_matrix: the engine keeps the rows of its slab in HBM and applies
   !> them with its own CSR kernel.  The matrix is not referenced after the call.
-  subroutine engine_set_sparse(eng, which, a)
+  subroutine engine_set_sparse_csr(eng, which, a)
     type(davidson_engine), intent(inout) :: eng
     integer, intent(in) :: which
     type(csr_matrix), intent(in) :: a
@@ -71,6 +96,65 @@ contains
     end if
     ! a stored matrix: the dense driver's sticky convergence flags, as for engine_set_dense
     if (which == 1) eng%free_semantics = .false.
-  end subroutine engine_set_sparse
+  end subroutine engine_set_sparse_csr
+
+  function new_bsr_matrix(n, b, row_ptr, col_idx, values, lower) result(a)
+    integer, intent(in) :: n, b
+    integer, intent(in) :: row_ptr(:), col_idx(:)
+    real(dp), intent(in) :: values(:, :, :)
+    logical, intent(in), optional :: lower
+    type(bsr_matrix) :: a
+    integer :: nb
+    if (b < 1 .or. b > 16) then
+       print *, "bsr_matrix: block size ", b, " must lie in 1..16"
+       error stop
+    end if
+    if (mod(n, b) /= 0) then
+       print *, "bsr_matrix: n = ", n, " is not a multiple of the block size ", b
+       error stop
+    end if
+    nb = n / b
+    if (size(row_ptr) /= nb + 1) then
+       print *, "bsr_matrix: row_ptr must hold n / b + 1 = ", nb + 1, " offsets, not ", size(row_ptr)
+       error stop
+    end if
+    if (size(values, 1) /= b .or. size(values, 2) /= b) then
+       print *, "bsr_matrix: values must have the shape (b, b, nnzb)"
+       error stop
+    end if
+    if (size(col_idx) < row_ptr(nb + 1) - 1 .or. size(values, 3) < row_ptr(nb + 1) - 1) then
+       print *, "bsr_matrix: row_ptr(n / b + 1) - 1 = ", row_ptr(nb + 1) - 1, " blocks, but col_idx / values hold ", size(col_idx), &
+            " / ", size(values, 3)
+       error stop
+    end if
+    a%n = n
+    a%block_size = b
+    a%row_ptr = int(row_ptr, c_int64_t)
+    a%col_idx = int(col_idx, c_int32_t)
+    a%values = values
+    if (present(lower)) a%lower = lower
+  end function new_bsr_matrix
+
+  !> Operator A (which = 1) or B (which = 2) of the engine from a bsr_matrix: the engine keeps the block rows of its slab in HBM and
+  !> applies them with its own matrix-core BSR kernel.  The matrix is not referenced after the call.
+  subroutine engine_set_sparse_bsr(eng, which, a)
+    type(davidson_engine), intent(inout) :: eng
+    integer, intent(in) :: which
+    type(bsr_matrix), intent(in) :: a
+    real(dp) :: nothing(1)
+    if (a%n /= eng%n .or. .not. allocated(a%row_ptr) .or. .not. allocated(a%values)) then
+       print *, "engine_set_sparse: the matrix must be of order ", eng%n
+       error stop
+    end if
+    if (size(a%values) > 0) then
+       call check_dav(dav_set_operator_bsr(eng%h, int(which - 1, c_int), int(a%block_size, c_int), a%row_ptr, a%col_idx, a%values, &
+            1_c_int, merge(DAV_CSR_LOWER, DAV_CSR_FULL, a%lower), DAV_BSR_COL_MAJOR), "dav_set_operator_bsr")
+    else
+       nothing = 0.0_dp
+       call check_dav(dav_set_operator_bsr(eng%h, int(which - 1, c_int), int(a%block_size, c_int), a%row_ptr, [0_c_int32_t], nothing, &
+            1_c_int, merge(DAV_CSR_LOWER, DAV_CSR_FULL, a%lower), DAV_BSR_COL_MAJOR), "dav_set_operator_bsr")
+    end if
+    if (which == 1) eng%free_semantics = .false.
+  end subroutine engine_set_sparse_bsr
 
 end module davidson_sparse

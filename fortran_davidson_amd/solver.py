@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import fortran_lib
-from .engine_c import CEngine, check_csr
+from .engine_c import CEngine, check_bsr, check_csr
 
 _METHOD = {"DPR": 0, "GJD": 1}
 _CB = C.CFUNCTYPE(None, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
@@ -91,6 +91,47 @@ def generalized_eigensolver_sparse(indptr, indices, data, lowest, method, max_it
     return evals, evecs, iters.value
 
 
+def _bsr_input(a, n, lower=False):
+    """(b, indptr, indices, values) of a BSR operator given as a tuple (indptr, indices, data (nnzb, b, b) row-major blocks) or an object
+    with .blocksize (a scipy bsr_matrix), 0-based, validated here (ValueError) - the Fortran door stops the process on an engine error.
+    The values come back in Fortran order (values(m, k, p) = A_p[m, k]: each block transposed in memory) for the Fortran doors."""
+    if hasattr(a, "blocksize"):
+        a = (a.indptr, a.indices, a.data)
+    indptr, indices, data = a
+    if n is None:
+        d = np.asarray(data)
+        n = (len(indptr) - 1) * (d.shape[1] if d.ndim == 3 else 1)
+    b, rp, ci, vv = check_bsr(indptr, indices, data, n, 0, lower)
+    vf = np.ascontiguousarray(vv.transpose(0, 2, 1))
+    return b, rp, ci, vf if vf.size else np.zeros(1)
+
+
+def generalized_eigensolver_bsr(indptr, indices, data, lowest, method, max_iterations, tolerance, max_dim_sub=None, second=None,
+                                lower=False, n=None):
+    """`call generalized_eigensolver(a_bsr, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters [, max_dim_sub]
+    [, b_bsr])` (the bsr_matrix specific of module davidson) with A in BSR form, 0-based: three arrays - data (nnzb, b, b), row-major
+    blocks - or `indptr` an object with .indptr / .indices / .data / .blocksize (a scipy bsr_matrix) and indices = data = None.
+    `second`: B the same way, with the same block size.  lower=True: only the blocks with block column <= block row are given, for A and
+    B.  n: the order (default: block rows x b).  Returns (eigenvalues, eigenvectors, iters)."""
+    a = indptr if indices is None and data is None else (indptr, indices, data)
+    b, rp, ci, vv = _bsr_input(a, n, lower)
+    n = (rp.size - 1) * b
+    if second is not None:
+        bb, rpb, cib, vvb = _bsr_input(second, n, lower)
+        if bb != b:
+            raise ValueError(f"BSR input: B has block size {bb}, A has {b}")
+    else:
+        rpb, cib, vvb = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int32), np.zeros(1)
+    evals = np.zeros(lowest)
+    evecs = np.zeros((n, lowest), order="F")
+    iters = C.c_int(-1)
+    fortran_lib().fd_bsr_solve(C.c_int(n), C.c_int(b), _i64(rp), _i32(ci), _dp(vv), C.c_int(0 if second is None else 1), _i64(rpb),
+                               _i32(cib), _dp(vvb), C.c_int(0), C.c_int(1 if lower else 0), C.c_int(lowest), C.c_int(_METHOD.get(method, 2)),
+                               C.c_int(max_iterations), C.c_double(tolerance), C.c_int(-1 if max_dim_sub is None else max_dim_sub),
+                               _dp(evals), _dp(evecs), C.byref(iters))
+    return evals, evecs, iters.value
+
+
 def generalized_eigensolver_free(fun_matrix_gemv, n, lowest, method, max_iterations, tolerance, max_dim_sub,
                                  fun_second_matrix_gemv):
     """Matrix-free specific with numpy callbacks X(n,k) -> Y(n,k) (reference: src/davidson.f90:277-337)."""
@@ -158,6 +199,15 @@ class DavidsonEngine:
         _, rp, ci, vv = _sparse_input(a, self.n, lower)
         self.lib.fd_engine_set_sparse(self.p, C.c_int(which), C.c_int(self.n), _i64(rp), _i32(ci), _dp(vv), C.c_int(0),
                                       C.c_int(1 if lower else 0))
+
+    def set_block_sparse(self, which, indptr, indices=None, data=None, lower=False):
+        """Operator A (which=1) or B (which=2) as a symmetric matrix in BSR form, 0-based (Fortran: engine_set_sparse with a bsr_matrix):
+        three arrays - data (nnzb, b, b), row-major blocks - or `indptr` an object with .blocksize (a scipy bsr_matrix).  lower=True:
+        only the blocks with block column <= block row are given."""
+        a = indptr if indices is None and data is None else (indptr, indices, data)
+        b, rp, ci, vv = _bsr_input(a, self.n, lower)
+        self.lib.fd_engine_set_block_sparse(self.p, C.c_int(which), C.c_int(self.n), C.c_int(b), _i64(rp), _i32(ci), _dp(vv), C.c_int(0),
+                                            C.c_int(1 if lower else 0))
 
     def set_correction_policy(self, policy):
         """"all" = the reference's policy (default); "unconverged" = opt-in: correct only the wanted pairs

@@ -218,6 +218,24 @@ int dav_set_operator_device(dav_handle_t h, int which, dav_device_apply_fn fn, v
 enum { DAV_CSR_FULL = 0, DAV_CSR_LOWER = 1 };
 int dav_set_operator_csr(dav_handle_t h, int which, const int64_t* row_ptr /* n+1 */, const int32_t* col_idx, const double* vals,
                          int index_base /* 0 or 1 */, int triangle);
+/* A symmetric real matrix in BSR (block sparse row) form with a uniform block size b, 1 <= b <= 16, n a multiple of b.  Purely additive
+ * within ABI 109: no existing entry, constant or the layout of dav_stats changes.  Host pointers to the GLOBAL matrix, as for
+ * dav_set_operator_csr: block_row_ptr[0..n/b] (int64), block_col_idx (block columns) and vals (b * b values per block) of the
+ * block_row_ptr[n/b] - index_base blocks; index_base applies to both index arrays.  block_layout orders the b * b values of one block:
+ * DAV_BSR_ROW_MAJOR (C / scipy: vals[blk][m][k]) or DAV_BSR_COL_MAJOR (a Fortran values(b, b, nnzb)).  DAV_CSR_FULL: every nonzero
+ * block is given, its symmetry is the caller's promise; DAV_CSR_LOWER: only blocks with block column J <= block row I are given - a
+ * diagonal block in full (its symmetry is the caller's promise) - and each strict lower block (I, J) also stands for its transpose at
+ * (J, I).  Validation before anything is allocated: b in range, n % b == 0, the base, block_row_ptr never decreasing, block columns in
+ * range, no block above the diagonal with DAV_CSR_LOWER, the layout, null pointers; a refused call leaves the operator UNSET and the
+ * engine usable, as with CSR.  Within a block row the blocks are sorted by block column (stable, after the mirrored blocks have joined
+ * their rows); duplicate blocks stay separate terms.  The diagonal (diagonal blocks, duplicates summed) is taken on the host.  The block
+ * product runs on the matrix cores (v_mfma_f64_4x4x4_4b for b <= 8, v_mfma_f64_16x16x4 above), reads the matrix once per 64 columns
+ * and is bitwise reproducible for every rank count and repetition - a block row that straddles two slabs is computed whole by both
+ * ranks.  dav_set_inner_precision(32) does not apply; the caller's arrays are not referenced after the call returns.  Statistics:
+ * apply_bytes = 8 nnzb b^2 + 4 nnzb + 8 (block rows + 1) + 8 N k + 8 nloc k, apply_flops = 2 nnzb b^2 k (this rank's block rows). */
+enum { DAV_BSR_ROW_MAJOR = 0, DAV_BSR_COL_MAJOR = 1 };
+int dav_set_operator_bsr(dav_handle_t h, int which, int block_size, const int64_t* block_row_ptr /* n/b + 1 */, const int32_t* block_col_idx,
+                         const double* vals /* nnzb * b * b */, int index_base /* 0 or 1 */, int triangle, int block_layout);
 int dav_get_diagonal(dav_handle_t h, int which, double* diag_out /* n, global */);
 
 /* ---- the per-iteration hot path ---------------------------------------------------------------- */
