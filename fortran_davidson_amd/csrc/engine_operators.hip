@@ -767,6 +767,218 @@ extern "C" int dav_set_operator_csr(dav_handle_t e, int which, const int64_t* ro
   return 0;
 }
 
+// ---- the same matrix from device arrays, built on the GPU (dav_set_operator_csr_dev; kernels in k_csr_build.hip) ------------------------
+// Validation, canonical rows, diagonal and storage equal those of dav_set_operator_csr bit for bit; only the work list is built on the
+// host, over the canonical row offsets read back (8 (nloc + 1) bytes).
+extern "C" int dav_set_operator_csr_dev(dav_handle_t e, int which, const void* row_ptr, int row_ptr_bits, const void* col_idx, int col_bits,
+                                        const double* vals, int index_base, int triangle) {
+  if (!e) return fail("dav_set_operator_csr_dev: null engine");
+  if (which < 0 || which > 1) return fail("dav_set_operator_csr_dev: bad operator id");
+  CHK(bind(e));
+  OpDesc& o = e->op[which];
+  auto refuse = [&](const std::string& msg) {
+    csr_release(e, o);
+    o.kind = DAV_KIND_NONE;
+    e->diag_host[which].clear();
+    if (which == DAV_OP_A) e->basis_order.clear();
+    return fail("dav_set_operator_csr_dev: " + msg);
+  };
+  const int64_t n = e->n, r0 = e->row0, nloc = e->nloc;
+  hipStream_t st = e->stream;
+  if (n >= ((int64_t)1 << 31)) return refuse("n = " + std::to_string(n) + " must be below 2^31 (int32 column indices)");
+  if (index_base != 0 && index_base != 1) return refuse("index_base must be 0 or 1");
+  if (triangle != DAV_CSR_FULL && triangle != DAV_CSR_LOWER) return refuse("triangle must be DAV_CSR_FULL or DAV_CSR_LOWER");
+  if (row_ptr_bits != 32 && row_ptr_bits != 64) return refuse("row_ptr_bits must be 32 or 64");
+  if (col_bits != 32 && col_bits != 64) return refuse("col_bits must be 32 or 64");
+  if (!row_ptr) return refuse("null row_ptr");
+  const int rp64 = row_ptr_bits == 64, ci64 = col_bits == 64;
+  const size_t rpw = rp64 ? 8 : 4, ciw = ci64 ? 8 : 4;
+  // ---- the caller's pointers: device memory of this engine's device, large enough where the runtime can tell (before any launch)
+  auto device_array = [&](const void* p, const char* name, size_t bytes, std::string* why) {
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+      (void)hipGetLastError();
+      *why = std::string(name) + " is not device memory (the runtime does not know the pointer)";
+      return false;
+    }
+    if (at.type != hipMemoryTypeDevice) { *why = std::string(name) + " is not device memory (host, pinned or managed)"; return false; }
+    if (at.device != e->device) {
+      *why = std::string(name) + " lies on device " + std::to_string(at.device) + ", the engine on device " + std::to_string(e->device);
+      return false;
+    }
+    hipDeviceptr_t lo = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&lo, &size, (hipDeviceptr_t)p) == hipSuccess) {
+      if ((const char*)p + bytes > (const char*)lo + size)
+        { *why = std::string(name) + " holds fewer than the " + std::to_string(bytes) + " bytes the matrix needs"; return false; }
+    } else {
+      (void)hipGetLastError();
+    }
+    return true;
+  };
+  std::string why;
+  if (!device_array(row_ptr, "row_ptr", rpw * (size_t)(n + 1), &why)) return refuse(why);
+  if (col_idx && !device_array(col_idx, "col_idx", 0, &why)) return refuse(why);
+  if (vals && !device_array(vals, "vals", 0, &why)) return refuse(why);
+  // ---- scratch of the build (released on every way out, after the stream has finished with it)
+  std::vector<void*> scratch;
+  struct Release {
+    hipStream_t st; std::vector<void*>& v;
+    ~Release() { (void)hipStreamSynchronize(st); for (void* p : v) pool_free(p); }
+  } release{st, scratch};
+  bool oom = false;
+  auto take = [&](auto** p, size_t count) {
+    *p = nullptr;
+    if (oom) return;
+    if (pool_malloc(p, sizeof(**p) * std::max<size_t>(count, 1)) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; oom = true; return; }
+    scratch.push_back((void*)*p);
+  };
+  auto no_memory = [&](const std::string& what) { return refuse("device memory for " + what + " could not be allocated"); };
+  auto readback = [&](void* dst, const void* src, size_t bytes) -> int {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+  };
+  // ---- validation on the device: row_ptr first, then the entries (the first offending position, as the host loop names it)
+  unsigned long long* info = nullptr;
+  take(&info, 4);
+  if (oom) return no_memory("the validation");
+  HIPCHK(hipMemsetAsync(info, 0xff, sizeof(unsigned long long) * 4, st));
+  launch_csr_build_rows(st, row_ptr, rp64, n, info);
+  unsigned long long hinfo[4];
+  CHK(readback(hinfo, info, sizeof(hinfo)));
+  const int64_t rp0 = (int64_t)hinfo[1], rpn = (int64_t)hinfo[2];
+  if (rp0 != index_base) return refuse("row_ptr[0] = " + std::to_string(rp0) + " must equal the index base " + std::to_string(index_base));
+  if (hinfo[0] != ~0ull) return refuse("row_ptr decreases at row " + std::to_string((int64_t)hinfo[0] + index_base));
+  const int64_t nnz = rpn - index_base;
+  if (nnz > 0 && (!col_idx || !vals)) return refuse("null col_idx or vals");
+  if (hinfo[3] != ~0ull) return refuse("row " + std::to_string((int64_t)hinfo[3] + index_base) + " holds 2^32 entries or more");
+  if (nnz > 0 && (!device_array(col_idx, "col_idx", ciw * (size_t)nnz, &why) || !device_array(vals, "vals", 8 * (size_t)nnz, &why)))
+    return refuse(why);
+  const bool lower = triangle == DAV_CSR_LOWER;
+  int32_t* mcount = nullptr;        // mirrored entries per local row; later the slots taken by the scatter
+  uint32_t* dcount = nullptr;       // diagonal entries per row of the whole matrix
+  unsigned long long* dfirst = nullptr;
+  int64_t* locate = nullptr;
+  take(&mcount, (size_t)nloc); take(&dcount, (size_t)n); take(&dfirst, (size_t)n); take(&locate, 2);
+  if (oom) return no_memory("the validation of " + std::to_string(n) + " rows");
+  HIPCHK(hipMemsetAsync(mcount, 0, sizeof(int32_t) * std::max<int64_t>(nloc, 1), st));
+  HIPCHK(hipMemsetAsync(dcount, 0, sizeof(uint32_t) * std::max<int64_t>(n, 1), st));
+  HIPCHK(hipMemsetAsync(dfirst, 0xff, sizeof(unsigned long long) * std::max<int64_t>(n, 1), st));
+  launch_csr_build_check(st, row_ptr, rp64, col_idx, ci64, n, nnz, index_base, lower ? 1 : 0, r0, nloc, info + 3, mcount, dcount, dfirst);
+  CHK(readback(hinfo, info, sizeof(hinfo)));
+  if (hinfo[3] != ~0ull) {
+    const int64_t p = (int64_t)hinfo[3];
+    launch_csr_build_locate(st, row_ptr, rp64, col_idx, ci64, n, index_base, p, locate);
+    int64_t loc[2];
+    CHK(readback(loc, locate, sizeof(loc)));
+    const int64_t i = loc[0], c = loc[1], j = c - index_base;
+    if (j < 0 || j >= n)
+      return refuse("column index " + std::to_string(c) + " out of range at entry " + std::to_string(p + index_base) + " (row " +
+                    std::to_string(i + index_base) + ")");
+    return refuse("entry (" + std::to_string(i + index_base) + ", " + std::to_string(c) + ") lies above the diagonal of a DAV_CSR_LOWER matrix");
+  }
+  // ---- valid: the previous operator goes, the canonical rows of this rank are built in its place
+  HIPCHK(hipStreamSynchronize(st));
+  sym_resident_release(o);
+  csr_release(e, o);
+  o.kind = DAV_KIND_NONE;
+  e->diag_host[which].clear();
+  if (which == DAV_OP_A) e->basis_order.clear();
+  auto keep = [&](auto** p, size_t count) {
+    if (pool_malloc(p, sizeof(**p) * std::max<size_t>(count, 1)) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
+    return true;
+  };
+  int64_t* tile_sums = nullptr;
+  take(&tile_sums, (size_t)csr_build_scan_tiles(nloc));
+  if (oom || !keep(&o.csr_rp, (size_t)nloc + 1)) return no_memory("the row offsets of this rank");
+  launch_csr_build_offsets(st, row_ptr, rp64, r0, nloc, mcount, o.csr_rp, tile_sums);
+  std::vector<int64_t> rp((size_t)nloc + 1);
+  CHK(readback(rp.data(), o.csr_rp, sizeof(int64_t) * rp.size()));
+  const int64_t lnnz = rp[(size_t)nloc];
+  if (!keep(&o.csr_col, (size_t)lnnz) || !keep(&o.csr_val, (size_t)lnnz))
+    return no_memory(std::to_string(lnnz) + " entries of this rank (" + std::to_string((12 * lnnz + 8 * nloc) >> 20) + " MiB)");
+  uint32_t* tie = nullptr;
+  uint8_t* flag = nullptr;
+  if (lower) take(&tie, (size_t)lnnz);
+  take(&flag, (size_t)nloc);
+  if (oom) return no_memory("sorting " + std::to_string(lnnz) + " entries");
+  // own entries: those of the local rows; mirrored entries (lower): any row of the matrix may send some
+  int64_t p_lo = 0, p_hi = nnz;
+  if (!lower && nloc > 0) {
+    int64_t ends[2] = {0, 0};
+    for (int s = 0; s < 2; ++s) {
+      const char* src = (const char*)row_ptr + rpw * (size_t)(s == 0 ? r0 : r0 + nloc);
+      CHK(readback(&ends[s], src, rpw));
+      if (!rp64) ends[s] = (int64_t)(int32_t)ends[s];
+    }
+    p_lo = ends[0] - index_base;
+    p_hi = ends[1] - index_base;
+  }
+  HIPCHK(hipMemsetAsync(mcount, 0, sizeof(int32_t) * std::max<int64_t>(nloc, 1), st));
+  HIPCHK(hipMemsetAsync(flag, 0, std::max<int64_t>(nloc, 1), st));
+  if (nloc > 0)
+    launch_csr_build_scatter(st, row_ptr, rp64, col_idx, ci64, vals, n, p_lo, p_hi, index_base, lower ? 1 : 0, r0, nloc, o.csr_rp, mcount,
+                             o.csr_col, o.csr_val, tie);
+  launch_csr_build_flag(st, o.csr_rp, nloc, lnnz, o.csr_col, tie, flag);
+  launch_csr_build_sort_rows(st, o.csr_rp, nloc, flag, o.csr_col, o.csr_val, tie);
+  // rows longer than one LDS tile that are out of order: tiles sorted, then merged (one row at a time)
+  std::vector<int64_t> longs_unsorted;
+  {
+    const int64_t tile = csr_build_sort_tile();
+    int64_t longest = 0;
+    std::vector<int64_t> cand;
+    for (int64_t i = 0; i < nloc; ++i)
+      if (rp[(size_t)i + 1] - rp[(size_t)i] > tile) cand.push_back(i);
+    if (!cand.empty()) {
+      std::vector<uint8_t> hflag((size_t)nloc);
+      CHK(readback(hflag.data(), flag, (size_t)nloc));
+      for (int64_t i : cand)
+        if (hflag[(size_t)i]) { longs_unsorted.push_back(i); longest = std::max(longest, rp[(size_t)i + 1] - rp[(size_t)i]); }
+    }
+    if (!longs_unsorted.empty()) {
+      uint64_t *k0 = nullptr, *k1 = nullptr;
+      double *v0 = nullptr, *v1 = nullptr;
+      take(&k0, (size_t)longest); take(&k1, (size_t)longest); take(&v0, (size_t)longest); take(&v1, (size_t)longest);
+      if (oom) return no_memory("sorting a row of " + std::to_string(longest) + " entries");
+      for (int64_t i : longs_unsorted)
+        launch_csr_build_sort_long(st, rp[(size_t)i], rp[(size_t)i + 1] - rp[(size_t)i], o.csr_col, o.csr_val, tie, k0, v0, k1, v1);
+    }
+  }
+  // the diagonal of the whole matrix: this rank's slab to o.diag, all of it to the host copy
+  double* diag = nullptr;
+  take(&diag, (size_t)n);
+  if (oom) return no_memory("the diagonal");
+  launch_csr_build_diag(st, row_ptr, rp64, col_idx, ci64, vals, n, index_base, dcount, dfirst, diag);
+  if (nloc > 0) HIPCHK(hipMemcpyAsync(o.diag, diag + r0, sizeof(double) * nloc, hipMemcpyDeviceToDevice, st));
+  std::vector<double> hdiag((size_t)n);
+  CHK(readback(hdiag.data(), diag, sizeof(double) * (size_t)n));
+  // ---- the work list of the block product, over the canonical offsets (as dav_set_operator_csr builds it)
+  std::vector<CsrItem> items;
+  std::vector<CsrLong> longs;
+  int nslots = 0;
+  csr_build_items(rp, items, longs, &nslots);
+  auto upload = [&](auto** dst, const auto* src, size_t count) -> int {
+    if (!keep(dst, count)) return 1;
+    if (count > 0 && hipMemcpy(*dst, src, sizeof(**dst) * count, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return 1; }
+    return 0;
+  };
+  if (upload(&o.csr_items, items.data(), items.size()) || upload(&o.csr_longs, longs.data(), longs.size()) ||
+      !keep(&o.csr_part, (size_t)nslots * 64))
+    return no_memory("the work list of " + std::to_string(lnnz) + " entries of this rank");
+  HIPCHK(hipStreamSynchronize(st));                 // the caller's arrays are free again when the call returns
+  HIPCHK(hipGetLastError());
+  o.csr_nitems = (int)items.size();
+  o.csr_nlong = (int)longs.size();
+  o.csr_nnz = lnnz;
+  o.storage = 0;
+  e->diag_host[which].swap(hdiag);
+  if (which == DAV_OP_A) e->basis_order.clear();
+  o.kind = DAV_KIND_CSR;
+  return 0;
+}
+
 // ---- a symmetric matrix in BSR form (dav_set_operator_bsr) ---------------------------------------------------------------------------
 // Work list of the block product over the canonical local block rows rp[0..nbl]: runs of whole block rows of at most BSR_ROWS matrix rows
 // and BSR_CHUNK blocks together, every block row longer than BSR_CHUNK cut into chunks at multiples of BSR_CHUNK from its first block.

@@ -190,6 +190,40 @@ void launch_spmm_csr(hipStream_t st, const CsrItem* items, int nitems, const int
                      const double* xt, int64_t xt_gstride, int groups, int kk, double* part, double* dst, int64_t ldd);
 void launch_spmm_csr_finish(hipStream_t st, const CsrLong* longs, int nlong, const double* part, int kk, double* dst, int64_t ldd);
 
+// ---- K1c': device build of a CSR operator (k_csr_build.hip; dav_set_operator_csr_dev) -----------------------------------------------
+// The caller's global arrays: row_ptr and col_idx of 32 (rp64 / ci64 = 0) or 64 bits, numbered from `base`.  info[4] (set to ~0 first):
+// [0] first row where row_ptr decreases, [1] row_ptr[0], [2] row_ptr[n], [3] first row of 2^32 or more entries.
+void launch_csr_build_rows(hipStream_t st, const void* rp, int rp64, int64_t n, unsigned long long* info);
+// entries [0, nnz): first_bad = the first entry with a column out of range or (lower) above the diagonal; dcount / dfirst (zero / ~0
+// first) = diagonal entries of every row and the first of them; mcount (zero first, lower) = mirrored entries of every local row
+void launch_csr_build_check(hipStream_t st, const void* rp, int rp64, const void* col, int ci64, int64_t n, int64_t nnz, int base, int lower,
+                            int64_t r0, int64_t nloc, unsigned long long* first_bad, int32_t* mcount, uint32_t* dcount,
+                            unsigned long long* dfirst);
+// out[0] = row of entry p, out[1] = col_idx[p]
+void launch_csr_build_locate(hipStream_t st, const void* rp, int rp64, const void* col, int ci64, int64_t n, int base, int64_t p, int64_t* out);
+// lrp[0..nloc] = int64 offsets of the canonical local rows (own + mcount entries); tile_sums holds csr_build_scan_tiles(nloc) values
+void launch_csr_build_offsets(hipStream_t st, const void* rp, int rp64, int64_t r0, int64_t nloc, const int32_t* mcount, int64_t* lrp,
+                              int64_t* tile_sums);
+int64_t csr_build_scan_tiles(int64_t m);
+// entries [p_lo, p_hi): own entries of local rows and (lower) mirrored entries to the canonical rows, columns narrowed to int32 without
+// the base; fill (zero first) = slots taken per local row; tie (lower: required; full: nullptr) = offset of each entry in its source row
+void launch_csr_build_scatter(hipStream_t st, const void* rp, int rp64, const void* col, int ci64, const double* vals, int64_t n, int64_t p_lo,
+                              int64_t p_hi, int base, int lower, int64_t r0, int64_t nloc, const int64_t* lrp, int32_t* fill, int32_t* ocol,
+                              double* oval, uint32_t* tie);
+// flag[i] = 1 (zero first) where canonical row i is not in key order (column, tie)
+void launch_csr_build_flag(hipStream_t st, const int64_t* lrp, int64_t nloc, int64_t lnnz, const int32_t* ocol, const uint32_t* tie,
+                           uint8_t* flag);
+// flagged rows of at most csr_build_sort_tile() entries sorted in place by key
+void launch_csr_build_sort_rows(hipStream_t st, const int64_t* lrp, int64_t nloc, const uint8_t* flag, int32_t* ocol, double* oval,
+                                const uint32_t* tie);
+int64_t csr_build_sort_tile();
+// one longer row [a, a + m) sorted in place by key; k0 / v0 / k1 / v1: scratch of m keys and values each
+void launch_csr_build_sort_long(hipStream_t st, int64_t a, int64_t m, int32_t* ocol, double* oval, const uint32_t* tie, uint64_t* k0,
+                                double* v0, uint64_t* k1, double* v1);
+// diag[0..n) = the diagonal of the whole matrix (a row's diagonal entries summed in input order from +0.0)
+void launch_csr_build_diag(hipStream_t st, const void* rp, int rp64, const void* col, int ci64, const double* vals, int64_t n, int base,
+                           const uint32_t* dcount, const unsigned long long* dfirst, double* diag);
+
 // ---- K1d: BSR block product on the matrix cores (k_bsrmm.hip) ------------------------------------------------------------------------
 // Y[rows of this rank, 0:kk] = A_bsr * X, uniform block size 1 <= b <= 16, blocks column-major on the device.  Work list built on the
 // host (engine_operators.hip: bsr_build_items) in the CSR item types over LOCAL block rows: a run of whole block rows of at most BSR_ROWS

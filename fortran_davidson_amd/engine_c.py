@@ -69,6 +69,49 @@ def csr_arrays(indptr, indices=None, data=None, n=None):
     return rp, ci, vv
 
 
+def is_torch_csr(t):
+    """True for a torch tensor in the sparse CSR layout (torch itself is imported only when the object comes from it)"""
+    if not type(t).__module__.startswith("torch"):
+        return False
+    import torch
+    return isinstance(t, torch.Tensor) and t.layout == torch.sparse_csr
+
+
+def device_csr_tensors(row_ptr, col_idx, vals, n, device):
+    """The checks of a CSR matrix in device tensors before any library call: int32 / int64 indices and float64 values (TypeError, never
+    converted), contiguous tensors on cuda:`device` and n + 1 offsets (ValueError).  Returns (row_ptr_bits, col_bits)."""
+    import torch
+    args = (("row_ptr", row_ptr, (torch.int32, torch.int64)), ("col_idx", col_idx, (torch.int32, torch.int64)),
+            ("vals", vals, (torch.float64,)))
+    for name, t, kinds in args:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"device CSR input: {name} must be a torch tensor, not {type(t).__name__}")
+        if t.dtype not in kinds:
+            raise TypeError(f"device CSR input: {name} has dtype {t.dtype}, expected " + " or ".join(str(k) for k in kinds))
+    for name, t, _ in args:
+        if t.layout != torch.strided or not t.is_contiguous() or t.dim() != 1:
+            raise ValueError(f"device CSR input: {name} must be a contiguous one-dimensional tensor")
+    for name, t, _ in args:
+        if t.device.type != "cuda" or t.device.index != device:
+            raise ValueError(f"device CSR input: {name} lies on {t.device}, the engine on cuda:{device}")
+    if row_ptr.numel() != n + 1:
+        raise ValueError(f"device CSR input: row_ptr must hold n + 1 = {n + 1} offsets, it holds {row_ptr.numel()}")
+    nnz = int(row_ptr[-1]) - int(row_ptr[0])          # two values read back: the kernels must not read past the tensors
+    if col_idx.numel() < nnz or vals.numel() < nnz:
+        raise ValueError(f"device CSR input: row_ptr says {nnz} entries, col_idx / vals hold {col_idx.numel()} / {vals.numel()}")
+    return (64 if row_ptr.dtype == torch.int64 else 32), (64 if col_idx.dtype == torch.int64 else 32)
+
+
+def torch_csr_parts(t):
+    """(crow_indices, col_indices, values) of a torch sparse CSR tensor; on the CPU as numpy arrays"""
+    if t.dim() != 2 or t.shape[0] != t.shape[1]:
+        raise ValueError(f"CSR input: a square matrix is needed, the tensor has shape {tuple(t.shape)}")
+    parts = (t.crow_indices(), t.col_indices(), t.values())
+    if t.device.type == "cpu":
+        return tuple(x.numpy() for x in parts)
+    return parts
+
+
 def check_csr(indptr, indices, data, n, base=0, lower=False):
     """Everything dav_set_operator_csr validates, checked in Python (ValueError) - for the Fortran doors, which stop the process on an
     engine error.  Returns the arrays as csr_arrays does."""
@@ -176,6 +219,7 @@ class CEngine:
             self.h = h
         else:
             self.h = C.c_void_p(handle)
+        self.device = device
         st = self.stats()
         self.n = st.n
 
@@ -310,13 +354,32 @@ class CEngine:
 
     def set_operator_csr(self, which, indptr, indices=None, data=None, base=0, lower=False):
         """dav_set_operator_csr: a symmetric matrix in CSR form (the global arrays; indptr / indices numbered from `base`), every nonzero
-        (lower=False) or only the entries with column <= row (lower=True).  Three numpy arrays, or one object with .tocsr().  The
-        engine validates the input (DavidsonHipError) and leaves the operator unset when it refuses it."""
+        (lower=False) or only the entries with column <= row (lower=True).  Three numpy arrays, or one object with .tocsr(), or a
+        torch.sparse_csr_tensor (one on the GPU goes to set_operator_csr_dev).  The engine validates the input (DavidsonHipError) and
+        leaves the operator unset when it refuses it."""
+        if is_torch_csr(indptr):
+            parts = torch_csr_parts(indptr)
+            if indptr.device.type != "cpu":
+                return self.set_operator_csr_dev(which, *parts, base=base, lower=lower)
+            indptr, indices, data = parts
         rp, ci, vv = csr_arrays(indptr, indices, data, self.n)
         ci_p = ci.ctypes.data_as(C.POINTER(C.c_int32)) if ci.size else (C.c_int32 * 1)()
         vv_p = _dp(vv) if vv.size else (C.c_double * 1)()
         self._chk(self.lib.dav_set_operator_csr(self.h, C.c_int(which), rp.ctypes.data_as(C.POINTER(C.c_int64)), ci_p, vv_p, C.c_int(base),
                                                 C.c_int(CSR_LOWER if lower else CSR_FULL)))
+
+    def set_operator_csr_dev(self, which, row_ptr, col_idx, vals, base=0, lower=False):
+        """dav_set_operator_csr_dev: the matrix of set_operator_csr as torch tensors on the engine's device, built on the GPU - row_ptr
+        (n + 1) and col_idx int32 or int64, vals float64, all contiguous.  Other dtypes are a TypeError (never converted).  Torch's
+        current stream on the device is synchronised first, so work queued on it that writes the arrays is complete.  The engine's
+        refusal is a DavidsonHipError; the operator is then unset."""
+        rpb, cib = device_csr_tensors(row_ptr, col_idx, vals, self.n, self.device)
+        import torch
+        torch.cuda.current_stream(row_ptr.device).synchronize()
+        self._chk(self.lib.dav_set_operator_csr_dev(self.h, C.c_int(which), C.c_void_p(row_ptr.data_ptr()), C.c_int(rpb),
+                                                    C.c_void_p(col_idx.data_ptr() or None), C.c_int(cib),
+                                                    C.c_void_p(vals.data_ptr() or None), C.c_int(base),
+                                                    C.c_int(CSR_LOWER if lower else CSR_FULL)))
 
     def set_operator_bsr(self, which, indptr, indices=None, data=None, base=0, lower=False, layout=BSR_ROW_MAJOR):
         """dav_set_operator_bsr: a symmetric matrix in BSR form with square blocks (the global arrays; indptr / indices count block

@@ -7,7 +7,7 @@ module davidson_c_api
   use davidson, only: generalized_eigensolver
   use davidson_device
   use davidson_free, only: free_matmul
-  use davidson_sparse, only: csr_matrix, bsr_matrix, engine_set_sparse
+  use davidson_sparse, only: csr_matrix, bsr_matrix, engine_set_sparse, engine_set_sparse_device
   use lapack_wrapper
   use array_utils
   implicit none
@@ -291,6 +291,22 @@ contains
     call c_f_pointer(p, eng)
     call engine_set_sparse(eng, int(which), csr_from_c(n, rp, col, vals, base, lower))
   end subroutine fd_engine_set_sparse
+
+  !> engine_set_sparse_device(eng, which, n, ...) with device arrays: returns the engine's status (0 = set; otherwise dav_last_error
+  !> says why and the operator is unset) instead of stopping the process - device arrays cannot be checked on the host first
+  function fd_engine_set_sparse_device(p, which, n, rp, rp_bits, col, col_bits, vals, base, lower) result(stat) &
+       bind(C, name="fd_engine_set_sparse_device")
+    type(c_ptr), value :: p
+    integer(c_int), value :: which, n, rp_bits, col_bits, base, lower
+    type(c_ptr), value :: rp, col, vals
+    integer(c_int) :: stat
+    type(davidson_engine), pointer :: eng
+    integer :: st
+    call c_f_pointer(p, eng)
+    call engine_set_sparse_device(eng, int(which), int(n), rp, col, vals, base=int(base), lower=lower /= 0, &
+         row_ptr_bits=int(rp_bits), col_bits=int(col_bits), stat=st)
+    stat = int(st, c_int)
+  end function fd_engine_set_sparse_device
 
   !> engine_set_sparse(eng, which, a) with a bsr_matrix from C arrays numbered from `base` (values in Fortran order, as bsr_from_c)
   subroutine fd_engine_set_block_sparse(p, which, n, b, rp, col, vals, base, lower) bind(C, name="fd_engine_set_block_sparse")

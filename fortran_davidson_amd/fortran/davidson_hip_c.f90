@@ -171,6 +171,20 @@ module davidson_hip_c
        real(c_double), intent(in) :: diag(*)
        integer(c_int) :: ierr
      end function
+     !> the same matrix from device arrays of the engine's device, built on the GPU (row_ptr_bits / col_bits: 32 or 64)
+     function dav_set_operator_csr_dev(h, which, row_ptr, row_ptr_bits, col_idx, col_bits, vals, index_base, triangle) &
+          bind(C, name="dav_set_operator_csr_dev") result(ierr)
+       import :: c_ptr, c_int
+       type(c_ptr), value :: h
+       integer(c_int), value :: which
+       type(c_ptr), value :: row_ptr
+       integer(c_int), value :: row_ptr_bits
+       type(c_ptr), value :: col_idx
+       integer(c_int), value :: col_bits
+       type(c_ptr), value :: vals
+       integer(c_int), value :: index_base, triangle
+       integer(c_int) :: ierr
+     end function
      !> a symmetric matrix in CSR form, global host arrays (ABI 109); index_base 1 = Fortran numbering of rows and columns
      function dav_set_operator_csr(h, which, row_ptr, col_idx, vals, index_base, triangle) bind(C, name="dav_set_operator_csr") &
           result(ierr)

@@ -9,7 +9,7 @@ module davidson_sparse
   use davidson_engine_setup, only: davidson_engine
   implicit none
   private
-  public :: csr_matrix, bsr_matrix, engine_set_sparse
+  public :: csr_matrix, bsr_matrix, engine_set_sparse, engine_set_sparse_device
 
   !> A symmetric real matrix of order n in CSR form, 1-based: the entries of row i are col_idx / values(row_ptr(i) : row_ptr(i+1) - 1).
   !> lower = .true.: only the entries with column <= row are given (the engine mirrors the strict lower part); .false.: every nonzero
@@ -97,6 +97,48 @@ contains
     ! a stored matrix: the dense driver's sticky convergence flags, as for engine_set_dense
     if (which == 1) eng%free_semantics = .false.
   end subroutine engine_set_sparse_csr
+
+  !> Operator A (which = 1) or B (which = 2) of the engine from a CSR matrix of order n whose arrays are DEVICE memory of the engine's
+  !> device (hipfort, OpenMP offload, a GPU assembly stage): dav_set_operator_csr_dev builds the operator on the GPU, bit for bit as
+  !> engine_set_sparse builds it from a csr_matrix holding the same arrays.  base: 1 (default, Fortran numbering) or 0; lower: only the
+  !> entries with column <= row are given; row_ptr_bits / col_bits: 64 (default for row_ptr) or 32 (default for col_idx).  The arrays
+  !> must be complete when the call is made (a caller that writes them asynchronously synchronises first) and are free again when it
+  !> returns.  stat present: a refused matrix returns its non-zero status here (dav_last_error says why; the operator is left unset),
+  !> otherwise the program stops.
+  subroutine engine_set_sparse_device(eng, which, n, row_ptr, col_idx, vals, base, lower, row_ptr_bits, col_bits, stat)
+    type(davidson_engine), intent(inout) :: eng
+    integer, intent(in) :: which, n
+    type(c_ptr), intent(in) :: row_ptr, col_idx, vals
+    integer, intent(in), optional :: base, row_ptr_bits, col_bits
+    logical, intent(in), optional :: lower
+    integer, intent(out), optional :: stat
+    integer(c_int) :: ib, rb, cb, tri, ierr
+    if (n /= eng%n) then
+       if (present(stat)) then
+          stat = -1
+          return
+       end if
+       print *, "engine_set_sparse_device: the matrix must be of order ", eng%n
+       error stop
+    end if
+    ib = 1_c_int
+    rb = 64_c_int
+    cb = 32_c_int
+    tri = DAV_CSR_FULL
+    if (present(base)) ib = int(base, c_int)
+    if (present(row_ptr_bits)) rb = int(row_ptr_bits, c_int)
+    if (present(col_bits)) cb = int(col_bits, c_int)
+    if (present(lower)) then
+       if (lower) tri = DAV_CSR_LOWER
+    end if
+    ierr = dav_set_operator_csr_dev(eng%h, int(which - 1, c_int), row_ptr, rb, col_idx, cb, vals, ib, tri)
+    if (present(stat)) then
+       stat = int(ierr)
+    else
+       call check_dav(ierr, "dav_set_operator_csr_dev")
+    end if
+    if (ierr == 0 .and. which == 1) eng%free_semantics = .false.
+  end subroutine engine_set_sparse_device
 
   function new_bsr_matrix(n, b, row_ptr, col_idx, values, lower) result(a)
     integer, intent(in) :: n, b

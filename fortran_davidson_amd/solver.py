@@ -15,8 +15,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import fortran_lib
-from .engine_c import CEngine, check_bsr, check_csr
+from ._lib import fortran_lib, hip_lib
+from .engine_c import CEngine, DavidsonHipError, check_bsr, check_csr, device_csr_tensors, is_torch_csr, torch_csr_parts
 
 _METHOD = {"DPR": 0, "GJD": 1}
 _CB = C.CFUNCTYPE(None, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
@@ -60,6 +60,8 @@ def _i32(a):
 def _sparse_input(a, n=None, lower=False):
     """(n, indptr, indices, data) of a CSR operator given as a tuple (indptr, indices, data) or an object with .tocsr(), 0-based,
     validated here (ValueError) - the Fortran door stops the process on an engine error"""
+    if is_torch_csr(a):
+        a = torch_csr_parts(a)
     if hasattr(a, "tocsr"):
         m = a.tocsr()
         a = (m.indptr, m.indices, m.data)
@@ -69,13 +71,27 @@ def _sparse_input(a, n=None, lower=False):
     return n, rp, ci, vv if vv.size else np.zeros(1)
 
 
+def _is_device_csr(a):
+    return is_torch_csr(a) and a.device.type != "cpu"
+
+
 def generalized_eigensolver_sparse(indptr, indices, data, lowest, method, max_iterations, tolerance, max_dim_sub=None, second=None,
                                    lower=False):
     """`call generalized_eigensolver(a_csr, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters [, max_dim_sub]
     [, b_csr])` (the csr_matrix specific of module davidson) with A in CSR form, 0-based: three arrays, or `indptr` an object with
-    .tocsr() and indices = data = None.  `second`: B the same way - a tuple (indptr, indices, data) or an object with .tocsr().
+    .tocsr() and indices = data = None.  `second`: B the same way - a tuple (indptr, indices, data) or an object with .tocsr().  Either
+    may also be a torch.sparse_csr_tensor; one on the GPU is built there (DavidsonEngine.set_sparse on the tensor's device).
     lower=True: only the entries with column <= row are given, for A and B.  Returns (eigenvalues, eigenvectors, iters)."""
     a = indptr if indices is None and data is None else (indptr, indices, data)
+    if _is_device_csr(a) or _is_device_csr(second):
+        # a matrix in device memory: an engine of its own, built on the GPU (DavidsonEngine.set_sparse)
+        n = a.shape[0] if hasattr(a, "shape") else len(a[0]) - 1
+        device = (a if _is_device_csr(a) else second).device.index
+        with DavidsonEngine(n, lowest, max_dim_sub, gev=second is not None, device=device) as eng:
+            eng.set_sparse(1, a, lower=lower)
+            if second is not None:
+                eng.set_sparse(2, second, lower=lower)
+            return eng.solve(method, max_iterations, tolerance)
     n, rp, ci, vv = _sparse_input(a, None, lower)
     if second is not None:
         _, rpb, cib, vvb = _sparse_input(second, n, lower)
@@ -169,7 +185,8 @@ class DavidsonEngine:
         self.p = C.c_void_p(self.lib.fd_engine_create(C.c_int(n), C.c_int(lowest), C.c_int(self.max_dim),
                                                       C.c_int(1 if gev else 0), C.c_int(device), C.c_int(rank),
                                                       C.c_int(nranks)))
-        self.c = CEngine(handle=self.lib.fd_engine_handle(self.p))
+        self.device = device
+        self.c = CEngine(handle=self.lib.fd_engine_handle(self.p), device=device)
         if storage != "full":
             self.lib.fd_engine_set_storage(self.p, C.c_int({"full": 0, "symmetric": 1}[storage]))
 
@@ -194,11 +211,25 @@ class DavidsonEngine:
 
     def set_sparse(self, which, indptr, indices=None, data=None, lower=False):
         """Operator A (which=1) or B (which=2) as a symmetric matrix in CSR form, 0-based (Fortran: engine_set_sparse): three arrays,
-        or `indptr` an object with .tocsr().  lower=True: only the entries with column <= row are given."""
+        or `indptr` an object with .tocsr(), or a torch.sparse_csr_tensor - one on the engine's GPU is built there (Fortran:
+        engine_set_sparse_device; a refused matrix raises DavidsonHipError and leaves the operator unset).  lower=True: only the
+        entries with column <= row are given."""
         a = indptr if indices is None and data is None else (indptr, indices, data)
+        if _is_device_csr(a):
+            return self._set_sparse_device(which, *torch_csr_parts(a), lower=lower)
         _, rp, ci, vv = _sparse_input(a, self.n, lower)
         self.lib.fd_engine_set_sparse(self.p, C.c_int(which), C.c_int(self.n), _i64(rp), _i32(ci), _dp(vv), C.c_int(0),
                                       C.c_int(1 if lower else 0))
+
+    def _set_sparse_device(self, which, row_ptr, col_idx, vals, lower=False):
+        rpb, cib = device_csr_tensors(row_ptr, col_idx, vals, self.n, self.device)
+        import torch
+        torch.cuda.current_stream(row_ptr.device).synchronize()
+        st = self.lib.fd_engine_set_sparse_device(self.p, C.c_int(which), C.c_int(self.n), C.c_void_p(row_ptr.data_ptr()), C.c_int(rpb),
+                                                  C.c_void_p(col_idx.data_ptr() or None), C.c_int(cib),
+                                                  C.c_void_p(vals.data_ptr() or None), C.c_int(0), C.c_int(1 if lower else 0))
+        if st != 0:
+            raise DavidsonHipError(hip_lib().dav_last_error().decode())
 
     def set_block_sparse(self, which, indptr, indices=None, data=None, lower=False):
         """Operator A (which=1) or B (which=2) as a symmetric matrix in BSR form, 0-based (Fortran: engine_set_sparse with a bsr_matrix):

@@ -218,6 +218,22 @@ int dav_set_operator_device(dav_handle_t h, int which, dav_device_apply_fn fn, v
 enum { DAV_CSR_FULL = 0, DAV_CSR_LOWER = 1 };
 int dav_set_operator_csr(dav_handle_t h, int which, const int64_t* row_ptr /* n+1 */, const int32_t* col_idx, const double* vals,
                          int index_base /* 0 or 1 */, int triangle);
+/* The same matrix from DEVICE arrays, built on the GPU by the engine's own kernels.  Purely additive within ABI 109.  The arguments mean
+ * what they mean for dav_set_operator_csr - the GLOBAL matrix on every rank, index_base, DAV_CSR_FULL / DAV_CSR_LOWER - except that
+ * row_ptr, col_idx and vals are pointers to device memory of the engine's device, and that row_ptr and col_idx may each hold 32- or 64-bit
+ * signed integers (row_ptr_bits, col_bits: 32 or 64; a torch CSR tensor has int64 for both, rocSPARSE arrays often int32).  The arrays
+ * must be COMPLETE when the call is made: a caller that writes them on a stream of its own synchronises that stream first (the engine
+ * reads them on its own stream).  The pointers are checked before anything is launched (hipPointerGetAttributes: a null pointer where one
+ * is needed, or memory that is not device memory of the engine's device - pageable or pinned host memory, another device - is refused,
+ * the message names the argument); the rules of dav_set_operator_csr are then checked on the device, with the same messages and the
+ * FIRST offending row or entry named; a row of 2^32 entries or more is refused as well.  A refused call leaves the operator UNSET and the
+ * engine usable.  The storage built - row offsets, columns, values, the diagonal and everything derived from them - is bit for bit what
+ * dav_set_operator_csr builds from the same matrix in host memory, so applies and solves agree bitwise.  The call returns after the
+ * engine has stopped reading the caller's arrays: they may be freed or overwritten at once.  Scratch comes from the engine's allocator
+ * (about 20 bytes per row of the matrix plus, with DAV_CSR_LOWER, 4 bytes per entry of this rank) and is released before the call
+ * returns. */
+int dav_set_operator_csr_dev(dav_handle_t h, int which, const void* row_ptr, int row_ptr_bits /* 32 | 64 */, const void* col_idx,
+                             int col_bits /* 32 | 64 */, const double* vals, int index_base /* 0 or 1 */, int triangle);
 /* A symmetric real matrix in BSR (block sparse row) form with a uniform block size b, 1 <= b <= 16, n a multiple of b.  Purely additive
  * within ABI 109: no existing entry, constant or the layout of dav_stats changes.  Host pointers to the GLOBAL matrix, as for
  * dav_set_operator_csr: block_row_ptr[0..n/b] (int64), block_col_idx (block columns) and vals (b * b values per block) of the
