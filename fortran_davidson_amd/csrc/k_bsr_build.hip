@@ -1,0 +1,119 @@
+// Device build of a BSR operator from the caller's device arrays (dav_set_operator_bsr_dev, engine_operators.hip): the values.
+//
+// The index level of a BSR matrix is a CSR pattern over its n / b block rows and is built by the kernels of k_csr_build.hip, which carry
+// the SOURCE of every block - input position p and whether the block is mirrored, src = p << 1 | tr - to its canonical place q.  Here the
+// 8 b^2 bytes of every block move once:  val[q b^2 + k b + m] = entry (tr ? k : m, tr ? m : k) of input block p  (column-major blocks, a
+// mirrored block the transpose of its source).  A row-major own block and a column-major mirrored block are transposed on the way, the
+// other two are copied.  Values are moved, never computed with.
+//
+// gather  one workgroup (256 threads, wave64) per tile of NB consecutive canonical blocks, NB b^2 <= 2048 values.  The tile is read block
+//         by block in the caller's order - consecutive lanes read consecutive doubles, whole 128-byte segments wherever a block holds one
+//         (b >= 4) - and laid into LDS at the place its element has in the output block, rows padded to an odd length so that the
+//         transposing store (lanes b doubles apart) spreads over the banks.  After the barrier the tile is written from LDS as ONE
+//         contiguous run of NB b^2 doubles: whole 128-byte segments on the output side for every b.  All loads of a thread are issued
+//         before its first LDS store.  b is a template parameter (1..16): every division of the element index is by a constant.
+// diag    one thread per row of the matrix: the diagonal blocks of its block row in input order from the first one the check pass found.
+#include "kernels.h"
+
+namespace {
+constexpr int BG_THREADS = 256;
+constexpr int BG_VALUES = 2048;             // values of a gather tile (8 per thread)
+constexpr int BG_BLOCKS = 512;              // at most that many blocks per tile (b = 1, 2: the block sources are staged in LDS too)
+
+template <int B> struct BgShape {
+  static constexpr int BB = B * B;
+  static constexpr int NB = BG_VALUES / BB < BG_BLOCKS ? BG_VALUES / BB : BG_BLOCKS;     // blocks per tile
+  static constexpr int BP = B | 1;                                                       // padded column length in LDS
+  static constexpr int EPT = (NB * BB + BG_THREADS - 1) / BG_THREADS;                    // values per thread
+};
+
+template <int B>
+__global__ __launch_bounds__(BG_THREADS) void bsr_build_gather_kernel(const uint64_t* __restrict__ src, int64_t lnnzb,
+                                                                      const double* __restrict__ vals, int rowmaj,
+                                                                      double* __restrict__ val) {
+  using S = BgShape<B>;
+  constexpr int BB = S::BB, NB = S::NB, BP = S::BP, EPT = S::EPT;
+  __shared__ uint64_t ssrc[NB];
+  __shared__ double tile[NB * B * BP];
+  const int64_t q0 = (int64_t)blockIdx.x * NB;
+  const int nbt = (int)(lnnzb - q0 < NB ? lnnzb - q0 : NB);        // blocks of this tile
+  const int nval = nbt * BB;
+  for (int l = threadIdx.x; l < nbt; l += BG_THREADS) ssrc[l] = src[q0 + l];
+  __syncthreads();
+  double v[EPT];
+  int at[EPT];
+#pragma unroll
+  for (int u = 0; u < EPT; ++u) {
+    const int e = u * BG_THREADS + threadIdx.x;
+    at[u] = -1;
+    if (e < nval) {
+      const int l = e / BB, r = e - l * BB;
+      const uint64_t s = ssrc[l];
+      v[u] = vals[(int64_t)(s >> 1) * BB + r];
+      const int i = r / B, j = r - i * B;                            // element r of the input block: (i, j) in the caller's layout
+      const bool transpose = ((int)(s & 1) != 0) != (rowmaj != 0);   // row-major own, column-major mirrored
+      at[u] = l * (B * BP) + (transpose ? j * BP + i : i * BP + j);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < EPT; ++u)
+    if (at[u] >= 0) tile[at[u]] = v[u];
+  __syncthreads();
+  double* __restrict__ out = val + q0 * BB;
+#pragma unroll
+  for (int u = 0; u < EPT; ++u) {
+    const int e = u * BG_THREADS + threadIdx.x;
+    if (e < nval) {
+      const int l = e / BB, r = e - l * BB;
+      const int k = r / B, m = r - k * B;
+      out[e] = tile[l * (B * BP) + k * BP + m];
+    }
+  }
+}
+
+template <class RP, class CI>
+__global__ __launch_bounds__(BG_THREADS) void bsr_build_diag_kernel(int b, const RP* __restrict__ rp, const CI* __restrict__ col,
+                                                                    const double* __restrict__ vals, int64_t nb, int base,
+                                                                    const uint32_t* __restrict__ dcount,
+                                                                    const unsigned long long* __restrict__ dfirst, double* __restrict__ diag) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x, n = nb * b, bb = (int64_t)b * b;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int64_t I = i / b;
+    const int64_t mm = (i - I * b) * (b + 1);
+    const uint32_t cnt = dcount[I];
+    double s = 0.0;
+    if (cnt > 0) {
+      const int64_t p0 = (int64_t)dfirst[I], p1 = (int64_t)rp[I + 1] - base;
+      uint32_t seen = 0;
+      for (int64_t p = p0; p < p1 && seen < cnt; ++p)
+        if ((int64_t)col[p] - base == I) { s += vals[p * bb + mm]; ++seen; }
+    }
+    diag[i] = s;
+  }
+}
+
+template <int B>
+void bg_launch(hipStream_t st, const uint64_t* src, int64_t lnnzb, const double* vals, int rowmaj, double* val) {
+  constexpr int NB = BgShape<B>::NB;
+  hipLaunchKernelGGL(bsr_build_gather_kernel<B>, dim3((unsigned)((lnnzb + NB - 1) / NB)), dim3(BG_THREADS), 0, st, src, lnnzb, vals, rowmaj, val);
+}
+}  // namespace
+
+void launch_bsr_build_gather(hipStream_t st, int bs, const uint64_t* src, int64_t lnnzb, const double* vals, int rowmaj, double* val) {
+  if (lnnzb <= 0) return;
+  switch (bs) {
+#define BG_CASE(B) case B: bg_launch<B>(st, src, lnnzb, vals, rowmaj, val); break;
+    BG_CASE(1) BG_CASE(2) BG_CASE(3) BG_CASE(4) BG_CASE(5) BG_CASE(6) BG_CASE(7) BG_CASE(8)
+    BG_CASE(9) BG_CASE(10) BG_CASE(11) BG_CASE(12) BG_CASE(13) BG_CASE(14) BG_CASE(15) BG_CASE(16)
+#undef BG_CASE
+    default: break;                          // the engine has refused any other block size
+  }
+}
+
+void launch_bsr_build_diag(hipStream_t st, int bs, const void* rp, int rp64, const void* col, int ci64, const double* vals, int64_t nb,
+                           int base, const uint32_t* dcount, const unsigned long long* dfirst, double* diag) {
+  if (nb <= 0) return;
+  const unsigned grid = (unsigned)std::min<int64_t>(8192, (nb * bs + BG_THREADS - 1) / BG_THREADS);
+  cb_dispatch(rp64, ci64, [&](auto r_, auto c_) { using RP = decltype(r_); using CI = decltype(c_); hipLaunchKernelGGL((bsr_build_diag_kernel<RP, CI>), dim3(grid), dim3(BG_THREADS), 0, st, bs, (const RP*)rp, (const CI*)col, vals, nb,
+                             base, dcount, dfirst, diag); });
+}

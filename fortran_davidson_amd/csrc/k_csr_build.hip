@@ -17,6 +17,10 @@
 //            then merged in passes (each element finds its place in the other run by a binary search: the keys are unique)
 //   diag     the diagonal of the whole matrix: a row's diagonal entries summed in input order from +0.0
 // The row of an entry is found by a binary search over row_ptr; consecutive entries of a thread reuse the previous row.
+//
+// The scatter and the sorts are templates on the 8-byte payload V that travels with a column: the entry's value (double, CSR), or the
+// SOURCE of a block (uint64_t: input position p << 1 | mirrored) when the rows are the block rows of a BSR matrix, whose b * b values
+// are moved once, after the order is known (dav_set_operator_bsr_dev, k_bsr_build.hip).
 #include "kernels.h"
 
 namespace {
@@ -42,6 +46,13 @@ __device__ __forceinline__ int64_t cb_row_of(const RP* __restrict__ rp, int64_t 
 }
 
 __device__ __forceinline__ uint64_t cb_key(int32_t c, uint32_t tie) { return ((uint64_t)(uint32_t)c << 32) | tie; }
+
+// what input entry p carries to its canonical place (vals is not read for a block source)
+template <class V> __device__ __forceinline__ V cb_payload(const double* __restrict__ vals, int64_t p, bool mirrored);
+template <> __device__ __forceinline__ double cb_payload<double>(const double* __restrict__ vals, int64_t p, bool) { return vals[p]; }
+template <> __device__ __forceinline__ uint64_t cb_payload<uint64_t>(const double* __restrict__, int64_t p, bool mirrored) {
+  return ((uint64_t)p << 1) | (mirrored ? 1u : 0u);
+}
 
 template <class RP>
 __global__ __launch_bounds__(CB_THREADS) void csr_build_rows_kernel(const RP* __restrict__ rp, int64_t n, unsigned long long* __restrict__ info) {
@@ -163,12 +174,12 @@ __global__ __launch_bounds__(CB_THREADS) void csr_build_scan_apply_kernel(int64_
 
 // entries [p_lo, p_hi) of the caller's arrays: own entries of local rows to their place, mirrored entries (lower) to an atomic slot of
 // their target row behind its own segment; tie (lower only) = offset of the entry within its source row
-template <class RP, class CI>
+template <class RP, class CI, class V>
 __global__ __launch_bounds__(CB_THREADS) void csr_build_scatter_kernel(const RP* __restrict__ rp, const CI* __restrict__ col,
                                                                        const double* __restrict__ vals, int64_t n, int64_t p_lo, int64_t p_hi,
                                                                        int base, int lower, int64_t r0, int64_t nloc,
                                                                        const int64_t* __restrict__ lrp, int32_t* __restrict__ fill,
-                                                                       int32_t* __restrict__ ocol, double* __restrict__ oval,
+                                                                       int32_t* __restrict__ ocol, V* __restrict__ oval,
                                                                        uint32_t* __restrict__ tie) {
   const int64_t tile = p_lo + (int64_t)blockIdx.x * CB_THREADS * CB_EPT;
   int64_t row = 0;
@@ -183,14 +194,14 @@ __global__ __launch_bounds__(CB_THREADS) void csr_build_scatter_kernel(const RP*
     if (row >= r0 && row < r0 + nloc) {
       const int64_t q = lrp[row - r0] + off;
       ocol[q] = (int32_t)j;
-      oval[q] = vals[p];
+      oval[q] = cb_payload<V>(vals, p, false);
       if (tie) tie[q] = (uint32_t)off;
     }
     if (lower && j < row && j >= r0 && j < r0 + nloc) {
       const int64_t own = (int64_t)rp[j + 1] - (int64_t)rp[j];
       const int64_t q = lrp[j - r0] + own + atomicAdd(&fill[j - r0], 1);
       ocol[q] = (int32_t)row;
-      oval[q] = vals[p];
+      oval[q] = cb_payload<V>(vals, p, true);
       tie[q] = (uint32_t)off;
     }
   }
@@ -216,10 +227,10 @@ __global__ __launch_bounds__(CB_THREADS) void csr_build_flag_kernel(const int64_
 __device__ __forceinline__ uint32_t cb_tie(const uint32_t* tie, int64_t q, int64_t a) { return tie ? tie[q] : (uint32_t)(q - a); }
 
 // bitonic sort of m <= SORT_TILE (key, value) pairs in LDS (padded to a power of two with the largest key)
-__device__ void cb_lds_sort(uint64_t* key, double* val, int m) {
+template <class V> __device__ void cb_lds_sort(uint64_t* key, V* val, int m) {
   int P = 64;
   while (P < m) P <<= 1;
-  for (int x = m + threadIdx.x; x < P; x += CB_THREADS) { key[x] = ~0ull; val[x] = 0.0; }
+  for (int x = m + threadIdx.x; x < P; x += CB_THREADS) { key[x] = ~0ull; val[x] = V{}; }
   __syncthreads();
   for (int k = 2; k <= P; k <<= 1)
     for (int j = k >> 1; j > 0; j >>= 1) {
@@ -230,7 +241,7 @@ __device__ void cb_lds_sort(uint64_t* key, double* val, int m) {
           const bool up = (x & k) == 0;
           if ((kx > kl) == up) {
             key[x] = kl; key[l] = kx;
-            const double t = val[x]; val[x] = val[l]; val[l] = t;
+            const V t = val[x]; val[x] = val[l]; val[l] = t;
           }
         }
       }
@@ -239,11 +250,12 @@ __device__ void cb_lds_sort(uint64_t* key, double* val, int m) {
 }
 
 // flagged rows of at most SORT_TILE entries, one workgroup per row (grid-stride over the local rows), sorted in place
+template <class V>
 __global__ __launch_bounds__(CB_THREADS) void csr_build_sort_rows_kernel(const int64_t* __restrict__ lrp, int64_t nloc,
                                                                          const uint8_t* __restrict__ flag, int32_t* __restrict__ ocol,
-                                                                         double* __restrict__ oval, const uint32_t* __restrict__ tie) {
+                                                                         V* __restrict__ oval, const uint32_t* __restrict__ tie) {
   __shared__ uint64_t key[SORT_TILE];
-  __shared__ double val[SORT_TILE];
+  __shared__ V val[SORT_TILE];
   for (int64_t i = blockIdx.x; i < nloc; i += gridDim.x) {
     if (!flag[i]) continue;
     const int64_t a = lrp[i], b = lrp[i + 1];
@@ -263,11 +275,12 @@ __global__ __launch_bounds__(CB_THREADS) void csr_build_sort_rows_kernel(const i
 }
 
 // a long row [a, a + m): tile t of SORT_TILE entries sorted into (kout, vout)[t * SORT_TILE ...]
+template <class V>
 __global__ __launch_bounds__(CB_THREADS) void csr_build_sort_tiles_kernel(int64_t a, int64_t m, const int32_t* __restrict__ ocol,
-                                                                          const double* __restrict__ oval, const uint32_t* __restrict__ tie,
-                                                                          uint64_t* __restrict__ kout, double* __restrict__ vout) {
+                                                                          const V* __restrict__ oval, const uint32_t* __restrict__ tie,
+                                                                          uint64_t* __restrict__ kout, V* __restrict__ vout) {
   __shared__ uint64_t key[SORT_TILE];
-  __shared__ double val[SORT_TILE];
+  __shared__ V val[SORT_TILE];
   const int64_t t0 = (int64_t)blockIdx.x * SORT_TILE;
   const int mt = (int)(m - t0 < SORT_TILE ? m - t0 : SORT_TILE);
   for (int x = threadIdx.x; x < mt; x += CB_THREADS) {
@@ -282,9 +295,10 @@ __global__ __launch_bounds__(CB_THREADS) void csr_build_sort_tiles_kernel(int64_
 }
 
 // one merge pass over sorted runs of w elements: element x of a run lands at its offset plus the count of smaller keys in the partner run
+template <class V>
 __global__ __launch_bounds__(CB_THREADS) void csr_build_merge_kernel(int64_t m, int64_t w, const uint64_t* __restrict__ kin,
-                                                                     const double* __restrict__ vin, uint64_t* __restrict__ kout,
-                                                                     double* __restrict__ vout) {
+                                                                     const V* __restrict__ vin, uint64_t* __restrict__ kout,
+                                                                     V* __restrict__ vout) {
   const int64_t x = (int64_t)blockIdx.x * CB_THREADS + threadIdx.x;
   if (x >= m) return;
   const int64_t base = x / (2 * w) * (2 * w);
@@ -303,9 +317,10 @@ __global__ __launch_bounds__(CB_THREADS) void csr_build_merge_kernel(int64_t m, 
   vout[dst] = vin[x];
 }
 
+template <class V>
 __global__ __launch_bounds__(CB_THREADS) void csr_build_unpack_kernel(int64_t a, int64_t m, const uint64_t* __restrict__ kin,
-                                                                      const double* __restrict__ vin, int32_t* __restrict__ ocol,
-                                                                      double* __restrict__ oval) {
+                                                                      const V* __restrict__ vin, int32_t* __restrict__ ocol,
+                                                                      V* __restrict__ oval) {
   const int64_t x = (int64_t)blockIdx.x * CB_THREADS + threadIdx.x;
   if (x >= m) return;
   ocol[a + x] = (int32_t)(kin[x] >> 32);
@@ -336,17 +351,6 @@ unsigned cb_grid(int64_t items, int64_t per_block) { return (unsigned)std::max<i
 unsigned cb_grid_stride(int64_t items) { return (unsigned)std::min<int64_t>(8192, cb_grid(items, CB_THREADS)); }
 }  // namespace
 
-// dispatch over the index widths of the caller's arrays (row_ptr, col_idx: 32 or 64 bits): f(RP{}, CI{})
-template <class F> void cb_dispatch(int rp64, int ci64, F&& f) {
-  if (rp64) {
-    if (ci64) f(int64_t{}, int64_t{});
-    else f(int64_t{}, int32_t{});
-  } else {
-    if (ci64) f(int32_t{}, int64_t{});
-    else f(int32_t{}, int32_t{});
-  }
-}
-
 void launch_csr_build_rows(hipStream_t st, const void* rp, int rp64, int64_t n, unsigned long long* info) {
   cb_dispatch(rp64, 0, [&](auto r_, auto) { using RP = decltype(r_); hipLaunchKernelGGL(csr_build_rows_kernel<RP>, dim3(cb_grid_stride(n)), dim3(CB_THREADS), 0, st, (const RP*)rp, n, info); });
 }
@@ -376,12 +380,25 @@ void launch_csr_build_offsets(hipStream_t st, const void* rp, int rp64, int64_t 
 
 int64_t csr_build_scan_tiles(int64_t m) { return std::max<int64_t>(1, (m + SCAN_TILE - 1) / SCAN_TILE); }
 
+template <class V>
+static void cb_scatter(hipStream_t st, const void* rp, int rp64, const void* col, int ci64, const double* vals, int64_t n, int64_t p_lo,
+                       int64_t p_hi, int base, int lower, int64_t r0, int64_t nloc, const int64_t* lrp, int32_t* fill, int32_t* ocol, V* oval,
+                       uint32_t* tie) {
+  if (p_hi <= p_lo) return;
+  cb_dispatch(rp64, ci64, [&](auto r_, auto c_) { using RP = decltype(r_); using CI = decltype(c_); hipLaunchKernelGGL((csr_build_scatter_kernel<RP, CI, V>), dim3(cb_grid(p_hi - p_lo, CB_THREADS * CB_EPT)), dim3(CB_THREADS), 0, st,
+                             (const RP*)rp, (const CI*)col, vals, n, p_lo, p_hi, base, lower, r0, nloc, lrp, fill, ocol, oval, tie); });
+}
+
 void launch_csr_build_scatter(hipStream_t st, const void* rp, int rp64, const void* col, int ci64, const double* vals, int64_t n, int64_t p_lo,
                               int64_t p_hi, int base, int lower, int64_t r0, int64_t nloc, const int64_t* lrp, int32_t* fill, int32_t* ocol,
                               double* oval, uint32_t* tie) {
-  if (p_hi <= p_lo) return;
-  cb_dispatch(rp64, ci64, [&](auto r_, auto c_) { using RP = decltype(r_); using CI = decltype(c_); hipLaunchKernelGGL((csr_build_scatter_kernel<RP, CI>), dim3(cb_grid(p_hi - p_lo, CB_THREADS * CB_EPT)), dim3(CB_THREADS), 0, st,
-                             (const RP*)rp, (const CI*)col, vals, n, p_lo, p_hi, base, lower, r0, nloc, lrp, fill, ocol, oval, tie); });
+  cb_scatter(st, rp, rp64, col, ci64, vals, n, p_lo, p_hi, base, lower, r0, nloc, lrp, fill, ocol, oval, tie);
+}
+
+void launch_csr_build_scatter(hipStream_t st, const void* rp, int rp64, const void* col, int ci64, int64_t n, int64_t p_lo, int64_t p_hi,
+                              int base, int lower, int64_t r0, int64_t nloc, const int64_t* lrp, int32_t* fill, int32_t* ocol, uint64_t* osrc,
+                              uint32_t* tie) {
+  cb_scatter(st, rp, rp64, col, ci64, (const double*)nullptr, n, p_lo, p_hi, base, lower, r0, nloc, lrp, fill, ocol, osrc, tie);
 }
 
 void launch_csr_build_flag(hipStream_t st, const int64_t* lrp, int64_t nloc, int64_t lnnz, const int32_t* ocol, const uint32_t* tie,
@@ -390,24 +407,33 @@ void launch_csr_build_flag(hipStream_t st, const int64_t* lrp, int64_t nloc, int
   hipLaunchKernelGGL(csr_build_flag_kernel, dim3(cb_grid(lnnz, CB_THREADS * CB_EPT)), dim3(CB_THREADS), 0, st, lrp, nloc, lnnz, ocol, tie, flag);
 }
 
-void launch_csr_build_sort_rows(hipStream_t st, const int64_t* lrp, int64_t nloc, const uint8_t* flag, int32_t* ocol, double* oval,
+template <class V>
+void launch_csr_build_sort_rows(hipStream_t st, const int64_t* lrp, int64_t nloc, const uint8_t* flag, int32_t* ocol, V* oval,
                                 const uint32_t* tie) {
   if (nloc <= 0) return;
-  hipLaunchKernelGGL(csr_build_sort_rows_kernel, dim3((unsigned)std::min<int64_t>(nloc, 16384)), dim3(CB_THREADS), 0, st, lrp, nloc, flag,
+  hipLaunchKernelGGL(csr_build_sort_rows_kernel<V>, dim3((unsigned)std::min<int64_t>(nloc, 16384)), dim3(CB_THREADS), 0, st, lrp, nloc, flag,
                      ocol, oval, tie);
 }
 
-void launch_csr_build_sort_long(hipStream_t st, int64_t a, int64_t m, int32_t* ocol, double* oval, const uint32_t* tie, uint64_t* k0,
-                                double* v0, uint64_t* k1, double* v1) {
+template <class V>
+void launch_csr_build_sort_long(hipStream_t st, int64_t a, int64_t m, int32_t* ocol, V* oval, const uint32_t* tie, uint64_t* k0, V* v0,
+                                uint64_t* k1, V* v1) {
   if (m <= 0) return;
-  hipLaunchKernelGGL(csr_build_sort_tiles_kernel, dim3(cb_grid(m, SORT_TILE)), dim3(CB_THREADS), 0, st, a, m, ocol, oval, tie, k0, v0);
+  hipLaunchKernelGGL(csr_build_sort_tiles_kernel<V>, dim3(cb_grid(m, SORT_TILE)), dim3(CB_THREADS), 0, st, a, m, ocol, oval, tie, k0, v0);
   for (int64_t w = SORT_TILE; w < m; w *= 2) {
-    hipLaunchKernelGGL(csr_build_merge_kernel, dim3(cb_grid(m, CB_THREADS)), dim3(CB_THREADS), 0, st, m, w, k0, v0, k1, v1);
+    hipLaunchKernelGGL(csr_build_merge_kernel<V>, dim3(cb_grid(m, CB_THREADS)), dim3(CB_THREADS), 0, st, m, w, k0, v0, k1, v1);
     std::swap(k0, k1);
     std::swap(v0, v1);
   }
-  hipLaunchKernelGGL(csr_build_unpack_kernel, dim3(cb_grid(m, CB_THREADS)), dim3(CB_THREADS), 0, st, a, m, k0, v0, ocol, oval);
+  hipLaunchKernelGGL(csr_build_unpack_kernel<V>, dim3(cb_grid(m, CB_THREADS)), dim3(CB_THREADS), 0, st, a, m, k0, v0, ocol, oval);
 }
+
+template void launch_csr_build_sort_rows<double>(hipStream_t, const int64_t*, int64_t, const uint8_t*, int32_t*, double*, const uint32_t*);
+template void launch_csr_build_sort_rows<uint64_t>(hipStream_t, const int64_t*, int64_t, const uint8_t*, int32_t*, uint64_t*, const uint32_t*);
+template void launch_csr_build_sort_long<double>(hipStream_t, int64_t, int64_t, int32_t*, double*, const uint32_t*, uint64_t*, double*, uint64_t*,
+                                                 double*);
+template void launch_csr_build_sort_long<uint64_t>(hipStream_t, int64_t, int64_t, int32_t*, uint64_t*, const uint32_t*, uint64_t*, uint64_t*,
+                                                   uint64_t*, uint64_t*);
 
 int64_t csr_build_sort_tile() { return SORT_TILE; }
 

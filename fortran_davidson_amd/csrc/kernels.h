@@ -193,6 +193,17 @@ void launch_spmm_csr_finish(hipStream_t st, const CsrLong* longs, int nlong, con
 // ---- K1c': device build of a CSR operator (k_csr_build.hip; dav_set_operator_csr_dev) -----------------------------------------------
 // The caller's global arrays: row_ptr and col_idx of 32 (rp64 / ci64 = 0) or 64 bits, numbered from `base`.  info[4] (set to ~0 first):
 // [0] first row where row_ptr decreases, [1] row_ptr[0], [2] row_ptr[n], [3] first row of 2^32 or more entries.
+// dispatch over the index widths of the caller's arrays (row_ptr, col_idx: 32 or 64 bits): f(RP{}, CI{})
+template <class F> void cb_dispatch(int rp64, int ci64, F&& f) {
+  if (rp64) {
+    if (ci64) f(int64_t{}, int64_t{});
+    else f(int64_t{}, int32_t{});
+  } else {
+    if (ci64) f(int32_t{}, int64_t{});
+    else f(int32_t{}, int32_t{});
+  }
+}
+
 void launch_csr_build_rows(hipStream_t st, const void* rp, int rp64, int64_t n, unsigned long long* info);
 // entries [0, nnz): first_bad = the first entry with a column out of range or (lower) above the diagonal; dcount / dfirst (zero / ~0
 // first) = diagonal entries of every row and the first of them; mcount (zero first, lower) = mirrored entries of every local row
@@ -210,19 +221,35 @@ int64_t csr_build_scan_tiles(int64_t m);
 void launch_csr_build_scatter(hipStream_t st, const void* rp, int rp64, const void* col, int ci64, const double* vals, int64_t n, int64_t p_lo,
                               int64_t p_hi, int base, int lower, int64_t r0, int64_t nloc, const int64_t* lrp, int32_t* fill, int32_t* ocol,
                               double* oval, uint32_t* tie);
+// the same over the block rows of a BSR matrix: what travels with a block column is the block's source, osrc = input block p << 1 | mirrored
+void launch_csr_build_scatter(hipStream_t st, const void* rp, int rp64, const void* col, int ci64, int64_t n, int64_t p_lo, int64_t p_hi,
+                              int base, int lower, int64_t r0, int64_t nloc, const int64_t* lrp, int32_t* fill, int32_t* ocol, uint64_t* osrc,
+                              uint32_t* tie);
 // flag[i] = 1 (zero first) where canonical row i is not in key order (column, tie)
 void launch_csr_build_flag(hipStream_t st, const int64_t* lrp, int64_t nloc, int64_t lnnz, const int32_t* ocol, const uint32_t* tie,
                            uint8_t* flag);
-// flagged rows of at most csr_build_sort_tile() entries sorted in place by key
-void launch_csr_build_sort_rows(hipStream_t st, const int64_t* lrp, int64_t nloc, const uint8_t* flag, int32_t* ocol, double* oval,
+// flagged rows of at most csr_build_sort_tile() entries sorted in place by key (V: double values, or uint64_t block sources)
+template <class V>
+void launch_csr_build_sort_rows(hipStream_t st, const int64_t* lrp, int64_t nloc, const uint8_t* flag, int32_t* ocol, V* oval,
                                 const uint32_t* tie);
 int64_t csr_build_sort_tile();
 // one longer row [a, a + m) sorted in place by key; k0 / v0 / k1 / v1: scratch of m keys and values each
-void launch_csr_build_sort_long(hipStream_t st, int64_t a, int64_t m, int32_t* ocol, double* oval, const uint32_t* tie, uint64_t* k0,
-                                double* v0, uint64_t* k1, double* v1);
+template <class V>
+void launch_csr_build_sort_long(hipStream_t st, int64_t a, int64_t m, int32_t* ocol, V* oval, const uint32_t* tie, uint64_t* k0, V* v0,
+                                uint64_t* k1, V* v1);
 // diag[0..n) = the diagonal of the whole matrix (a row's diagonal entries summed in input order from +0.0)
 void launch_csr_build_diag(hipStream_t st, const void* rp, int rp64, const void* col, int ci64, const double* vals, int64_t n, int base,
                            const uint32_t* dcount, const unsigned long long* dfirst, double* diag);
+
+// ---- K1d': device build of a BSR operator (k_bsr_build.hip; dav_set_operator_bsr_dev) -----------------------------------------------
+// The index level is the CSR build above over the n / b block rows with the block source as payload.  Then the values move once:
+// val[q b^2 + k b + m] = entry (tr ? k : m, tr ? m : k) of input block p, for canonical block q with src[q] = p << 1 | tr; rowmaj: the
+// caller's blocks are row-major.  vals holds the caller's nnzb blocks, every p < nnzb.
+void launch_bsr_build_gather(hipStream_t st, int bs, const uint64_t* src, int64_t lnnzb, const double* vals, int rowmaj, double* val);
+// diag[0..n) = the diagonal of the whole matrix: per block row the diagonal entries of its diagonal blocks, summed in input order from
+// +0.0 (dcount / dfirst of the check pass over the block rows; entry (m, m) sits at m b + m in either layout)
+void launch_bsr_build_diag(hipStream_t st, int bs, const void* rp, int rp64, const void* col, int ci64, const double* vals, int64_t nb,
+                           int base, const uint32_t* dcount, const unsigned long long* dfirst, double* diag);
 
 // ---- K1d: BSR block product on the matrix cores (k_bsrmm.hip) ------------------------------------------------------------------------
 // Y[rows of this rank, 0:kk] = A_bsr * X, uniform block size 1 <= b <= 16, blocks column-major on the device.  Work list built on the

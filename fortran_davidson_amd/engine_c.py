@@ -200,6 +200,57 @@ def check_bsr(indptr, indices, data, n, base=0, lower=False, layout=BSR_ROW_MAJO
     return b, rp, ci, vv
 
 
+def is_torch_bsr(t):
+    """True for a torch tensor in the sparse BSR layout (torch itself is imported only when the object comes from it)"""
+    if not type(t).__module__.startswith("torch"):
+        return False
+    import torch
+    return isinstance(t, torch.Tensor) and t.layout == torch.sparse_bsr
+
+
+def torch_bsr_parts(t):
+    """(crow_indices, col_indices, values (nnzb, b, b), row-major blocks) of a torch sparse BSR tensor; on the CPU as numpy arrays"""
+    if t.dim() != 2 or t.shape[0] != t.shape[1]:
+        raise ValueError(f"BSR input: a square matrix is needed, the tensor has shape {tuple(t.shape)}")
+    parts = (t.crow_indices(), t.col_indices(), t.values())
+    if t.device.type == "cpu":
+        return tuple(x.numpy() for x in parts)
+    return parts
+
+
+def device_bsr_tensors(row_ptr, col_idx, vals, n, device):
+    """The checks of a BSR matrix in device tensors before any library call: int32 / int64 indices and float64 values (TypeError, never
+    converted); contiguous tensors on cuda:`device`, vals of shape (nnzb, b, b) with 1 <= b <= 16 dividing n, n / b + 1 offsets and
+    enough block columns and blocks (ValueError).  Returns (b, row_ptr_bits, col_bits)."""
+    import torch
+    args = (("row_ptr", row_ptr, (torch.int32, torch.int64), 1), ("col_idx", col_idx, (torch.int32, torch.int64), 1),
+            ("vals", vals, (torch.float64,), 3))
+    for name, t, kinds, _ in args:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"device BSR input: {name} must be a torch tensor, not {type(t).__name__}")
+        if t.dtype not in kinds:
+            raise TypeError(f"device BSR input: {name} has dtype {t.dtype}, expected " + " or ".join(str(k) for k in kinds))
+    for name, t, _, dims in args:
+        if t.layout != torch.strided or not t.is_contiguous() or t.dim() != dims:
+            raise ValueError(f"device BSR input: {name} must be a contiguous tensor of {dims} dimension{'s' if dims > 1 else ''}")
+    for name, t, _, _ in args:
+        if t.device.type != "cuda" or t.device.index != device:
+            raise ValueError(f"device BSR input: {name} lies on {t.device}, the engine on cuda:{device}")
+    if vals.shape[1] != vals.shape[2]:
+        raise ValueError(f"device BSR input: vals must have shape (nnzb, b, b), it has {tuple(vals.shape)}")
+    b = int(vals.shape[1])
+    if b < 1 or b > 16:
+        raise ValueError(f"device BSR input: block size {b} must lie in 1..16")
+    if n % b:
+        raise ValueError(f"device BSR input: n = {n} is not a multiple of the block size {b}")
+    if row_ptr.numel() != n // b + 1:
+        raise ValueError(f"device BSR input: row_ptr must hold n / b + 1 = {n // b + 1} offsets, it holds {row_ptr.numel()}")
+    nnzb = int(row_ptr[-1]) - int(row_ptr[0])         # two values read back: the kernels must not read past the tensors
+    if col_idx.numel() < nnzb or vals.shape[0] < nnzb:
+        raise ValueError(f"device BSR input: row_ptr says {nnzb} blocks, col_idx / vals hold {col_idx.numel()} / {vals.shape[0]}")
+    return b, (64 if row_ptr.dtype == torch.int64 else 32), (64 if col_idx.dtype == torch.int64 else 32)
+
+
 def _f(a):
     return np.asfortranarray(a, dtype=np.float64)
 
@@ -385,13 +436,31 @@ class CEngine:
         """dav_set_operator_bsr: a symmetric matrix in BSR form with square blocks (the global arrays; indptr / indices count block
         rows / columns from `base`), every nonzero block (lower=False) or only the blocks with block column <= block row (lower=True).
         Three numpy arrays - data of shape (nnzb, b, b), row-major blocks unless layout=BSR_COL_MAJOR - or one object with .indptr,
-        .indices, .data and .blocksize (a scipy bsr_matrix).  The engine validates the input (DavidsonHipError) and leaves the operator
-        unset when it refuses it."""
+        .indices, .data and .blocksize (a scipy bsr_matrix), or a torch.sparse_bsr_tensor (row-major blocks; one on the GPU goes to
+        set_operator_bsr_dev).  The engine validates the input (DavidsonHipError) and leaves the operator unset when it refuses it."""
+        if is_torch_bsr(indptr):
+            parts = torch_bsr_parts(indptr)
+            if indptr.device.type != "cpu":
+                return self.set_operator_bsr_dev(which, *parts, base=base, lower=lower, layout=BSR_ROW_MAJOR)
+            (indptr, indices, data), layout = parts, BSR_ROW_MAJOR
         b, rp, ci, vv = bsr_arrays(indptr, indices, data, self.n, layout)
         ci_p = ci.ctypes.data_as(C.POINTER(C.c_int32)) if ci.size else (C.c_int32 * 1)()
         vv_p = _dp(vv) if vv.size else (C.c_double * 1)()
         self._chk(self.lib.dav_set_operator_bsr(self.h, C.c_int(which), C.c_int(b), rp.ctypes.data_as(C.POINTER(C.c_int64)), ci_p, vv_p,
                                                 C.c_int(base), C.c_int(CSR_LOWER if lower else CSR_FULL), C.c_int(layout)))
+
+    def set_operator_bsr_dev(self, which, row_ptr, col_idx, vals, base=0, lower=False, layout=BSR_ROW_MAJOR):
+        """dav_set_operator_bsr_dev: the matrix of set_operator_bsr as torch tensors on the engine's device, built on the GPU - row_ptr
+        (n / b + 1) and col_idx int32 or int64, vals float64 of shape (nnzb, b, b), all contiguous.  Other dtypes are a TypeError (never
+        converted).  Torch's current stream on the device is synchronised first, so work queued on it that writes the arrays is
+        complete.  The engine's refusal is a DavidsonHipError; the operator is then unset."""
+        b, rpb, cib = device_bsr_tensors(row_ptr, col_idx, vals, self.n, self.device)
+        import torch
+        torch.cuda.current_stream(row_ptr.device).synchronize()
+        self._chk(self.lib.dav_set_operator_bsr_dev(self.h, C.c_int(which), C.c_int(b), C.c_void_p(row_ptr.data_ptr()), C.c_int(rpb),
+                                                    C.c_void_p(col_idx.data_ptr() or None), C.c_int(cib),
+                                                    C.c_void_p(vals.data_ptr() or None), C.c_int(base),
+                                                    C.c_int(CSR_LOWER if lower else CSR_FULL), C.c_int(layout)))
 
     def get_diagonal(self, which):
         d = np.zeros(self.n)

@@ -7,7 +7,7 @@ module davidson_c_api
   use davidson, only: generalized_eigensolver
   use davidson_device
   use davidson_free, only: free_matmul
-  use davidson_sparse, only: csr_matrix, bsr_matrix, engine_set_sparse, engine_set_sparse_device
+  use davidson_sparse, only: csr_matrix, bsr_matrix, engine_set_sparse, engine_set_sparse_device, engine_set_block_sparse_device
   use lapack_wrapper
   use array_utils
   implicit none
@@ -319,6 +319,22 @@ contains
     call c_f_pointer(p, eng)
     call engine_set_sparse(eng, int(which), bsr_from_c(n, b, rp, col, vals, base, lower))
   end subroutine fd_engine_set_block_sparse
+
+  !> engine_set_block_sparse_device(eng, which, n, b, ...) with device arrays: returns the engine's status (0 = set; otherwise
+  !> dav_last_error says why and the operator is unset) instead of stopping the process
+  function fd_engine_set_block_sparse_device(p, which, n, b, rp, rp_bits, col, col_bits, vals, base, lower, row_major) result(stat) &
+       bind(C, name="fd_engine_set_block_sparse_device")
+    type(c_ptr), value :: p
+    integer(c_int), value :: which, n, b, rp_bits, col_bits, base, lower, row_major
+    type(c_ptr), value :: rp, col, vals
+    integer(c_int) :: stat
+    type(davidson_engine), pointer :: eng
+    integer :: st
+    call c_f_pointer(p, eng)
+    call engine_set_block_sparse_device(eng, int(which), int(n), int(b), rp, col, vals, base=int(base), lower=lower /= 0, &
+         row_major=row_major /= 0, row_ptr_bits=int(rp_bits), col_bits=int(col_bits), stat=st)
+    stat = int(st, c_int)
+  end function fd_engine_set_block_sparse_device
 
   !> kind 0: dense generated in HBM, 1: hashed matrix-free operator, 2: harness operator, 3: identity
   subroutine fd_engine_set_operator(p, which, kind, seed, sparsity, use_diag_val, diag_val) &

@@ -185,6 +185,20 @@ module davidson_hip_c
        integer(c_int), value :: index_base, triangle
        integer(c_int) :: ierr
      end function
+     !> a BSR matrix from device arrays of the engine's device, built on the GPU (row_ptr_bits / col_bits: 32 or 64)
+     function dav_set_operator_bsr_dev(h, which, block_size, block_row_ptr, row_ptr_bits, block_col_idx, col_bits, vals, index_base, &
+          triangle, block_layout) bind(C, name="dav_set_operator_bsr_dev") result(ierr)
+       import :: c_ptr, c_int
+       type(c_ptr), value :: h
+       integer(c_int), value :: which, block_size
+       type(c_ptr), value :: block_row_ptr
+       integer(c_int), value :: row_ptr_bits
+       type(c_ptr), value :: block_col_idx
+       integer(c_int), value :: col_bits
+       type(c_ptr), value :: vals
+       integer(c_int), value :: index_base, triangle, block_layout
+       integer(c_int) :: ierr
+     end function
      !> a symmetric matrix in CSR form, global host arrays (ABI 109); index_base 1 = Fortran numbering of rows and columns
      function dav_set_operator_csr(h, which, row_ptr, col_idx, vals, index_base, triangle) bind(C, name="dav_set_operator_csr") &
           result(ierr)

@@ -1,6 +1,6 @@
 !> Sparse operators: a symmetric real matrix in CSR (compressed sparse row) or BSR (block sparse row) form, 1-based as Fortran numbers
 !> rows and columns, and engine_set_sparse, which hands either to a device-resident problem (dav_set_operator_csr / dav_set_operator_bsr,
-!> include/davidson_hip.h).  The solves of a csr_matrix / bsr_matrix are the specifics generalized_eigensolver_sparse /
+!> include/davidson_hip.h); engine_set_sparse_device / engine_set_block_sparse_device take the same matrices from device arrays.  The solves of a csr_matrix / bsr_matrix are the specifics generalized_eigensolver_sparse /
 !> generalized_eigensolver_bsr of the generic generalized_eigensolver (module davidson).
 module davidson_sparse
   use, intrinsic :: iso_c_binding
@@ -9,7 +9,7 @@ module davidson_sparse
   use davidson_engine_setup, only: davidson_engine
   implicit none
   private
-  public :: csr_matrix, bsr_matrix, engine_set_sparse, engine_set_sparse_device
+  public :: csr_matrix, bsr_matrix, engine_set_sparse, engine_set_sparse_device, engine_set_block_sparse_device
 
   !> A symmetric real matrix of order n in CSR form, 1-based: the entries of row i are col_idx / values(row_ptr(i) : row_ptr(i+1) - 1).
   !> lower = .true.: only the entries with column <= row are given (the engine mirrors the strict lower part); .false.: every nonzero
@@ -198,5 +198,52 @@ contains
     end if
     if (which == 1) eng%free_semantics = .false.
   end subroutine engine_set_sparse_bsr
+
+  !> Operator A (which = 1) or B (which = 2) of the engine from a BSR matrix of order n with square blocks of size block_size whose
+  !> arrays are DEVICE memory of the engine's device: dav_set_operator_bsr_dev builds the operator on the GPU, bit for bit as
+  !> engine_set_sparse builds it from a bsr_matrix holding the same arrays.  base: 1 (default, Fortran numbering of block rows and
+  !> columns) or 0; lower: only the blocks with block column <= block row are given; row_major: the b * b values of a block are in C
+  !> order (default .false.: a Fortran values(b, b, nnzb)); row_ptr_bits / col_bits: 64 (default for row_ptr) or 32 (default for
+  !> col_idx).  The arrays must be complete when the call is made and are free again when it returns.  stat present: a refused matrix
+  !> returns its non-zero status here (dav_last_error says why; the operator is left unset), otherwise the program stops.
+  subroutine engine_set_block_sparse_device(eng, which, n, block_size, row_ptr, col_idx, vals, base, lower, row_major, row_ptr_bits, &
+       col_bits, stat)
+    type(davidson_engine), intent(inout) :: eng
+    integer, intent(in) :: which, n, block_size
+    type(c_ptr), intent(in) :: row_ptr, col_idx, vals
+    integer, intent(in), optional :: base, row_ptr_bits, col_bits
+    logical, intent(in), optional :: lower, row_major
+    integer, intent(out), optional :: stat
+    integer(c_int) :: ib, rb, cb, tri, lay, ierr
+    if (n /= eng%n) then
+       if (present(stat)) then
+          stat = -1
+          return
+       end if
+       print *, "engine_set_block_sparse_device: the matrix must be of order ", eng%n
+       error stop
+    end if
+    ib = 1_c_int
+    rb = 64_c_int
+    cb = 32_c_int
+    tri = DAV_CSR_FULL
+    lay = DAV_BSR_COL_MAJOR
+    if (present(base)) ib = int(base, c_int)
+    if (present(row_ptr_bits)) rb = int(row_ptr_bits, c_int)
+    if (present(col_bits)) cb = int(col_bits, c_int)
+    if (present(lower)) then
+       if (lower) tri = DAV_CSR_LOWER
+    end if
+    if (present(row_major)) then
+       if (row_major) lay = DAV_BSR_ROW_MAJOR
+    end if
+    ierr = dav_set_operator_bsr_dev(eng%h, int(which - 1, c_int), int(block_size, c_int), row_ptr, rb, col_idx, cb, vals, ib, tri, lay)
+    if (present(stat)) then
+       stat = int(ierr)
+    else
+       call check_dav(ierr, "dav_set_operator_bsr_dev")
+    end if
+    if (ierr == 0 .and. which == 1) eng%free_semantics = .false.
+  end subroutine engine_set_block_sparse_device
 
 end module davidson_sparse

@@ -16,7 +16,8 @@ import ctypes as C
 import numpy as np
 
 from ._lib import fortran_lib, hip_lib
-from .engine_c import CEngine, DavidsonHipError, check_bsr, check_csr, device_csr_tensors, is_torch_csr, torch_csr_parts
+from .engine_c import (CEngine, DavidsonHipError, check_bsr, check_csr, device_bsr_tensors, device_csr_tensors, is_torch_bsr, is_torch_csr,
+                       torch_bsr_parts, torch_csr_parts)
 
 _METHOD = {"DPR": 0, "GJD": 1}
 _CB = C.CFUNCTYPE(None, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
@@ -111,6 +112,8 @@ def _bsr_input(a, n, lower=False):
     """(b, indptr, indices, values) of a BSR operator given as a tuple (indptr, indices, data (nnzb, b, b) row-major blocks) or an object
     with .blocksize (a scipy bsr_matrix), 0-based, validated here (ValueError) - the Fortran door stops the process on an engine error.
     The values come back in Fortran order (values(m, k, p) = A_p[m, k]: each block transposed in memory) for the Fortran doors."""
+    if is_torch_bsr(a):
+        a = torch_bsr_parts(a)
     if hasattr(a, "blocksize"):
         a = (a.indptr, a.indices, a.data)
     indptr, indices, data = a
@@ -122,14 +125,32 @@ def _bsr_input(a, n, lower=False):
     return b, rp, ci, vf if vf.size else np.zeros(1)
 
 
+def _is_device_bsr(a):
+    return is_torch_bsr(a) and a.device.type != "cpu"
+
+
 def generalized_eigensolver_bsr(indptr, indices, data, lowest, method, max_iterations, tolerance, max_dim_sub=None, second=None,
                                 lower=False, n=None):
     """`call generalized_eigensolver(a_bsr, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters [, max_dim_sub]
     [, b_bsr])` (the bsr_matrix specific of module davidson) with A in BSR form, 0-based: three arrays - data (nnzb, b, b), row-major
     blocks - or `indptr` an object with .indptr / .indices / .data / .blocksize (a scipy bsr_matrix) and indices = data = None.
-    `second`: B the same way, with the same block size.  lower=True: only the blocks with block column <= block row are given, for A and
-    B.  n: the order (default: block rows x b).  Returns (eigenvalues, eigenvectors, iters)."""
+    `second`: B the same way, with the same block size.  Either may also be a torch.sparse_bsr_tensor; one on the GPU is built there
+    (DavidsonEngine.set_block_sparse on the tensor's device).  lower=True: only the blocks with block column <= block row are given,
+    for A and B.  n: the order (default: block rows x b).  Returns (eigenvalues, eigenvectors, iters)."""
     a = indptr if indices is None and data is None else (indptr, indices, data)
+    if _is_device_bsr(a) or _is_device_bsr(second):
+        # a matrix in device memory: an engine of its own, built on the GPU (DavidsonEngine.set_block_sparse)
+        if n is None:
+            if hasattr(a, "shape"):
+                n = a.shape[0]
+            else:
+                n = (len(a[0]) - 1) * (np.asarray(a[2]).shape[1] if np.asarray(a[2]).ndim == 3 else 1)
+        device = (a if _is_device_bsr(a) else second).device.index
+        with DavidsonEngine(n, lowest, max_dim_sub, gev=second is not None, device=device) as eng:
+            eng.set_block_sparse(1, a, lower=lower)
+            if second is not None:
+                eng.set_block_sparse(2, second, lower=lower)
+            return eng.solve(method, max_iterations, tolerance)
     b, rp, ci, vv = _bsr_input(a, n, lower)
     n = (rp.size - 1) * b
     if second is not None:
@@ -233,12 +254,26 @@ class DavidsonEngine:
 
     def set_block_sparse(self, which, indptr, indices=None, data=None, lower=False):
         """Operator A (which=1) or B (which=2) as a symmetric matrix in BSR form, 0-based (Fortran: engine_set_sparse with a bsr_matrix):
-        three arrays - data (nnzb, b, b), row-major blocks - or `indptr` an object with .blocksize (a scipy bsr_matrix).  lower=True:
-        only the blocks with block column <= block row are given."""
+        three arrays - data (nnzb, b, b), row-major blocks - or `indptr` an object with .blocksize (a scipy bsr_matrix), or a
+        torch.sparse_bsr_tensor - one on the engine's GPU is built there (Fortran: engine_set_block_sparse_device; a refused matrix
+        raises DavidsonHipError and leaves the operator unset).  lower=True: only the blocks with block column <= block row are given."""
         a = indptr if indices is None and data is None else (indptr, indices, data)
+        if _is_device_bsr(a):
+            return self._set_block_sparse_device(which, *torch_bsr_parts(a), lower=lower)
         b, rp, ci, vv = _bsr_input(a, self.n, lower)
         self.lib.fd_engine_set_block_sparse(self.p, C.c_int(which), C.c_int(self.n), C.c_int(b), _i64(rp), _i32(ci), _dp(vv), C.c_int(0),
                                             C.c_int(1 if lower else 0))
+
+    def _set_block_sparse_device(self, which, row_ptr, col_idx, vals, lower=False):
+        b, rpb, cib = device_bsr_tensors(row_ptr, col_idx, vals, self.n, self.device)
+        import torch
+        torch.cuda.current_stream(row_ptr.device).synchronize()
+        st = self.lib.fd_engine_set_block_sparse_device(self.p, C.c_int(which), C.c_int(self.n), C.c_int(b), C.c_void_p(row_ptr.data_ptr()),
+                                                        C.c_int(rpb), C.c_void_p(col_idx.data_ptr() or None), C.c_int(cib),
+                                                        C.c_void_p(vals.data_ptr() or None), C.c_int(0), C.c_int(1 if lower else 0),
+                                                        C.c_int(1))
+        if st != 0:
+            raise DavidsonHipError(hip_lib().dav_last_error().decode())
 
     def set_correction_policy(self, policy):
         """"all" = the reference's policy (default); "unconverged" = opt-in: correct only the wanted pairs

@@ -252,6 +252,27 @@ int dav_set_operator_csr_dev(dav_handle_t h, int which, const void* row_ptr, int
 enum { DAV_BSR_ROW_MAJOR = 0, DAV_BSR_COL_MAJOR = 1 };
 int dav_set_operator_bsr(dav_handle_t h, int which, int block_size, const int64_t* block_row_ptr /* n/b + 1 */, const int32_t* block_col_idx,
                          const double* vals /* nnzb * b * b */, int index_base /* 0 or 1 */, int triangle, int block_layout);
+/* The same matrix from DEVICE arrays, built on the GPU by the engine's own kernels.  Purely additive within ABI 109.  The arguments mean
+ * what they mean for dav_set_operator_bsr - the GLOBAL matrix on every rank, index_base for both index arrays, DAV_CSR_FULL /
+ * DAV_CSR_LOWER, DAV_BSR_ROW_MAJOR / DAV_BSR_COL_MAJOR - except that block_row_ptr, block_col_idx and vals are pointers to device memory
+ * of the engine's device, and that the two index arrays may each hold 32- or 64-bit signed integers (row_ptr_bits, col_bits: 32 or 64; a
+ * torch BSR tensor has int64 for both and row-major blocks, rocSPARSE bsr* arrays int32).  The arrays must be COMPLETE when the call is
+ * made: a caller that writes them on a stream of its own synchronises that stream first.  The scalar rules of dav_set_operator_bsr are
+ * checked first, in its order and words (plus row_ptr_bits / col_bits); then the pointers, before anything is launched
+ * (hipPointerGetAttributes, hipMemGetAddressRange: a null pointer where one is needed, pageable / pinned / managed memory, another device,
+ * an allocation shorter than n/b + 1 offsets, nnzb block columns or 8 nnzb b^2 bytes of values - the message names the argument); then
+ * the array rules on the device, with the messages of dav_set_operator_bsr and the FIRST offending block row or block named; a block row
+ * of 2^32 blocks or more is refused as well.  No block column is used as an address before that check has passed.  A refused call leaves
+ * the operator UNSET and the engine usable.  The storage built - block row offsets, block columns, the column-major values (a mirrored
+ * block the transpose of its source), the diagonal, the work list - is bit for bit what dav_set_operator_bsr builds from the same arrays
+ * in host memory: values are moved, never computed with, so applies and solves agree bitwise on any number of ranks.  A rank keeps the
+ * block rows that TOUCH its slab (a block row straddling two slabs is kept whole by both ranks); a rank without rows keeps nothing.  The
+ * call returns after the engine has stopped reading the caller's arrays: they may be freed or overwritten at once.  Scratch comes from
+ * the engine's allocator (about 20 bytes per block row of the matrix plus 8 - with DAV_CSR_LOWER 12 - bytes per block of this rank) and
+ * is released before the call returns. */
+int dav_set_operator_bsr_dev(dav_handle_t h, int which, int block_size, const void* block_row_ptr, int row_ptr_bits /* 32 | 64 */,
+                             const void* block_col_idx, int col_bits /* 32 | 64 */, const double* vals, int index_base /* 0 or 1 */,
+                             int triangle, int block_layout);
 int dav_get_diagonal(dav_handle_t h, int which, double* diag_out /* n, global */);
 
 /* ---- the per-iteration hot path ---------------------------------------------------------------- */
