@@ -1,8 +1,9 @@
 // Engine core + C ABI (include/davidson_hip.h): lifetime, statistics and HIP-event timing, small-matrix staging, panels and
 // block movement.  The engine owns every N-long object in HBM and sequences the kernels of k_*.hip on one HIP stream; the host
 // (Fortran driver) keeps only m x m matrices.  Other parts: engine_comm.hip (RCCL, watchdog, collectives, test transports),
-// engine_operators.hip (operators and their storage, ingest glue), engine_apply.hip (K1 scheduling), engine_solver.hip
-// (projection, Ritz phase, orthonormalisation, restart, device-side Rayleigh-Ritz), engine_gjd.hip (K7).
+// engine_operators.hip (dense, generated and matrix-free operators and their storage, ingest glue), engine_sparse.hip (CSR / BSR
+// operators), engine_apply.hip (K1 scheduling), engine_solver.hip (projection, Ritz phase, orthonormalisation, restart, device-side
+// Rayleigh-Ritz), engine_gjd.hip (K7).
 #include "engine_internal.h"
 
 thread_local std::string g_err;
@@ -569,7 +570,7 @@ extern "C" int dav_destroy(dav_handle_t e) {
     pool_free(e->op[w].e_table);
     pool_free(e->op[w].l2_table);
     pool_free(e->op[w].dadd_table);
-    csr_release(e, e->op[w]);
+    sparse_release(e, e->op[w]);
   }
   lt.lap("operators");
   if (e->stream) { (void)hipStreamSynchronize(e->stream); pool_stream_put(e->stream, e->device); }

@@ -448,6 +448,14 @@ static int apply_sym_set(E* e, int which, OpDesc& o, const SymSet& set, bool par
   }
 }
 
+// Byte and flop model of one product of a sparse operator with k columns (include/davidson_hip.h: dav_stats): values and columns of the
+// entries (blocks of b x b; CSR: b = 1), the offsets, the gathered operand read and this rank's rows written.
+static void sparse_traffic(const E* e, const OpDesc& o, int k, double* bytes, double* flops) {
+  const double bb = (double)o.sp.b * o.sp.b, nnz = (double)o.sp.nnz;
+  *bytes = 8.0 * bb * nnz + 4.0 * nnz + 8.0 * (double)(o.sp.nrows + 1) + 8.0 * (double)e->n * k + 8.0 * (double)e->nloc * k;
+  *flops = 2.0 * bb * nnz * k;
+}
+
 // inner = true: a sweep inside the GJD correction solve (may run on the fp32 copy, dav_set_inner_precision)
 int apply_ptr(E* e, int which, const double* src, int k, double* dst, bool timed, bool inner) {
   OpDesc& o = e->op[which];
@@ -489,14 +497,16 @@ int apply_ptr(E* e, int which, const double* src, int k, double* dst, bool timed
     HIPCHK(hipGetLastError());
     return 0;
   }
-  if (o.kind == DAV_KIND_CSR) {
-    // CSR rows of this rank (k_spmm.hip): the operand packed - and gathered over the ranks - as for the row slabs, then one launch of
-    // the wave-per-item kernel per 64 columns (the matrix is read once per 64 columns) and the chunk sums of the long rows.  Always fp64
-    // (inner sweeps too: there is no fp32 copy of a CSR operator).
+  if (o.kind == DAV_KIND_CSR || o.kind == DAV_KIND_BSR) {
+    // The rows of this rank (CSR, k_spmm.hip) or the block rows touching its slab (BSR, k_bsrmm.hip): the operand packed - and gathered over
+    // the ranks - as for the row slabs, then one launch of the wave-per-item kernel per 64 columns (the matrix is read once per 64 columns)
+    // and the chunk sums of the long rows.  Always fp64 (inner sweeps too: there is no fp32 copy of a sparse operator).
+    const SparseStore& s = o.sp;
     for (int c = 0; c < k; c += 64) {
       const int kk = std::min(64, k - c), groups = (kk + 15) / 16, gp = groups == 3 ? 4 : groups;
       int slot = -1, kslot = -1;
-      const double bytes = 12.0 * (double)o.csr_nnz + 8.0 * (double)(e->nloc + 1) + 8.0 * (double)e->n * kk + 8.0 * (double)e->nloc * kk;
+      double bytes, flops;
+      sparse_traffic(e, o, kk, &bytes, &flops);
       if (timed) CHK(timed_begin(e, which == DAV_OP_A ? 0 : 2, bytes, &slot));
       launch_pack_xt(e->stream, src + (int64_t)c * e->ldp, e->ldp, e->nloc, e->nslab, kk, e->xt, e->xt_group_stride, e->row0);
       if (has_comm(e)) {
@@ -509,46 +519,15 @@ int apply_ptr(E* e, int which, const double* src, int k, double* dst, bool timed
         CHK(grp.end("all-gather of the new block", e->stream));
       }
       double* out = dst + (int64_t)c * e->ldp;
-      if (timed && which == DAV_OP_A) CHK(timed_begin(e, 4, 2.0 * (double)o.csr_nnz * kk, &kslot));
-      launch_spmm_csr(e->stream, o.csr_items, o.csr_nitems, o.csr_rp, o.csr_col, o.csr_val, e->xt, e->xt_group_stride, gp, kk, o.csr_part, out,
-                      e->ldp);
-      launch_spmm_csr_finish(e->stream, o.csr_longs, o.csr_nlong, o.csr_part, kk, out, e->ldp);
-      CHK(timed_end(e, kslot));
-      launch_zero_pad_rows(e->stream, out, e->ldp, e->nloc, e->nloc_pad, kk);
-      CHK(timed_end(e, slot));
-      if (which == DAV_OP_A) {
-        e->st.applies += 1;
-        e->st.apply_cols += kk;
+      if (timed && which == DAV_OP_A) CHK(timed_begin(e, 4, flops, &kslot));
+      if (o.kind == DAV_KIND_CSR) {
+        launch_spmm_csr(e->stream, s.items, s.nitems, s.rp, s.col, s.val, e->xt, e->xt_group_stride, gp, kk, s.part, out, e->ldp);
+        launch_spmm_csr_finish(e->stream, s.longs, s.nlong, s.part, kk, out, e->ldp);
+      } else {
+        launch_spmm_bsr(e->stream, s.items, s.nitems, s.b, s.rp, s.col, s.val, e->xt, e->xt_group_stride, gp, kk, s.part, out, e->ldp, s.grow0,
+                        e->nloc);
+        launch_spmm_bsr_finish(e->stream, s.longs, s.nlong, s.part, s.b, kk, out, e->ldp, s.grow0, e->nloc);
       }
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  if (o.kind == DAV_KIND_BSR) {
-    // BSR block rows touching this rank's slab (k_bsrmm.hip): the same packed, gathered operand as CSR, then one launch of the
-    // matrix-core kernel per 64 columns and the chunk sums of the long block rows.  Always fp64, as CSR.
-    for (int c = 0; c < k; c += 64) {
-      const int kk = std::min(64, k - c), groups = (kk + 15) / 16, gp = groups == 3 ? 4 : groups;
-      int slot = -1, kslot = -1;
-      const double bb = (double)o.bsr_b * o.bsr_b;
-      const double bytes = 8.0 * bb * (double)o.bsr_nnzb + 4.0 * (double)o.bsr_nnzb + 8.0 * (double)(o.bsr_nbl + 1) + 8.0 * (double)e->n * kk +
-                           8.0 * (double)e->nloc * kk;
-      if (timed) CHK(timed_begin(e, which == DAV_OP_A ? 0 : 2, bytes, &slot));
-      launch_pack_xt(e->stream, src + (int64_t)c * e->ldp, e->ldp, e->nloc, e->nslab, kk, e->xt, e->xt_group_stride, e->row0);
-      if (has_comm(e)) {
-        CollGroup grp(e);
-        CHK(grp.begin(5, 8.0 * (double)e->nslab * 16 * groups * e->nranks));
-        for (int g = 0; g < groups; ++g) {
-          double* base = e->xt + g * e->xt_group_stride;
-          CHK(coll_allgather(e, base + e->row0 * 16, base, (size_t)e->nslab * 16));
-        }
-        CHK(grp.end("all-gather of the new block", e->stream));
-      }
-      double* out = dst + (int64_t)c * e->ldp;
-      if (timed && which == DAV_OP_A) CHK(timed_begin(e, 4, 2.0 * bb * (double)o.bsr_nnzb * kk, &kslot));
-      launch_spmm_bsr(e->stream, o.bsr_items, o.bsr_nitems, o.bsr_b, o.bsr_rp, o.bsr_col, o.bsr_val, e->xt, e->xt_group_stride, gp, kk,
-                      o.bsr_part, out, e->ldp, o.bsr_grow0, e->nloc);
-      launch_spmm_bsr_finish(e->stream, o.bsr_longs, o.bsr_nlong, o.bsr_part, o.bsr_b, kk, out, e->ldp, o.bsr_grow0, e->nloc);
       CHK(timed_end(e, kslot));
       launch_zero_pad_rows(e->stream, out, e->ldp, e->nloc, e->nloc_pad, kk);
       CHK(timed_end(e, slot));
@@ -708,19 +687,8 @@ extern "C" int dav_bench_apply2(dav_handle_t e, int which, int k, int reps, doub
   e->timing_level = saved_level;
   *avg_ms = total / reps;
   *kernel_ms = ktotal / reps;
-  if (e->op[which].kind == DAV_KIND_CSR) {     // the CSR byte model of apply_ptr (include/davidson_hip.h: dav_stats)
-    const OpDesc& o = e->op[which];
-    *bytes = 12.0 * (double)o.csr_nnz + 8.0 * (double)(e->nloc + 1) + 8.0 * (double)e->n * k + 8.0 * (double)e->nloc * k;
-    *flops = 2.0 * (double)o.csr_nnz * k;
-    e->st = saved;
-    return 0;
-  }
-  if (e->op[which].kind == DAV_KIND_BSR) {     // the BSR byte model of apply_ptr
-    const OpDesc& o = e->op[which];
-    const double bb = (double)o.bsr_b * o.bsr_b;
-    *bytes = 8.0 * bb * (double)o.bsr_nnzb + 4.0 * (double)o.bsr_nnzb + 8.0 * (double)(o.bsr_nbl + 1) + 8.0 * (double)e->n * k +
-             8.0 * (double)e->nloc * k;
-    *flops = 2.0 * bb * (double)o.bsr_nnzb * k;
+  if (e->op[which].kind == DAV_KIND_CSR || e->op[which].kind == DAV_KIND_BSR) {
+    sparse_traffic(e, e->op[which], k, bytes, flops);
     e->st = saved;
     return 0;
   }

@@ -117,6 +117,22 @@ struct SymSet {
 };
 void sym_set_release(SymSet& s);
 
+// A sparse operator of either kind (engine_sparse.hip): this rank's rows (CSR) or the block rows touching its slab (BSR) in canonical form,
+// and the work list of the block product.  OpDesc::kind says which kernel reads it (k_spmm.hip / k_bsrmm.hip).
+struct SparseStore {
+  int64_t* rp = nullptr;            // device: nrows + 1 offsets from 0 (int64: a rank may hold more than 2^31 entries)
+  int32_t* col = nullptr;           // device: global column (block column) of each entry (block)
+  double* val = nullptr;            // device: value of each entry; b * b values of each block, column-major
+  CsrItem* items = nullptr;         // device: one item per wave (runs of whole rows, chunks of long rows)
+  CsrLong* longs = nullptr;         // device: the rows longer than CSR_CHUNK / BSR_CHUNK and their partial slots
+  double* part = nullptr;           // device: 64 (CSR) / 16 x 64 (BSR) doubles per chunk of a long row
+  int nitems = 0, nlong = 0;
+  int64_t nnz = 0;                  // entries (blocks) of this rank
+  int64_t nrows = 0;                // local rows (block rows)
+  int b = 0;                        // block size; 1 = CSR
+  int64_t grow0 = 0;                // BSR: local row of the first row of local block row 0 (<= 0)
+};
+
 struct OpDesc {
   int kind = DAV_KIND_NONE;
   double* a = nullptr;       // dense: nloc_pad x ncols_pad, column-major, lda = nloc_pad
@@ -145,25 +161,7 @@ struct OpDesc {
   // DAV_KIND_DEVICE: the caller's own block apply on device memory (dav_set_operator_device)
   dav_device_apply_fn dev_fn = nullptr;
   void* dev_ctx = nullptr;
-  // DAV_KIND_CSR (dav_set_operator_csr): this rank's rows in canonical form and the work list of the block product (k_spmm.hip)
-  int64_t* csr_rp = nullptr;        // device: nloc + 1 row offsets from 0 (int64: a rank may hold more than 2^31 entries)
-  int32_t* csr_col = nullptr;       // device: global column of each entry
-  double* csr_val = nullptr;        // device: value of each entry
-  CsrItem* csr_items = nullptr;     // device: one item per wave (runs of whole rows, chunks of long rows)
-  CsrLong* csr_longs = nullptr;     // device: the rows longer than CSR_CHUNK and their partial slots
-  double* csr_part = nullptr;       // device: 64 doubles per chunk of a long row
-  int csr_nitems = 0, csr_nlong = 0;
-  int64_t csr_nnz = 0;              // entries of this rank's rows
-  // DAV_KIND_BSR (dav_set_operator_bsr): the block rows touching this rank's slab in canonical form, blocks column-major (k_bsrmm.hip)
-  int64_t* bsr_rp = nullptr;        // device: nbl + 1 block offsets from 0 over the local block rows
-  int32_t* bsr_col = nullptr;       // device: global block column of each block
-  double* bsr_val = nullptr;        // device: b * b values of each block, column-major
-  CsrItem* bsr_items = nullptr;     // device: one item per wave (runs of whole block rows, chunks of long block rows)
-  CsrLong* bsr_longs = nullptr;     // device: the block rows longer than BSR_CHUNK and their partial slots
-  double* bsr_part = nullptr;       // device: 16 x 64 doubles per chunk of a long block row
-  int bsr_nitems = 0, bsr_nlong = 0, bsr_b = 0;
-  int64_t bsr_nnzb = 0, bsr_nbl = 0;  // blocks and block rows of this rank
-  int64_t bsr_grow0 = 0;            // local row of the first row of local block row 0 (<= 0)
+  SparseStore sp;            // DAV_KIND_CSR / DAV_KIND_BSR
 };
 
 struct SmallBuf {            // device small matrix + pinned staging
@@ -439,8 +437,9 @@ int ingest_acquire(E* e, double** buf, int64_t* cap_rows);
 int ingest_commit(E* e, int64_t row0, int64_t nrows);
 void ingest_wanted(E* e, int64_t* first, int64_t* count);
 OpParams op_params(const OpDesc& o);
-void csr_release(E* e, OpDesc& o);
-void bsr_release(E* e, OpDesc& o);
+int operator_goes(E* e, int which, bool unset = false);
+// ---- engine_sparse.hip -----------------------------------------------------------------------------------
+void sparse_release(E* e, OpDesc& o);
 // ---- engine_apply.hip ------------------------------------------------------------------------------------
 bool inner_f32_tiles(E* e, OpDesc& o);
 bool sym_wide_enabled(const E* e);

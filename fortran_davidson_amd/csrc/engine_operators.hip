@@ -1,6 +1,6 @@
 // Engine, operators: storage modes (full row slabs, symmetric tiles dealt out over the ranks), work lists of the symmetric
 // sweep, dense matrices from host / device memory / row streams / files (ingest glue), generated and matrix-free operators,
-// diagonals.
+// diagonals.  Sparse (CSR / BSR) operators: engine_sparse.hip.
 #include "engine_internal.h"
 
 int refresh_diag_host(E* e, int which) {
@@ -198,11 +198,26 @@ int sym_ensure_slabs(E* e, size_t doubles) {
   return 0;
 }
 
+// What every setter does before it writes a new definition of operator `which`: sweeps in flight may still read the resident tiles or the
+// sparse arrays of the previous one.  unset (the sparse entries, which can still refuse from here on): the operator counts as not set,
+// without diagonal or start-vector order, until the entry commits.
+int operator_goes(E* e, int which, bool unset) {
+  OpDesc& o = e->op[which];
+  HIPCHK(hipStreamSynchronize(e->stream));
+  sym_resident_release(o);
+  sparse_release(e, o);
+  o.res_decided = false;
+  if (unset) {
+    o.kind = DAV_KIND_NONE;
+    e->diag_host[which].clear();
+    if (which == DAV_OP_A) e->basis_order.clear();
+  }
+  return 0;
+}
+
 int alloc_dense(E* e, int which) {
   OpDesc& o = e->op[which];
-  sym_resident_release(o);
-  csr_release(e, o);
-  o.res_decided = false;
+  CHK(operator_goes(e, which));
   o.a32_valid = false;       // new contents: the fp32 copy is rebuilt when the next inner sweep asks for it
   o.a32_refused = false;
   if (o.a && o.storage != e->storage) { pool_free(o.a); o.a = nullptr; }
@@ -495,10 +510,7 @@ extern "C" int dav_set_operator_hashed(dav_handle_t e, int which, uint64_t seed,
   if (which < 0 || which > 1) return fail("dav_set_operator_hashed: bad operator id");
   CHK(bind(e));
   OpDesc& o = e->op[which];
-  HIPCHK(hipStreamSynchronize(e->stream));      // sweeps in flight may still read the resident tiles of the previous definition
-  sym_resident_release(o);
-  csr_release(e, o);
-  o.res_decided = false;
+  CHK(operator_goes(e, which));
   o.kind = DAV_KIND_HASHED; o.seed = seed; o.sparsity = sparsity; o.use_diag = use_diag_val; o.diag_val = diag_val;
   // storage mode "symmetric" (single rank) also applies to the generated operator: every entry of the lower
   // block triangle is produced once and used for both products
@@ -513,10 +525,7 @@ extern "C" int dav_set_operator_harness(dav_handle_t e, int which, const double*
   if (which < 0 || which > 1 || !e_table) return fail("dav_set_operator_harness: bad arguments");
   CHK(bind(e));
   OpDesc& o = e->op[which];
-  HIPCHK(hipStreamSynchronize(e->stream));
-  sym_resident_release(o);
-  csr_release(e, o);
-  o.res_decided = false;
+  CHK(operator_goes(e, which));
   o.kind = DAV_KIND_HARNESS; o.trig = which == DAV_OP_A ? 0 : 1;
   o.storage = e->storage == 1 ? 1 : 0;      // symmetric mode: each entry generated once
   if (o.storage == 1) CHK(sym_setup(e));
@@ -561,10 +570,7 @@ extern "C" int dav_set_operator_identity(dav_handle_t e, int which) {
   if (which < 0 || which > 1) return fail("dav_set_operator_identity: bad operator id");
   CHK(bind(e));
   OpDesc& o = e->op[which];
-  HIPCHK(hipStreamSynchronize(e->stream));
-  sym_resident_release(o);
-  csr_release(e, o);
-  o.res_decided = false;
+  CHK(operator_goes(e, which));
   o.kind = DAV_KIND_IDENTITY;
   launch_diag_free(e->stream, op_params(o), e->row0, e->nloc, o.diag);
   CHK(refresh_diag_host(e, which));
@@ -575,10 +581,7 @@ extern "C" int dav_set_operator_host(dav_handle_t e, int which, const double* di
   if (which < 0 || which > 1 || !diag) return fail("dav_set_operator_host: bad arguments");
   CHK(bind(e));
   OpDesc& o = e->op[which];
-  HIPCHK(hipStreamSynchronize(e->stream));
-  sym_resident_release(o);
-  csr_release(e, o);
-  o.res_decided = false;
+  CHK(operator_goes(e, which));
   o.kind = DAV_KIND_HOST;
   if (e->nloc > 0)
     HIPCHK(hipMemcpyAsync(o.diag, diag + e->row0, sizeof(double) * e->nloc, hipMemcpyHostToDevice, e->stream));
@@ -595,724 +598,6 @@ extern "C" int dav_set_operator_device(dav_handle_t e, int which, dav_device_app
   o.kind = DAV_KIND_DEVICE;
   o.dev_fn = fn;
   o.dev_ctx = ctx;
-  return 0;
-}
-
-// ---- a symmetric matrix in CSR form (dav_set_operator_csr) ---------------------------------------------------------------------------
-// (the arrays of a BSR operator too: every path that sets an operator releases both kinds)
-void csr_release(E* e, OpDesc& o) {
-  bsr_release(e, o);
-  if (!o.csr_rp && !o.csr_col && !o.csr_val && !o.csr_items && !o.csr_longs && !o.csr_part) return;
-  (void)hipStreamSynchronize(e->stream);         // applies in flight may still read the arrays
-  pool_free(o.csr_rp); pool_free(o.csr_col); pool_free(o.csr_val);
-  pool_free(o.csr_items); pool_free(o.csr_longs); pool_free(o.csr_part);
-  o.csr_rp = nullptr; o.csr_col = nullptr; o.csr_val = nullptr;
-  o.csr_items = nullptr; o.csr_longs = nullptr; o.csr_part = nullptr;
-  o.csr_nitems = o.csr_nlong = 0;
-  o.csr_nnz = 0;
-}
-
-void bsr_release(E* e, OpDesc& o) {
-  if (!o.bsr_rp && !o.bsr_col && !o.bsr_val && !o.bsr_items && !o.bsr_longs && !o.bsr_part) return;
-  (void)hipStreamSynchronize(e->stream);
-  pool_free(o.bsr_rp); pool_free(o.bsr_col); pool_free(o.bsr_val);
-  pool_free(o.bsr_items); pool_free(o.bsr_longs); pool_free(o.bsr_part);
-  o.bsr_rp = nullptr; o.bsr_col = nullptr; o.bsr_val = nullptr;
-  o.bsr_items = nullptr; o.bsr_longs = nullptr; o.bsr_part = nullptr;
-  o.bsr_nitems = o.bsr_nlong = o.bsr_b = 0;
-  o.bsr_nnzb = o.bsr_nbl = o.bsr_grow0 = 0;
-}
-
-// Work list of the block product over the canonical local rows rp[0..nloc]: runs of at most CSR_ROWS whole rows with at most CSR_CHUNK
-// entries together, and every row longer than CSR_CHUNK cut into chunks at multiples of CSR_CHUNK from its first entry (one item and
-// one partial slot each; CsrLong lists the slots of the row).  The cut depends on the row alone, so the sums do not depend on the ranks.
-static void csr_build_items(const std::vector<int64_t>& rp, std::vector<CsrItem>& items, std::vector<CsrLong>& longs, int* nslots) {
-  const int64_t nloc = (int64_t)rp.size() - 1;
-  CsrItem cur{0, 0, 0, 0, -1, 0};
-  int slots = 0;
-  auto flush = [&]() { if (cur.nrows > 0) items.push_back(cur); cur.nrows = 0; };
-  for (int64_t i = 0; i < nloc; ++i) {
-    const int64_t a = rp[(size_t)i], b = rp[(size_t)i + 1];
-    if (b - a > CSR_CHUNK) {
-      flush();
-      const int first = slots;
-      for (int64_t q = a; q < b; q += CSR_CHUNK) items.push_back({q, std::min(b, q + CSR_CHUNK), (int32_t)i, 1, slots++, 0});
-      longs.push_back({(int32_t)i, first, slots - first, 0});
-      continue;
-    }
-    if (cur.nrows > 0 && (cur.nrows == CSR_ROWS || b - cur.p0 > CSR_CHUNK)) flush();
-    if (cur.nrows == 0) { cur.p0 = a; cur.row = (int32_t)i; }
-    cur.p1 = b;
-    cur.nrows += 1;
-  }
-  flush();
-  *nslots = slots;
-}
-
-extern "C" int dav_set_operator_csr(dav_handle_t e, int which, const int64_t* row_ptr, const int32_t* col_idx, const double* vals,
-                                    int index_base, int triangle) {
-  if (!e) return fail("dav_set_operator_csr: null engine");
-  if (which < 0 || which > 1) return fail("dav_set_operator_csr: bad operator id");
-  CHK(bind(e));
-  OpDesc& o = e->op[which];
-  // a call that fails leaves the operator unset (the engine stays usable: set it again)
-  auto refuse = [&](const std::string& msg) {
-    csr_release(e, o);
-    o.kind = DAV_KIND_NONE;
-    e->diag_host[which].clear();
-    if (which == DAV_OP_A) e->basis_order.clear();
-    return fail("dav_set_operator_csr: " + msg);
-  };
-  const int64_t n = e->n;
-  // ---- validation of the caller's global arrays: before anything is allocated or launched
-  if (n >= ((int64_t)1 << 31)) return refuse("n = " + std::to_string(n) + " must be below 2^31 (int32 column indices)");
-  if (index_base != 0 && index_base != 1) return refuse("index_base must be 0 or 1");
-  if (triangle != DAV_CSR_FULL && triangle != DAV_CSR_LOWER) return refuse("triangle must be DAV_CSR_FULL or DAV_CSR_LOWER");
-  if (!row_ptr) return refuse("null row_ptr");
-  if (row_ptr[0] != index_base) return refuse("row_ptr[0] = " + std::to_string(row_ptr[0]) + " must equal the index base " + std::to_string(index_base));
-  for (int64_t i = 0; i < n; ++i)
-    if (row_ptr[i + 1] < row_ptr[i]) return refuse("row_ptr decreases at row " + std::to_string(i + index_base));
-  const int64_t nnz = row_ptr[n] - index_base;
-  if (nnz > 0 && (!col_idx || !vals)) return refuse("null col_idx or vals");
-  const bool lower = triangle == DAV_CSR_LOWER;
-  for (int64_t i = 0; i < n; ++i)
-    for (int64_t p = row_ptr[i] - index_base; p < row_ptr[i + 1] - index_base; ++p) {
-      const int64_t j = (int64_t)col_idx[p] - index_base;
-      if (j < 0 || j >= n)
-        return refuse("column index " + std::to_string(col_idx[p]) + " out of range at entry " + std::to_string(p + index_base) + " (row " +
-                      std::to_string(i + index_base) + ")");
-      if (lower && j > i)
-        return refuse("entry (" + std::to_string(i + index_base) + ", " + std::to_string(col_idx[p]) + ") lies above the diagonal of a "
-                      "DAV_CSR_LOWER matrix");
-    }
-  // ---- canonical rows of this rank: own entries in input order, then (DAV_CSR_LOWER) the mirrored strict lower entries in the order of
-  // their source rows; stable sort by column (duplicates stay separate terms, in that order)
-  const int64_t r0 = e->row0, nloc = e->nloc;
-  auto local = [&](int64_t i) { return i >= r0 && i < r0 + nloc; };
-  std::vector<int64_t> rp((size_t)nloc + 1, 0);
-  for (int64_t i = r0; i < r0 + nloc; ++i) rp[(size_t)(i - r0) + 1] = row_ptr[i + 1] - row_ptr[i];
-  if (lower)
-    for (int64_t i = 0; i < n; ++i)
-      for (int64_t p = row_ptr[i] - index_base; p < row_ptr[i + 1] - index_base; ++p) {
-        const int64_t j = (int64_t)col_idx[p] - index_base;
-        if (j < i && local(j)) rp[(size_t)(j - r0) + 1] += 1;
-      }
-  for (int64_t i = 0; i < nloc; ++i) rp[(size_t)i + 1] += rp[(size_t)i];
-  const int64_t lnnz = rp[(size_t)nloc];
-  std::vector<int32_t> lcol((size_t)lnnz);
-  std::vector<double> lval((size_t)lnnz);
-  std::vector<int64_t> pos(rp.begin(), rp.end() - 1);
-  for (int64_t i = r0; i < r0 + nloc; ++i)
-    for (int64_t p = row_ptr[i] - index_base; p < row_ptr[i + 1] - index_base; ++p) {
-      const size_t q = (size_t)pos[(size_t)(i - r0)]++;
-      lcol[q] = (int32_t)(col_idx[p] - index_base);
-      lval[q] = vals[p];
-    }
-  if (lower)
-    for (int64_t i = 0; i < n; ++i)
-      for (int64_t p = row_ptr[i] - index_base; p < row_ptr[i + 1] - index_base; ++p) {
-        const int64_t j = (int64_t)col_idx[p] - index_base;
-        if (j < i && local(j)) {
-          const size_t q = (size_t)pos[(size_t)(j - r0)]++;
-          lcol[q] = (int32_t)i;
-          lval[q] = vals[p];
-        }
-      }
-  std::vector<std::pair<int32_t, double>> row;
-  for (int64_t i = 0; i < nloc; ++i) {
-    const size_t a = (size_t)rp[(size_t)i], b = (size_t)rp[(size_t)i + 1];
-    if (std::is_sorted(lcol.begin() + a, lcol.begin() + b)) continue;
-    row.clear();
-    for (size_t q = a; q < b; ++q) row.push_back({lcol[q], lval[q]});
-    std::stable_sort(row.begin(), row.end(), [](const std::pair<int32_t, double>& x, const std::pair<int32_t, double>& y) { return x.first < y.first; });
-    for (size_t q = a; q < b; ++q) { lcol[q] = row[q - a].first; lval[q] = row[q - a].second; }
-  }
-  // the diagonal of the whole matrix, from the global arrays: duplicates summed in input order, a missing entry counts as 0
-  std::vector<double> diag((size_t)n, 0.0);
-  for (int64_t i = 0; i < n; ++i)
-    for (int64_t p = row_ptr[i] - index_base; p < row_ptr[i + 1] - index_base; ++p)
-      if ((int64_t)col_idx[p] - index_base == i) diag[(size_t)i] += vals[p];
-  std::vector<CsrItem> items;
-  std::vector<CsrLong> longs;
-  int nslots = 0;
-  csr_build_items(rp, items, longs, &nslots);
-  // ---- device copies (the engine's allocator; released when the operator is set again and at dav_destroy)
-  HIPCHK(hipStreamSynchronize(e->stream));
-  sym_resident_release(o);
-  csr_release(e, o);
-  o.kind = DAV_KIND_NONE;
-  auto upload = [&](auto** dst, const auto* src, size_t count) -> int {
-    const size_t bytes = sizeof(**dst) * std::max<size_t>(count, 1);
-    if (pool_malloc(dst, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      *dst = nullptr;
-      return 1;
-    }
-    if (src && count > 0 && hipMemcpy(*dst, src, sizeof(**dst) * count, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return 1; }
-    return 0;
-  };
-  if (upload(&o.csr_rp, rp.data(), rp.size()) || upload(&o.csr_col, lcol.data(), lcol.size()) || upload(&o.csr_val, lval.data(), lval.size()) ||
-      upload(&o.csr_items, items.data(), items.size()) || upload(&o.csr_longs, longs.data(), longs.size()) ||
-      upload(&o.csr_part, (const double*)nullptr, (size_t)nslots * 64))
-    return refuse("device memory for " + std::to_string(lnnz) + " entries of this rank (" + std::to_string((12 * lnnz + 8 * nloc) >> 20) +
-                  " MiB) could not be allocated");
-  o.csr_nitems = (int)items.size();
-  o.csr_nlong = (int)longs.size();
-  o.csr_nnz = lnnz;
-  o.storage = 0;
-  if (nloc > 0) HIPCHK(hipMemcpy(o.diag, diag.data() + r0, sizeof(double) * nloc, hipMemcpyHostToDevice));
-  e->diag_host[which].swap(diag);
-  if (which == DAV_OP_A) e->basis_order.clear();
-  o.kind = DAV_KIND_CSR;
-  return 0;
-}
-
-// ---- sparse matrices from device arrays, built on the GPU (dav_set_operator_csr_dev, dav_set_operator_bsr_dev) ---------------------------
-// Both entries build the same index level with the kernels of k_csr_build.hip - over the rows of a CSR matrix with the value of an entry
-// as payload, over the block rows of a BSR matrix with the source of a block - and share the steps below.  Each step returns 0, or
-// non-zero with *why set (the caller refuses the matrix with that message) or *why empty (a HIP failure, already recorded by fail()).
-namespace {
-// the nouns of the host entries' messages
-struct SparseWords { const char *rp, *ci, *row, *rows, *col, *item, *items; };
-const SparseWords CSR_WORDS{"row_ptr", "col_idx", "row", "rows", "column index", "entry", "entries"};
-const SparseWords BSR_WORDS{"block_row_ptr", "block_col_idx", "block row", "block rows", "block column", "block", "blocks"};
-
-// a caller's pointer: device memory of this engine's device, large enough where the runtime can tell (before any launch)
-bool device_array(E* e, const void* p, const char* name, size_t bytes, std::string* why) {
-  hipPointerAttribute_t at{};
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-    (void)hipGetLastError();
-    *why = std::string(name) + " is not device memory (the runtime does not know the pointer)";
-    return false;
-  }
-  if (at.type != hipMemoryTypeDevice) { *why = std::string(name) + " is not device memory (host, pinned or managed)"; return false; }
-  if (at.device != e->device) {
-    *why = std::string(name) + " lies on device " + std::to_string(at.device) + ", the engine on device " + std::to_string(e->device);
-    return false;
-  }
-  hipDeviceptr_t lo = nullptr;
-  size_t size = 0;
-  if (hipMemGetAddressRange(&lo, &size, (hipDeviceptr_t)p) == hipSuccess) {
-    if ((const char*)p + bytes > (const char*)lo + size)
-      { *why = std::string(name) + " holds fewer than the " + std::to_string(bytes) + " bytes the matrix needs"; return false; }
-  } else {
-    (void)hipGetLastError();
-  }
-  return true;
-}
-
-// scratch of a build: released on every way out, after the stream has finished with it
-struct BuildScratch {
-  hipStream_t st;
-  std::vector<void*> held;
-  bool oom = false;
-  explicit BuildScratch(hipStream_t s) : st(s) {}
-  BuildScratch(const BuildScratch&) = delete;
-  ~BuildScratch() { (void)hipStreamSynchronize(st); for (void* p : held) pool_free(p); }
-  template <class T> void take(T** p, size_t count) {
-    *p = nullptr;
-    if (oom) return;
-    if (pool_malloc(p, sizeof(T) * std::max<size_t>(count, 1)) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; oom = true; return; }
-    held.push_back((void*)*p);
-  }
-};
-
-// storage that stays with the operator
-template <class T> bool keep(T** p, size_t count) {
-  if (pool_malloc(p, sizeof(T) * std::max<size_t>(count, 1)) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
-  return true;
-}
-
-int readback(hipStream_t st, void* dst, const void* src, size_t bytes) {
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return 0;
-}
-
-std::string no_memory(const std::string& what) { return "device memory for " + what + " could not be allocated"; }
-
-// the caller's pattern: n rows (block rows) of the whole matrix, of which [r0, r0 + nloc) are this rank's; item_bytes of vals per entry
-struct DevPattern {
-  const void* row_ptr; int rp64;
-  const void* col_idx; int ci64;
-  const double* vals; size_t item_bytes;
-  int64_t n, r0, nloc;
-  int base; bool lower;
-  // set by pattern_validate_dev
-  int64_t nnz = 0;
-  int32_t* mcount = nullptr;               // mirrored entries per local row; later the slots taken by the scatter
-  uint32_t* dcount = nullptr;              // diagonal entries per row of the whole matrix
-  unsigned long long* dfirst = nullptr;    // the first of them
-};
-
-// the pointers, then the rules of the host entry on the device: row_ptr first, then the entries (the first offending position, as the host
-// loop names it)
-int pattern_validate_dev(E* e, BuildScratch& sc, DevPattern& P, const SparseWords& w, std::string* why) {
-  hipStream_t st = e->stream;
-  const size_t rpw = P.rp64 ? 8 : 4, ciw = P.ci64 ? 8 : 4;
-  const int64_t n = P.n;
-  if (!device_array(e, P.row_ptr, w.rp, rpw * (size_t)(n + 1), why)) return 1;
-  if (P.col_idx && !device_array(e, P.col_idx, w.ci, 0, why)) return 1;
-  if (P.vals && !device_array(e, P.vals, "vals", 0, why)) return 1;
-  unsigned long long* info = nullptr;
-  sc.take(&info, 4);
-  if (sc.oom) { *why = no_memory("the validation"); return 1; }
-  HIPCHK(hipMemsetAsync(info, 0xff, sizeof(unsigned long long) * 4, st));
-  launch_csr_build_rows(st, P.row_ptr, P.rp64, n, info);
-  unsigned long long hinfo[4];
-  CHK(readback(st, hinfo, info, sizeof(hinfo)));
-  const int64_t rp0 = (int64_t)hinfo[1], rpn = (int64_t)hinfo[2];
-  if (rp0 != P.base) {
-    *why = std::string(w.rp) + "[0] = " + std::to_string(rp0) + " must equal the index base " + std::to_string(P.base);
-    return 1;
-  }
-  if (hinfo[0] != ~0ull) { *why = std::string(w.rp) + " decreases at " + w.row + " " + std::to_string((int64_t)hinfo[0] + P.base); return 1; }
-  P.nnz = rpn - P.base;
-  if (P.nnz > 0 && (!P.col_idx || !P.vals)) { *why = std::string("null ") + w.ci + " or vals"; return 1; }
-  if (hinfo[3] != ~0ull) {
-    *why = std::string(w.row) + " " + std::to_string((int64_t)hinfo[3] + P.base) + " holds 2^32 " + w.items + " or more";
-    return 1;
-  }
-  if (P.nnz > 0 && (!device_array(e, P.col_idx, w.ci, ciw * (size_t)P.nnz, why) || !device_array(e, P.vals, "vals", P.item_bytes * (size_t)P.nnz, why)))
-    return 1;
-  int64_t* locate = nullptr;
-  sc.take(&P.mcount, (size_t)P.nloc); sc.take(&P.dcount, (size_t)n); sc.take(&P.dfirst, (size_t)n); sc.take(&locate, 2);
-  if (sc.oom) { *why = no_memory("the validation of " + std::to_string(n) + " " + w.rows); return 1; }
-  HIPCHK(hipMemsetAsync(P.mcount, 0, sizeof(int32_t) * std::max<int64_t>(P.nloc, 1), st));
-  HIPCHK(hipMemsetAsync(P.dcount, 0, sizeof(uint32_t) * std::max<int64_t>(n, 1), st));
-  HIPCHK(hipMemsetAsync(P.dfirst, 0xff, sizeof(unsigned long long) * std::max<int64_t>(n, 1), st));
-  launch_csr_build_check(st, P.row_ptr, P.rp64, P.col_idx, P.ci64, n, P.nnz, P.base, P.lower ? 1 : 0, P.r0, P.nloc, info + 3, P.mcount, P.dcount,
-                         P.dfirst);
-  CHK(readback(st, hinfo, info, sizeof(hinfo)));
-  if (hinfo[3] != ~0ull) {
-    const int64_t p = (int64_t)hinfo[3];
-    launch_csr_build_locate(st, P.row_ptr, P.rp64, P.col_idx, P.ci64, n, P.base, p, locate);
-    int64_t loc[2];
-    CHK(readback(st, loc, locate, sizeof(loc)));
-    const int64_t i = loc[0], c = loc[1], j = c - P.base;
-    if (j < 0 || j >= n)
-      *why = std::string(w.col) + " " + std::to_string(c) + " out of range at " + w.item + " " + std::to_string(p + P.base) + " (" + w.row + " " +
-             std::to_string(i + P.base) + ")";
-    else
-      *why = std::string(w.item) + " (" + std::to_string(i + P.base) + ", " + std::to_string(c) + ") lies above the diagonal of a DAV_CSR_LOWER matrix";
-    return 1;
-  }
-  return 0;
-}
-
-// *lrp (kept with the operator) and rp = the int64 offsets of the canonical local rows
-int pattern_offsets_dev(E* e, BuildScratch& sc, const DevPattern& P, const SparseWords& w, int64_t** lrp, std::vector<int64_t>& rp, std::string* why) {
-  int64_t* tile_sums = nullptr;
-  sc.take(&tile_sums, (size_t)csr_build_scan_tiles(P.nloc));
-  if (sc.oom || !keep(lrp, (size_t)P.nloc + 1)) { *why = no_memory(std::string("the ") + w.row + " offsets of this rank"); return 1; }
-  launch_csr_build_offsets(e->stream, P.row_ptr, P.rp64, P.r0, P.nloc, P.mcount, *lrp, tile_sums);
-  rp.assign((size_t)P.nloc + 1, 0);
-  CHK(readback(e->stream, rp.data(), *lrp, sizeof(int64_t) * rp.size()));
-  return 0;
-}
-
-void pattern_scatter(hipStream_t st, const DevPattern& P, int64_t p_lo, int64_t p_hi, const int64_t* lrp, int32_t* ocol, double* oval, uint32_t* tie) {
-  launch_csr_build_scatter(st, P.row_ptr, P.rp64, P.col_idx, P.ci64, P.vals, P.n, p_lo, p_hi, P.base, P.lower ? 1 : 0, P.r0, P.nloc, lrp, P.mcount,
-                           ocol, oval, tie);
-}
-void pattern_scatter(hipStream_t st, const DevPattern& P, int64_t p_lo, int64_t p_hi, const int64_t* lrp, int32_t* ocol, uint64_t* osrc, uint32_t* tie) {
-  launch_csr_build_scatter(st, P.row_ptr, P.rp64, P.col_idx, P.ci64, P.n, p_lo, p_hi, P.base, P.lower ? 1 : 0, P.r0, P.nloc, lrp, P.mcount, ocol,
-                           osrc, tie);
-}
-
-// the canonical order: columns to ocol and payloads (values / block sources) to oval, every local row in the order of the host entry
-template <class V>
-int pattern_order_dev(E* e, BuildScratch& sc, const DevPattern& P, const SparseWords& w, const int64_t* lrp, const std::vector<int64_t>& rp,
-                      int32_t* ocol, V* oval, std::string* why) {
-  hipStream_t st = e->stream;
-  const int64_t nloc = P.nloc, lnnz = rp[(size_t)nloc];
-  const size_t rpw = P.rp64 ? 8 : 4;
-  uint32_t* tie = nullptr;
-  uint8_t* flag = nullptr;
-  if (P.lower) sc.take(&tie, (size_t)lnnz);
-  sc.take(&flag, (size_t)nloc);
-  if (sc.oom) { *why = no_memory("sorting " + std::to_string(lnnz) + " " + w.items); return 1; }
-  // own entries: those of the local rows; mirrored entries (lower): any row of the matrix may send some
-  int64_t p_lo = 0, p_hi = P.nnz;
-  if (!P.lower && nloc > 0) {
-    int64_t ends[2] = {0, 0};
-    for (int s = 0; s < 2; ++s) {
-      const char* src = (const char*)P.row_ptr + rpw * (size_t)(s == 0 ? P.r0 : P.r0 + nloc);
-      CHK(readback(st, &ends[s], src, rpw));
-      if (!P.rp64) ends[s] = (int64_t)(int32_t)ends[s];
-    }
-    p_lo = ends[0] - P.base;
-    p_hi = ends[1] - P.base;
-  }
-  HIPCHK(hipMemsetAsync(P.mcount, 0, sizeof(int32_t) * std::max<int64_t>(nloc, 1), st));
-  HIPCHK(hipMemsetAsync(flag, 0, std::max<int64_t>(nloc, 1), st));
-  if (nloc > 0) pattern_scatter(st, P, p_lo, p_hi, lrp, ocol, oval, tie);
-  launch_csr_build_flag(st, lrp, nloc, lnnz, ocol, tie, flag);
-  launch_csr_build_sort_rows(st, lrp, nloc, flag, ocol, oval, tie);
-  // rows longer than one LDS tile that are out of order: tiles sorted, then merged (one row at a time)
-  const int64_t tile = csr_build_sort_tile();
-  int64_t longest = 0;
-  std::vector<int64_t> cand, longs_unsorted;
-  for (int64_t i = 0; i < nloc; ++i)
-    if (rp[(size_t)i + 1] - rp[(size_t)i] > tile) cand.push_back(i);
-  if (!cand.empty()) {
-    std::vector<uint8_t> hflag((size_t)nloc);
-    CHK(readback(st, hflag.data(), flag, (size_t)nloc));
-    for (int64_t i : cand)
-      if (hflag[(size_t)i]) { longs_unsorted.push_back(i); longest = std::max(longest, rp[(size_t)i + 1] - rp[(size_t)i]); }
-  }
-  if (!longs_unsorted.empty()) {
-    uint64_t *k0 = nullptr, *k1 = nullptr;
-    V *v0 = nullptr, *v1 = nullptr;
-    sc.take(&k0, (size_t)longest); sc.take(&k1, (size_t)longest); sc.take(&v0, (size_t)longest); sc.take(&v1, (size_t)longest);
-    if (sc.oom) { *why = no_memory(std::string("sorting a ") + w.row + " of " + std::to_string(longest) + " " + w.items); return 1; }
-    for (int64_t i : longs_unsorted)
-      launch_csr_build_sort_long(st, rp[(size_t)i], rp[(size_t)i + 1] - rp[(size_t)i], ocol, oval, tie, k0, v0, k1, v1);
-  }
-  return 0;
-}
-}  // namespace
-
-// Validation, canonical rows, diagonal and storage equal those of dav_set_operator_csr bit for bit; only the work list is built on the
-// host, over the canonical row offsets read back (8 (nloc + 1) bytes).
-extern "C" int dav_set_operator_csr_dev(dav_handle_t e, int which, const void* row_ptr, int row_ptr_bits, const void* col_idx, int col_bits,
-                                        const double* vals, int index_base, int triangle) {
-  if (!e) return fail("dav_set_operator_csr_dev: null engine");
-  if (which < 0 || which > 1) return fail("dav_set_operator_csr_dev: bad operator id");
-  CHK(bind(e));
-  OpDesc& o = e->op[which];
-  auto refuse = [&](const std::string& msg) {
-    csr_release(e, o);
-    o.kind = DAV_KIND_NONE;
-    e->diag_host[which].clear();
-    if (which == DAV_OP_A) e->basis_order.clear();
-    return fail("dav_set_operator_csr_dev: " + msg);
-  };
-  const int64_t n = e->n, r0 = e->row0, nloc = e->nloc;
-  hipStream_t st = e->stream;
-  if (n >= ((int64_t)1 << 31)) return refuse("n = " + std::to_string(n) + " must be below 2^31 (int32 column indices)");
-  if (index_base != 0 && index_base != 1) return refuse("index_base must be 0 or 1");
-  if (triangle != DAV_CSR_FULL && triangle != DAV_CSR_LOWER) return refuse("triangle must be DAV_CSR_FULL or DAV_CSR_LOWER");
-  if (row_ptr_bits != 32 && row_ptr_bits != 64) return refuse("row_ptr_bits must be 32 or 64");
-  if (col_bits != 32 && col_bits != 64) return refuse("col_bits must be 32 or 64");
-  if (!row_ptr) return refuse("null row_ptr");
-  BuildScratch sc(st);
-  std::string why;
-  auto step = [&](int rc) { return why.empty() ? rc : refuse(why); };
-  DevPattern P{row_ptr, row_ptr_bits == 64, col_idx, col_bits == 64, vals, 8, n, r0, nloc, index_base, triangle == DAV_CSR_LOWER};
-  if (int rc = pattern_validate_dev(e, sc, P, CSR_WORDS, &why)) return step(rc);
-  // ---- valid: the previous operator goes, the canonical rows of this rank are built in its place
-  HIPCHK(hipStreamSynchronize(st));
-  sym_resident_release(o);
-  csr_release(e, o);
-  o.kind = DAV_KIND_NONE;
-  e->diag_host[which].clear();
-  if (which == DAV_OP_A) e->basis_order.clear();
-  std::vector<int64_t> rp;
-  if (int rc = pattern_offsets_dev(e, sc, P, CSR_WORDS, &o.csr_rp, rp, &why)) return step(rc);
-  const int64_t lnnz = rp[(size_t)nloc];
-  if (!keep(&o.csr_col, (size_t)lnnz) || !keep(&o.csr_val, (size_t)lnnz))
-    return refuse(no_memory(std::to_string(lnnz) + " entries of this rank (" + std::to_string((12 * lnnz + 8 * nloc) >> 20) + " MiB)"));
-  if (int rc = pattern_order_dev(e, sc, P, CSR_WORDS, o.csr_rp, rp, o.csr_col, o.csr_val, &why)) return step(rc);
-  // the diagonal of the whole matrix: this rank's slab to o.diag, all of it to the host copy
-  double* diag = nullptr;
-  sc.take(&diag, (size_t)n);
-  if (sc.oom) return refuse(no_memory("the diagonal"));
-  launch_csr_build_diag(st, row_ptr, P.rp64, col_idx, P.ci64, vals, n, index_base, P.dcount, P.dfirst, diag);
-  if (nloc > 0) HIPCHK(hipMemcpyAsync(o.diag, diag + r0, sizeof(double) * nloc, hipMemcpyDeviceToDevice, st));
-  std::vector<double> hdiag((size_t)n);
-  CHK(readback(st, hdiag.data(), diag, sizeof(double) * (size_t)n));
-  // ---- the work list of the block product, over the canonical offsets (as dav_set_operator_csr builds it)
-  std::vector<CsrItem> items;
-  std::vector<CsrLong> longs;
-  int nslots = 0;
-  csr_build_items(rp, items, longs, &nslots);
-  auto upload = [&](auto** dst, const auto* src, size_t count) -> int {
-    if (!keep(dst, count)) return 1;
-    if (count > 0 && hipMemcpy(*dst, src, sizeof(**dst) * count, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return 1; }
-    return 0;
-  };
-  if (upload(&o.csr_items, items.data(), items.size()) || upload(&o.csr_longs, longs.data(), longs.size()) ||
-      !keep(&o.csr_part, (size_t)nslots * 64))
-    return refuse(no_memory("the work list of " + std::to_string(lnnz) + " entries of this rank"));
-  HIPCHK(hipStreamSynchronize(st));                 // the caller's arrays are free again when the call returns
-  HIPCHK(hipGetLastError());
-  o.csr_nitems = (int)items.size();
-  o.csr_nlong = (int)longs.size();
-  o.csr_nnz = lnnz;
-  o.storage = 0;
-  e->diag_host[which].swap(hdiag);
-  if (which == DAV_OP_A) e->basis_order.clear();
-  o.kind = DAV_KIND_CSR;
-  return 0;
-}
-
-// ---- a symmetric matrix in BSR form (dav_set_operator_bsr) ---------------------------------------------------------------------------
-// Work list of the block product over the canonical local block rows rp[0..nbl]: runs of whole block rows of at most BSR_ROWS matrix rows
-// and BSR_CHUNK blocks together, every block row longer than BSR_CHUNK cut into chunks at multiples of BSR_CHUNK from its first block.
-static void bsr_build_items(const std::vector<int64_t>& rp, int b, std::vector<CsrItem>& items, std::vector<CsrLong>& longs, int* nslots) {
-  const int64_t nbl = (int64_t)rp.size() - 1;
-  const int max_rows = std::max(1, BSR_ROWS / b);
-  CsrItem cur{0, 0, 0, 0, -1, 0};
-  int slots = 0;
-  auto flush = [&]() { if (cur.nrows > 0) items.push_back(cur); cur.nrows = 0; };
-  for (int64_t i = 0; i < nbl; ++i) {
-    const int64_t a = rp[(size_t)i], e = rp[(size_t)i + 1];
-    if (e - a > BSR_CHUNK) {
-      flush();
-      const int first = slots;
-      for (int64_t q = a; q < e; q += BSR_CHUNK) items.push_back({q, std::min(e, q + BSR_CHUNK), (int32_t)i, 1, slots++, 0});
-      longs.push_back({(int32_t)i, first, slots - first, 0});
-      continue;
-    }
-    if (cur.nrows > 0 && (cur.nrows == max_rows || e - cur.p0 > BSR_CHUNK)) flush();
-    if (cur.nrows == 0) { cur.p0 = a; cur.row = (int32_t)i; }
-    cur.p1 = e;
-    cur.nrows += 1;
-  }
-  flush();
-  *nslots = slots;
-}
-
-extern "C" int dav_set_operator_bsr(dav_handle_t e, int which, int block_size, const int64_t* block_row_ptr, const int32_t* block_col_idx,
-                                    const double* vals, int index_base, int triangle, int block_layout) {
-  if (!e) return fail("dav_set_operator_bsr: null engine");
-  if (which < 0 || which > 1) return fail("dav_set_operator_bsr: bad operator id");
-  CHK(bind(e));
-  OpDesc& o = e->op[which];
-  // a call that fails leaves the operator unset (the engine stays usable: set it again)
-  auto refuse = [&](const std::string& msg) {
-    csr_release(e, o);
-    o.kind = DAV_KIND_NONE;
-    e->diag_host[which].clear();
-    if (which == DAV_OP_A) e->basis_order.clear();
-    return fail("dav_set_operator_bsr: " + msg);
-  };
-  const int64_t n = e->n;
-  const int b = block_size;
-  // ---- validation of the caller's global arrays: before anything is allocated or launched
-  if (b < 1 || b > 16) return refuse("block_size = " + std::to_string(b) + " must lie in 1..16");
-  if (n % b != 0) return refuse("n = " + std::to_string(n) + " is not a multiple of block_size = " + std::to_string(b));
-  const int64_t nb = n / b;
-  if (nb >= ((int64_t)1 << 31)) return refuse("n / block_size must be below 2^31 (int32 block columns)");
-  if (index_base != 0 && index_base != 1) return refuse("index_base must be 0 or 1");
-  if (triangle != DAV_CSR_FULL && triangle != DAV_CSR_LOWER) return refuse("triangle must be DAV_CSR_FULL or DAV_CSR_LOWER");
-  if (block_layout != DAV_BSR_ROW_MAJOR && block_layout != DAV_BSR_COL_MAJOR) return refuse("block_layout must be DAV_BSR_ROW_MAJOR or DAV_BSR_COL_MAJOR");
-  if (!block_row_ptr) return refuse("null block_row_ptr");
-  const int64_t* rpg = block_row_ptr;
-  if (rpg[0] != index_base) return refuse("block_row_ptr[0] = " + std::to_string(rpg[0]) + " must equal the index base " + std::to_string(index_base));
-  for (int64_t I = 0; I < nb; ++I)
-    if (rpg[I + 1] < rpg[I]) return refuse("block_row_ptr decreases at block row " + std::to_string(I + index_base));
-  const int64_t nnzb = rpg[nb] - index_base;
-  if (nnzb > 0 && (!block_col_idx || !vals)) return refuse("null block_col_idx or vals");
-  const bool lower = triangle == DAV_CSR_LOWER;
-  for (int64_t I = 0; I < nb; ++I)
-    for (int64_t p = rpg[I] - index_base; p < rpg[I + 1] - index_base; ++p) {
-      const int64_t J = (int64_t)block_col_idx[p] - index_base;
-      if (J < 0 || J >= nb)
-        return refuse("block column " + std::to_string(block_col_idx[p]) + " out of range at block " + std::to_string(p + index_base) +
-                      " (block row " + std::to_string(I + index_base) + ")");
-      if (lower && J > I)
-        return refuse("block (" + std::to_string(I + index_base) + ", " + std::to_string(block_col_idx[p]) + ") lies above the diagonal of a "
-                      "DAV_CSR_LOWER matrix");
-    }
-  // entry (m, k) of input block p in the caller's layout
-  const int64_t bb = (int64_t)b * b;
-  const bool rowmaj = block_layout == DAV_BSR_ROW_MAJOR;
-  auto entry = [&](int64_t p, int m, int k) { return vals[p * bb + (rowmaj ? (int64_t)m * b + k : (int64_t)k * b + m)]; };
-  // ---- canonical block rows touching this rank's slab [row0, row0 + nloc): own blocks in input order, then (DAV_CSR_LOWER) the mirrored
-  // strict lower blocks in the order of their source block rows; stable sort by block column (duplicates stay separate terms)
-  const int64_t r0 = e->row0, nloc = e->nloc;
-  const int64_t ib0 = nloc > 0 ? r0 / b : 0, ib1 = nloc > 0 ? (r0 + nloc + b - 1) / b : 0, nbl = ib1 - ib0;
-  auto local = [&](int64_t I) { return I >= ib0 && I < ib1; };
-  std::vector<int64_t> rp((size_t)nbl + 1, 0);
-  for (int64_t I = ib0; I < ib1; ++I) rp[(size_t)(I - ib0) + 1] = rpg[I + 1] - rpg[I];
-  if (lower)
-    for (int64_t I = 0; I < nb; ++I)
-      for (int64_t p = rpg[I] - index_base; p < rpg[I + 1] - index_base; ++p) {
-        const int64_t J = (int64_t)block_col_idx[p] - index_base;
-        if (J < I && local(J)) rp[(size_t)(J - ib0) + 1] += 1;
-      }
-  for (int64_t i = 0; i < nbl; ++i) rp[(size_t)i + 1] += rp[(size_t)i];
-  const int64_t lnnzb = rp[(size_t)nbl];
-  // source of each canonical block: input block p, transposed or not
-  std::vector<int32_t> lcol((size_t)lnnzb);
-  std::vector<std::pair<int64_t, bool>> src((size_t)lnnzb);
-  std::vector<int64_t> pos(rp.begin(), rp.end() - 1);
-  for (int64_t I = ib0; I < ib1; ++I)
-    for (int64_t p = rpg[I] - index_base; p < rpg[I + 1] - index_base; ++p) {
-      const size_t q = (size_t)pos[(size_t)(I - ib0)]++;
-      lcol[q] = (int32_t)(block_col_idx[p] - index_base);
-      src[q] = {p, false};
-    }
-  if (lower)
-    for (int64_t I = 0; I < nb; ++I)
-      for (int64_t p = rpg[I] - index_base; p < rpg[I + 1] - index_base; ++p) {
-        const int64_t J = (int64_t)block_col_idx[p] - index_base;
-        if (J < I && local(J)) {
-          const size_t q = (size_t)pos[(size_t)(J - ib0)]++;
-          lcol[q] = (int32_t)I;
-          src[q] = {p, true};
-        }
-      }
-  std::vector<size_t> perm;
-  for (int64_t i = 0; i < nbl; ++i) {
-    const size_t a = (size_t)rp[(size_t)i], z = (size_t)rp[(size_t)i + 1];
-    if (std::is_sorted(lcol.begin() + a, lcol.begin() + z)) continue;
-    perm.resize(z - a);
-    for (size_t q = a; q < z; ++q) perm[q - a] = q;
-    std::stable_sort(perm.begin(), perm.end(), [&](size_t x, size_t y) { return lcol[x] < lcol[y]; });
-    std::vector<int32_t> c2(z - a);
-    std::vector<std::pair<int64_t, bool>> s2(z - a);
-    for (size_t q = 0; q < z - a; ++q) { c2[q] = lcol[perm[q]]; s2[q] = src[perm[q]]; }
-    std::copy(c2.begin(), c2.end(), lcol.begin() + a);
-    std::copy(s2.begin(), s2.end(), src.begin() + a);
-  }
-  // values column-major per block: lval[q * b * b + k * b + m] = A_q[m][k] (a mirrored block is the transpose of its source)
-  std::vector<double> lval((size_t)(lnnzb * bb));
-  for (int64_t q = 0; q < lnnzb; ++q) {
-    double* d = lval.data() + q * bb;
-    const int64_t p = src[(size_t)q].first;
-    const bool tr = src[(size_t)q].second;
-    for (int k = 0; k < b; ++k)
-      for (int m = 0; m < b; ++m) d[(int64_t)k * b + m] = tr ? entry(p, k, m) : entry(p, m, k);
-  }
-  // the diagonal of the whole matrix, from the diagonal blocks of the global arrays (duplicates summed in input order)
-  std::vector<double> diag((size_t)n, 0.0);
-  for (int64_t I = 0; I < nb; ++I)
-    for (int64_t p = rpg[I] - index_base; p < rpg[I + 1] - index_base; ++p)
-      if ((int64_t)block_col_idx[p] - index_base == I)
-        for (int m = 0; m < b; ++m) diag[(size_t)(I * b + m)] += entry(p, m, m);
-  std::vector<CsrItem> items;
-  std::vector<CsrLong> longs;
-  int nslots = 0;
-  bsr_build_items(rp, b, items, longs, &nslots);
-  // ---- device copies (the engine's allocator; released when the operator is set again and at dav_destroy)
-  HIPCHK(hipStreamSynchronize(e->stream));
-  sym_resident_release(o);
-  csr_release(e, o);
-  o.kind = DAV_KIND_NONE;
-  auto upload = [&](auto** dst, const auto* s, size_t count) -> int {
-    const size_t bytes = sizeof(**dst) * std::max<size_t>(count, 1);
-    if (pool_malloc(dst, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      *dst = nullptr;
-      return 1;
-    }
-    if (s && count > 0 && hipMemcpy(*dst, s, sizeof(**dst) * count, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return 1; }
-    return 0;
-  };
-  if (upload(&o.bsr_rp, rp.data(), rp.size()) || upload(&o.bsr_col, lcol.data(), lcol.size()) || upload(&o.bsr_val, lval.data(), lval.size()) ||
-      upload(&o.bsr_items, items.data(), items.size()) || upload(&o.bsr_longs, longs.data(), longs.size()) ||
-      upload(&o.bsr_part, (const double*)nullptr, (size_t)nslots * 1024))
-    return refuse("device memory for " + std::to_string(lnnzb) + " blocks of this rank (" + std::to_string((lnnzb * (8 * bb + 4)) >> 20) +
-                  " MiB) could not be allocated");
-  o.bsr_nitems = (int)items.size();
-  o.bsr_nlong = (int)longs.size();
-  o.bsr_b = b;
-  o.bsr_nnzb = lnnzb;
-  o.bsr_nbl = nbl;
-  o.bsr_grow0 = ib0 * b - r0;
-  o.storage = 0;
-  if (nloc > 0) HIPCHK(hipMemcpy(o.diag, diag.data() + r0, sizeof(double) * nloc, hipMemcpyHostToDevice));
-  e->diag_host[which].swap(diag);
-  if (which == DAV_OP_A) e->basis_order.clear();
-  o.kind = DAV_KIND_BSR;
-  return 0;
-}
-
-// ---- the same matrix from device arrays, built on the GPU (dav_set_operator_bsr_dev; kernels in k_csr_build.hip and k_bsr_build.hip) ----
-// The index level is the CSR device build over the n / b block rows, local block rows = those that touch the slab, with the SOURCE of a
-// block (input position, mirrored or not) as payload; the values then move once (launch_bsr_build_gather).  Validation, canonical block
-// rows, values, diagonal and work list equal those of dav_set_operator_bsr bit for bit.
-extern "C" int dav_set_operator_bsr_dev(dav_handle_t e, int which, int block_size, const void* block_row_ptr, int row_ptr_bits,
-                                        const void* block_col_idx, int col_bits, const double* vals, int index_base, int triangle,
-                                        int block_layout) {
-  if (!e) return fail("dav_set_operator_bsr_dev: null engine");
-  if (which < 0 || which > 1) return fail("dav_set_operator_bsr_dev: bad operator id");
-  CHK(bind(e));
-  OpDesc& o = e->op[which];
-  auto refuse = [&](const std::string& msg) {
-    csr_release(e, o);
-    o.kind = DAV_KIND_NONE;
-    e->diag_host[which].clear();
-    if (which == DAV_OP_A) e->basis_order.clear();
-    return fail("dav_set_operator_bsr_dev: " + msg);
-  };
-  const int64_t n = e->n;
-  const int b = block_size;
-  hipStream_t st = e->stream;
-  if (b < 1 || b > 16) return refuse("block_size = " + std::to_string(b) + " must lie in 1..16");
-  if (n % b != 0) return refuse("n = " + std::to_string(n) + " is not a multiple of block_size = " + std::to_string(b));
-  const int64_t nb = n / b;
-  if (nb >= ((int64_t)1 << 31)) return refuse("n / block_size must be below 2^31 (int32 block columns)");
-  if (index_base != 0 && index_base != 1) return refuse("index_base must be 0 or 1");
-  if (triangle != DAV_CSR_FULL && triangle != DAV_CSR_LOWER) return refuse("triangle must be DAV_CSR_FULL or DAV_CSR_LOWER");
-  if (block_layout != DAV_BSR_ROW_MAJOR && block_layout != DAV_BSR_COL_MAJOR) return refuse("block_layout must be DAV_BSR_ROW_MAJOR or DAV_BSR_COL_MAJOR");
-  if (row_ptr_bits != 32 && row_ptr_bits != 64) return refuse("row_ptr_bits must be 32 or 64");
-  if (col_bits != 32 && col_bits != 64) return refuse("col_bits must be 32 or 64");
-  if (!block_row_ptr) return refuse("null block_row_ptr");
-  const int64_t bb = (int64_t)b * b;
-  // the block rows that touch this rank's slab [row0, row0 + nloc)
-  const int64_t r0 = e->row0, nloc = e->nloc;
-  const int64_t ib0 = nloc > 0 ? r0 / b : 0, ib1 = nloc > 0 ? (r0 + nloc + b - 1) / b : 0, nbl = ib1 - ib0;
-  BuildScratch sc(st);
-  std::string why;
-  auto step = [&](int rc) { return why.empty() ? rc : refuse(why); };
-  DevPattern P{block_row_ptr, row_ptr_bits == 64, block_col_idx, col_bits == 64, vals, 8 * (size_t)bb, nb, ib0, nbl, index_base,
-               triangle == DAV_CSR_LOWER};
-  if (int rc = pattern_validate_dev(e, sc, P, BSR_WORDS, &why)) return step(rc);
-  // ---- valid: the previous operator goes, the canonical block rows of this rank are built in its place
-  HIPCHK(hipStreamSynchronize(st));
-  sym_resident_release(o);
-  csr_release(e, o);
-  o.kind = DAV_KIND_NONE;
-  e->diag_host[which].clear();
-  if (which == DAV_OP_A) e->basis_order.clear();
-  std::vector<int64_t> rp;
-  if (int rc = pattern_offsets_dev(e, sc, P, BSR_WORDS, &o.bsr_rp, rp, &why)) return step(rc);
-  const int64_t lnnzb = rp[(size_t)nbl];
-  uint64_t* src = nullptr;          // source of each canonical block: input block p << 1 | mirrored
-  sc.take(&src, (size_t)lnnzb);
-  if (sc.oom || !keep(&o.bsr_col, (size_t)lnnzb) || !keep(&o.bsr_val, (size_t)(lnnzb * bb)))
-    return refuse(no_memory(std::to_string(lnnzb) + " blocks of this rank (" + std::to_string((lnnzb * (8 * bb + 12)) >> 20) + " MiB)"));
-  if (int rc = pattern_order_dev(e, sc, P, BSR_WORDS, o.bsr_rp, rp, o.bsr_col, src, &why)) return step(rc);
-  // the values: column-major per block, a mirrored block the transpose of its source
-  launch_bsr_build_gather(st, b, src, lnnzb, vals, block_layout == DAV_BSR_ROW_MAJOR ? 1 : 0, o.bsr_val);
-  // the diagonal of the whole matrix: this rank's slab to o.diag, all of it to the host copy
-  double* diag = nullptr;
-  sc.take(&diag, (size_t)n);
-  if (sc.oom) return refuse(no_memory("the diagonal"));
-  launch_bsr_build_diag(st, b, block_row_ptr, P.rp64, block_col_idx, P.ci64, vals, nb, index_base, P.dcount, P.dfirst, diag);
-  if (nloc > 0) HIPCHK(hipMemcpyAsync(o.diag, diag + r0, sizeof(double) * nloc, hipMemcpyDeviceToDevice, st));
-  std::vector<double> hdiag((size_t)n);
-  CHK(readback(st, hdiag.data(), diag, sizeof(double) * (size_t)n));
-  // ---- the work list of the block product, over the canonical offsets (as dav_set_operator_bsr builds it)
-  std::vector<CsrItem> items;
-  std::vector<CsrLong> longs;
-  int nslots = 0;
-  bsr_build_items(rp, b, items, longs, &nslots);
-  auto upload = [&](auto** dst, const auto* s, size_t count) -> int {
-    if (!keep(dst, count)) return 1;
-    if (count > 0 && hipMemcpy(*dst, s, sizeof(**dst) * count, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return 1; }
-    return 0;
-  };
-  if (upload(&o.bsr_items, items.data(), items.size()) || upload(&o.bsr_longs, longs.data(), longs.size()) ||
-      !keep(&o.bsr_part, (size_t)nslots * 1024))
-    return refuse(no_memory("the work list of " + std::to_string(lnnzb) + " blocks of this rank"));
-  HIPCHK(hipStreamSynchronize(st));                 // the caller's arrays are free again when the call returns
-  HIPCHK(hipGetLastError());
-  o.bsr_nitems = (int)items.size();
-  o.bsr_nlong = (int)longs.size();
-  o.bsr_b = b;
-  o.bsr_nnzb = lnnzb;
-  o.bsr_nbl = nbl;
-  o.bsr_grow0 = ib0 * b - r0;
-  o.storage = 0;
-  e->diag_host[which].swap(hdiag);
-  if (which == DAV_OP_A) e->basis_order.clear();
-  o.kind = DAV_KIND_BSR;
   return 0;
 }
 

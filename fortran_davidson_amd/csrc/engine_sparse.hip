@@ -1,0 +1,559 @@
+// Engine, sparse operators: a symmetric matrix in CSR or BSR form, given in host arrays (dav_set_operator_csr, dav_set_operator_bsr) or in
+// device arrays and built on the GPU (dav_set_operator_csr_dev, dav_set_operator_bsr_dev; kernels in k_csr_build.hip, k_bsr_build.hip).
+// All four entries follow one structure: the PATTERN - row_ptr and col_idx over rows or block rows - is validated; the
+// canonical order of this rank's rows is built with a PAYLOAD per column index (CSR: the value of the entry; BSR: the source of the block,
+// input position << 1 | mirrored); BSR gathers the VALUES from the sources; the DIAGONAL is summed per kind; one COMMIT step builds the
+// work list and sets the operator.  Host and device entries produce the same arrays bit for bit.
+#include "engine_internal.h"
+
+void sparse_release(E* e, OpDesc& o) {
+  SparseStore& s = o.sp;
+  if (!s.rp && !s.col && !s.val && !s.items && !s.longs && !s.part) return;
+  (void)hipStreamSynchronize(e->stream);         // applies in flight may still read the arrays
+  pool_free(s.rp); pool_free(s.col); pool_free(s.val);
+  pool_free(s.items); pool_free(s.longs); pool_free(s.part);
+  s = SparseStore();
+}
+
+namespace {
+// Work list of the block product over the canonical local rows (block rows) rp[0..nrows]: runs of at most max_rows whole rows with at most
+// chunk entries (blocks) together, and every row longer than chunk cut into chunks at multiples of chunk from its first entry (one item
+// and one partial slot each; CsrLong lists the slots of the row).  The cut depends on the row alone, so the sums do not depend on the ranks.
+void sparse_build_items(const std::vector<int64_t>& rp, int max_rows, int64_t chunk, std::vector<CsrItem>& items, std::vector<CsrLong>& longs,
+                        int* nslots) {
+  const int64_t nrows = (int64_t)rp.size() - 1;
+  CsrItem cur{0, 0, 0, 0, -1, 0};
+  int slots = 0;
+  auto flush = [&]() { if (cur.nrows > 0) items.push_back(cur); cur.nrows = 0; };
+  for (int64_t i = 0; i < nrows; ++i) {
+    const int64_t a = rp[(size_t)i], z = rp[(size_t)i + 1];
+    if (z - a > chunk) {
+      flush();
+      const int first = slots;
+      for (int64_t q = a; q < z; q += chunk) items.push_back({q, std::min(z, q + chunk), (int32_t)i, 1, slots++, 0});
+      longs.push_back({(int32_t)i, first, slots - first, 0});
+      continue;
+    }
+    if (cur.nrows > 0 && (cur.nrows == max_rows || z - cur.p0 > chunk)) flush();
+    if (cur.nrows == 0) { cur.p0 = a; cur.row = (int32_t)i; }
+    cur.p1 = z;
+    cur.nrows += 1;
+  }
+  flush();
+  *nslots = slots;
+}
+
+// ---- messages: every text exists once, composed from the nouns of the kind ---------------------------------------------------------------
+struct SparseWords { const char *rp, *ci, *row, *rows, *col, *item, *items; };
+const SparseWords CSR_WORDS{"row_ptr", "col_idx", "row", "rows", "column index", "entry", "entries"};
+const SparseWords BSR_WORDS{"block_row_ptr", "block_col_idx", "block row", "block rows", "block column", "block", "blocks"};
+
+// one call of one of the four entries
+struct Entry {
+  E* e; int which; const char* name; const SparseWords& w;
+  // a call that fails leaves the operator unset (the engine stays usable: set it again)
+  int refuse(const std::string& msg) const {
+    sparse_release(e, e->op[which]);
+    e->op[which].kind = DAV_KIND_NONE;
+    e->diag_host[which].clear();
+    if (which == DAV_OP_A) e->basis_order.clear();
+    return fail(std::string(name) + ": " + msg);
+  }
+  // the outcome of a build step: non-zero with a reason (the matrix is refused with it) or without (a HIP failure, already recorded by fail())
+  int step(int rc, const std::string& why) const { return why.empty() ? rc : refuse(why); }
+};
+
+int entry_begin(E* e, int which, const char* name) {
+  if (!e) return fail(std::string(name) + ": null engine");
+  if (which < 0 || which > 1) return fail(std::string(name) + ": bad operator id");
+  return bind(e);
+}
+
+// the scalar arguments, before anything is read, allocated or launched ("" = fine).  bsr: b and block_layout count (a CSR entry passes
+// neither); bits = {row_ptr_bits, col_bits} of a device entry, nullptr for a host entry
+std::string bad_arguments(const SparseWords& w, int64_t n, bool bsr, int b, int index_base, int triangle, int block_layout, const int* bits,
+                          const void* row_ptr) {
+  if (!bsr) {
+    if (n >= ((int64_t)1 << 31)) return "n = " + std::to_string(n) + " must be below 2^31 (int32 column indices)";
+  } else {
+    if (b < 1 || b > 16) return "block_size = " + std::to_string(b) + " must lie in 1..16";
+    if (n % b != 0) return "n = " + std::to_string(n) + " is not a multiple of block_size = " + std::to_string(b);
+    if (n / b >= ((int64_t)1 << 31)) return "n / block_size must be below 2^31 (int32 block columns)";
+  }
+  if (index_base != 0 && index_base != 1) return "index_base must be 0 or 1";
+  if (triangle != DAV_CSR_FULL && triangle != DAV_CSR_LOWER) return "triangle must be DAV_CSR_FULL or DAV_CSR_LOWER";
+  if (bsr && block_layout != DAV_BSR_ROW_MAJOR && block_layout != DAV_BSR_COL_MAJOR) return "block_layout must be DAV_BSR_ROW_MAJOR or DAV_BSR_COL_MAJOR";
+  if (bits && bits[0] != 32 && bits[0] != 64) return "row_ptr_bits must be 32 or 64";
+  if (bits && bits[1] != 32 && bits[1] != 64) return "col_bits must be 32 or 64";
+  if (!row_ptr) return std::string("null ") + w.rp;
+  return "";
+}
+
+std::string msg_first_offset(const SparseWords& w, int64_t rp0, int base) {
+  return std::string(w.rp) + "[0] = " + std::to_string(rp0) + " must equal the index base " + std::to_string(base);
+}
+std::string msg_decreases(const SparseWords& w, int64_t row) { return std::string(w.rp) + " decreases at " + w.row + " " + std::to_string(row); }
+std::string msg_null_entries(const SparseWords& w) { return std::string("null ") + w.ci + " or vals"; }
+// entry p of row i (both from 0) carries the caller's column c: outside the matrix, or above the diagonal of a lower triangle
+std::string msg_bad_entry(const SparseWords& w, int64_t n, int base, int64_t p, int64_t i, int64_t c) {
+  if (c - base < 0 || c - base >= n)
+    return std::string(w.col) + " " + std::to_string(c) + " out of range at " + w.item + " " + std::to_string(p + base) + " (" + w.row + " " +
+           std::to_string(i + base) + ")";
+  return std::string(w.item) + " (" + std::to_string(i + base) + ", " + std::to_string(c) + ") lies above the diagonal of a DAV_CSR_LOWER matrix";
+}
+std::string no_memory(const std::string& what) { return "device memory for " + what + " could not be allocated"; }
+// (the estimates of the entries differ: 12 lnnz + 8 nloc bytes for CSR, 8 b^2 + 4 per block from host arrays, 8 b^2 + 12 from device arrays)
+std::string stored(const SparseWords& w, int64_t count, int64_t bytes) {
+  return std::to_string(count) + " " + w.items + " of this rank (" + std::to_string(bytes >> 20) + " MiB)";
+}
+std::string work_list(const SparseWords& w, int64_t count) { return "the work list of " + std::to_string(count) + " " + w.items + " of this rank"; }
+
+// ---- storage that stays with the operator -------------------------------------------------------------------------------------------------
+template <class T> bool keep(T** p, size_t count) {
+  if (pool_malloc(p, sizeof(T) * std::max<size_t>(count, 1)) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
+  return true;
+}
+template <class T> bool upload(T** dst, const std::vector<T>& src) {
+  if (!keep(dst, src.size())) return false;
+  if (!src.empty() && hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return true;
+}
+
+int readback(hipStream_t st, void* dst, const void* src, size_t bytes) {
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+// The last step of every entry, with rp / col / val of the store in place: the diagonal (of the whole matrix: diag on the host, or diag_dev
+// on the device, read back into diag), the work list over the canonical offsets rp, and the operator's description.  oom: the entry's
+// words for a failed allocation.
+int sparse_commit(const Entry& en, int kind, int b, int64_t grow0, const std::vector<int64_t>& rp, std::vector<double>& diag, const double* diag_dev,
+                  const std::string& oom) {
+  E* e = en.e;
+  OpDesc& o = e->op[en.which];
+  SparseStore& s = o.sp;
+  if (diag_dev) {
+    if (e->nloc > 0) HIPCHK(hipMemcpyAsync(o.diag, diag_dev + e->row0, sizeof(double) * e->nloc, hipMemcpyDeviceToDevice, e->stream));
+    diag.resize((size_t)e->n);
+    CHK(readback(e->stream, diag.data(), diag_dev, sizeof(double) * (size_t)e->n));
+  } else if (e->nloc > 0) {
+    HIPCHK(hipMemcpy(o.diag, diag.data() + e->row0, sizeof(double) * e->nloc, hipMemcpyHostToDevice));
+  }
+  const bool csr = kind == DAV_KIND_CSR;
+  std::vector<CsrItem> items;
+  std::vector<CsrLong> longs;
+  int nslots = 0;
+  sparse_build_items(rp, csr ? CSR_ROWS : std::max(1, BSR_ROWS / b), csr ? CSR_CHUNK : BSR_CHUNK, items, longs, &nslots);
+  if (!upload(&s.items, items) || !upload(&s.longs, longs) || !keep(&s.part, (size_t)nslots * (csr ? 64 : 1024))) return en.refuse(oom);
+  HIPCHK(hipStreamSynchronize(e->stream));          // the caller's arrays are free again when the call returns
+  HIPCHK(hipGetLastError());
+  s.nitems = (int)items.size();
+  s.nlong = (int)longs.size();
+  s.nnz = rp.back();
+  s.nrows = (int64_t)rp.size() - 1;
+  s.b = b;
+  s.grow0 = grow0;
+  o.storage = 0;
+  e->diag_host[en.which].swap(diag);
+  if (en.which == DAV_OP_A) e->basis_order.clear();
+  o.kind = kind;
+  return 0;
+}
+
+// the block rows [ib0, ib0 + nbl) that touch this rank's slab [row0, row0 + nloc)
+void local_block_rows(const E* e, int b, int64_t* ib0, int64_t* nbl) {
+  *ib0 = e->nloc > 0 ? e->row0 / b : 0;
+  *nbl = e->nloc > 0 ? (e->row0 + e->nloc + b - 1) / b - *ib0 : 0;
+}
+
+// ---- host arrays ------------------------------------------------------------------------------------------------------------------------
+// the caller's pattern: n rows (block rows) of the whole matrix, of which [r0, r0 + nloc) are this rank's
+struct HostPattern {
+  const int64_t* row_ptr; const int32_t* col_idx;
+  int64_t n, r0, nloc;
+  int base; bool lower;
+};
+
+// row_ptr first, then the entries: the first offending position
+bool pattern_validate(const HostPattern& P, const void* vals, const SparseWords& w, std::string* why) {
+  const int64_t* g = P.row_ptr;
+  if (g[0] != P.base) { *why = msg_first_offset(w, g[0], P.base); return false; }
+  for (int64_t i = 0; i < P.n; ++i)
+    if (g[i + 1] < g[i]) { *why = msg_decreases(w, i + P.base); return false; }
+  if (g[P.n] - P.base > 0 && (!P.col_idx || !vals)) { *why = msg_null_entries(w); return false; }
+  for (int64_t i = 0; i < P.n; ++i)
+    for (int64_t p = g[i] - P.base; p < g[i + 1] - P.base; ++p) {
+      const int64_t j = (int64_t)P.col_idx[p] - P.base;
+      if (j < 0 || j >= P.n || (P.lower && j > i)) { *why = msg_bad_entry(w, P.n, P.base, p, i, P.col_idx[p]); return false; }
+    }
+  return true;
+}
+
+// Canonical rows of this rank: own entries in input order, then (lower) the mirrored strict lower entries in the order of their source rows;
+// stable sort by column (duplicates stay separate terms, in that order).  payload(p, mirrored) is what travels with the column of input entry p.
+template <class V, class F>
+void pattern_order(const HostPattern& P, F payload, std::vector<int64_t>& rp, std::vector<int32_t>& lcol, std::vector<V>& lpay) {
+  const int64_t* g = P.row_ptr;
+  const int64_t r0 = P.r0, nloc = P.nloc, base = P.base;
+  auto each_mirrored = [&](auto&& f) {         // f(i, j, p): entry p of row i lies below the diagonal and its mirror image in local row j
+    if (!P.lower) return;
+    for (int64_t i = 0; i < P.n; ++i)
+      for (int64_t p = g[i] - base; p < g[i + 1] - base; ++p) {
+        const int64_t j = (int64_t)P.col_idx[p] - base;
+        if (j < i && j >= r0 && j < r0 + nloc) f(i, j, p);
+      }
+  };
+  rp.assign((size_t)nloc + 1, 0);
+  for (int64_t i = r0; i < r0 + nloc; ++i) rp[(size_t)(i - r0) + 1] = g[i + 1] - g[i];
+  each_mirrored([&](int64_t, int64_t j, int64_t) { rp[(size_t)(j - r0) + 1] += 1; });
+  for (int64_t i = 0; i < nloc; ++i) rp[(size_t)i + 1] += rp[(size_t)i];
+  lcol.resize((size_t)rp[(size_t)nloc]);
+  lpay.resize((size_t)rp[(size_t)nloc]);
+  std::vector<int64_t> pos(rp.begin(), rp.end() - 1);
+  for (int64_t i = r0; i < r0 + nloc; ++i)
+    for (int64_t p = g[i] - base; p < g[i + 1] - base; ++p) {
+      const size_t q = (size_t)pos[(size_t)(i - r0)]++;
+      lcol[q] = (int32_t)(P.col_idx[p] - base);
+      lpay[q] = payload(p, false);
+    }
+  each_mirrored([&](int64_t i, int64_t j, int64_t p) {
+    const size_t q = (size_t)pos[(size_t)(j - r0)]++;
+    lcol[q] = (int32_t)i;
+    lpay[q] = payload(p, true);
+  });
+  std::vector<std::pair<int32_t, V>> row;
+  for (int64_t i = 0; i < nloc; ++i) {
+    const size_t a = (size_t)rp[(size_t)i], z = (size_t)rp[(size_t)i + 1];
+    if (std::is_sorted(lcol.begin() + a, lcol.begin() + z)) continue;
+    row.clear();
+    for (size_t q = a; q < z; ++q) row.push_back({lcol[q], lpay[q]});
+    std::stable_sort(row.begin(), row.end(), [](const std::pair<int32_t, V>& x, const std::pair<int32_t, V>& y) { return x.first < y.first; });
+    for (size_t q = a; q < z; ++q) { lcol[q] = row[q - a].first; lpay[q] = row[q - a].second; }
+  }
+}
+
+// the canonical arrays to the device (the engine's allocator; released when the operator is set again and at dav_destroy), then the commit
+int commit_host(const Entry& en, int kind, int b, int64_t grow0, const std::vector<int64_t>& rp, const std::vector<int32_t>& lcol,
+                const std::vector<double>& lval, std::vector<double>& diag, int64_t bytes) {
+  CHK(operator_goes(en.e, en.which, true));
+  SparseStore& s = en.e->op[en.which].sp;
+  const std::string oom = no_memory(stored(en.w, rp.back(), bytes));
+  if (!upload(&s.rp, rp) || !upload(&s.col, lcol) || !upload(&s.val, lval)) return en.refuse(oom);
+  return sparse_commit(en, kind, b, grow0, rp, diag, nullptr, oom);
+}
+}  // namespace
+
+extern "C" int dav_set_operator_csr(dav_handle_t e, int which, const int64_t* row_ptr, const int32_t* col_idx, const double* vals,
+                                    int index_base, int triangle) {
+  CHK(entry_begin(e, which, "dav_set_operator_csr"));
+  const Entry en{e, which, "dav_set_operator_csr", CSR_WORDS};
+  const int64_t n = e->n;
+  std::string why = bad_arguments(en.w, n, false, 0, index_base, triangle, 0, nullptr, row_ptr);
+  if (!why.empty()) return en.refuse(why);
+  const HostPattern P{row_ptr, col_idx, n, e->row0, e->nloc, index_base, triangle == DAV_CSR_LOWER};
+  if (!pattern_validate(P, vals, en.w, &why)) return en.refuse(why);
+  std::vector<int64_t> rp;
+  std::vector<int32_t> lcol;
+  std::vector<double> lval;
+  pattern_order(P, [&](int64_t p, bool) { return vals[p]; }, rp, lcol, lval);
+  // the diagonal of the whole matrix, from the global arrays: duplicates summed in input order, a missing entry counts as 0
+  std::vector<double> diag((size_t)n, 0.0);
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t p = row_ptr[i] - index_base; p < row_ptr[i + 1] - index_base; ++p)
+      if ((int64_t)col_idx[p] - index_base == i) diag[(size_t)i] += vals[p];
+  return commit_host(en, DAV_KIND_CSR, 1, 0, rp, lcol, lval, diag, 12 * rp.back() + 8 * e->nloc);
+}
+
+extern "C" int dav_set_operator_bsr(dav_handle_t e, int which, int block_size, const int64_t* block_row_ptr, const int32_t* block_col_idx,
+                                    const double* vals, int index_base, int triangle, int block_layout) {
+  CHK(entry_begin(e, which, "dav_set_operator_bsr"));
+  const Entry en{e, which, "dav_set_operator_bsr", BSR_WORDS};
+  const int64_t n = e->n;
+  const int b = block_size;
+  std::string why = bad_arguments(en.w, n, true, b, index_base, triangle, block_layout, nullptr, block_row_ptr);
+  if (!why.empty()) return en.refuse(why);
+  const int64_t nb = n / b, bb = (int64_t)b * b;
+  int64_t ib0, nbl;
+  local_block_rows(e, b, &ib0, &nbl);
+  const HostPattern P{block_row_ptr, block_col_idx, nb, ib0, nbl, index_base, triangle == DAV_CSR_LOWER};
+  if (!pattern_validate(P, vals, en.w, &why)) return en.refuse(why);
+  std::vector<int64_t> rp;
+  std::vector<int32_t> lcol;
+  std::vector<uint64_t> src;        // source of each canonical block: input block p << 1 | mirrored
+  pattern_order(P, [](int64_t p, bool mirrored) { return (uint64_t)p << 1 | (uint64_t)mirrored; }, rp, lcol, src);
+  // entry (m, k) of input block p in the caller's layout
+  const bool rowmaj = block_layout == DAV_BSR_ROW_MAJOR;
+  auto entry = [&](int64_t p, int m, int k) { return vals[p * bb + (rowmaj ? (int64_t)m * b + k : (int64_t)k * b + m)]; };
+  // values column-major per block: lval[q * b * b + k * b + m] = A_q[m][k] (a mirrored block is the transpose of its source)
+  std::vector<double> lval(src.size() * (size_t)bb);
+  for (size_t q = 0; q < src.size(); ++q) {
+    double* d = lval.data() + q * (size_t)bb;
+    const int64_t p = (int64_t)(src[q] >> 1);
+    const bool tr = src[q] & 1;
+    for (int k = 0; k < b; ++k)
+      for (int m = 0; m < b; ++m) d[(int64_t)k * b + m] = tr ? entry(p, k, m) : entry(p, m, k);
+  }
+  // the diagonal of the whole matrix, from the diagonal blocks of the global arrays (duplicates summed in input order)
+  std::vector<double> diag((size_t)n, 0.0);
+  for (int64_t I = 0; I < nb; ++I)
+    for (int64_t p = block_row_ptr[I] - index_base; p < block_row_ptr[I + 1] - index_base; ++p)
+      if ((int64_t)block_col_idx[p] - index_base == I)
+        for (int m = 0; m < b; ++m) diag[(size_t)(I * b + m)] += entry(p, m, m);
+  return commit_host(en, DAV_KIND_BSR, b, ib0 * b - e->row0, rp, lcol, lval, diag, rp.back() * (8 * bb + 4));
+}
+
+// ---- device arrays: the same steps on the GPU --------------------------------------------------------------------------------------------
+// Both entries build the index level with the kernels of k_csr_build.hip - over the rows of a CSR matrix with the value of an entry as
+// payload, over the block rows of a BSR matrix with the source of a block.  Each step returns 0, or non-zero with *why set (the caller
+// refuses the matrix with that message) or *why empty (a HIP failure, already recorded by fail()).
+namespace {
+// a caller's pointer: device memory of this engine's device, large enough where the runtime can tell (before any launch)
+bool device_array(E* e, const void* p, const char* name, size_t bytes, std::string* why) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    *why = std::string(name) + " is not device memory (the runtime does not know the pointer)";
+    return false;
+  }
+  if (at.type != hipMemoryTypeDevice) { *why = std::string(name) + " is not device memory (host, pinned or managed)"; return false; }
+  if (at.device != e->device) {
+    *why = std::string(name) + " lies on device " + std::to_string(at.device) + ", the engine on device " + std::to_string(e->device);
+    return false;
+  }
+  hipDeviceptr_t lo = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&lo, &size, (hipDeviceptr_t)p) == hipSuccess) {
+    if ((const char*)p + bytes > (const char*)lo + size)
+      { *why = std::string(name) + " holds fewer than the " + std::to_string(bytes) + " bytes the matrix needs"; return false; }
+  } else {
+    (void)hipGetLastError();
+  }
+  return true;
+}
+
+// scratch of a build: released on every way out, after the stream has finished with it
+struct BuildScratch {
+  hipStream_t st;
+  std::vector<void*> held;
+  bool oom = false;
+  explicit BuildScratch(hipStream_t s) : st(s) {}
+  BuildScratch(const BuildScratch&) = delete;
+  ~BuildScratch() { (void)hipStreamSynchronize(st); for (void* p : held) pool_free(p); }
+  template <class T> void take(T** p, size_t count) {
+    *p = nullptr;
+    if (oom) return;
+    if (pool_malloc(p, sizeof(T) * std::max<size_t>(count, 1)) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; oom = true; return; }
+    held.push_back((void*)*p);
+  }
+};
+
+// the caller's pattern: n rows (block rows) of the whole matrix, of which [r0, r0 + nloc) are this rank's; item_bytes of vals per entry
+struct DevPattern {
+  const void* row_ptr; int rp64;
+  const void* col_idx; int ci64;
+  const double* vals; size_t item_bytes;
+  int64_t n, r0, nloc;
+  int base; bool lower;
+  // set by pattern_validate_dev
+  int64_t nnz = 0;
+  int32_t* mcount = nullptr;               // mirrored entries per local row; later the slots taken by the scatter
+  uint32_t* dcount = nullptr;              // diagonal entries per row of the whole matrix
+  unsigned long long* dfirst = nullptr;    // the first of them
+};
+
+// the pointers, then the rules of pattern_validate on the device: row_ptr first, then the entries (the first offending position, as the host
+// loop names it)
+int pattern_validate_dev(E* e, BuildScratch& sc, DevPattern& P, const SparseWords& w, std::string* why) {
+  hipStream_t st = e->stream;
+  const size_t rpw = P.rp64 ? 8 : 4, ciw = P.ci64 ? 8 : 4;
+  const int64_t n = P.n;
+  if (!device_array(e, P.row_ptr, w.rp, rpw * (size_t)(n + 1), why)) return 1;
+  if (P.col_idx && !device_array(e, P.col_idx, w.ci, 0, why)) return 1;
+  if (P.vals && !device_array(e, P.vals, "vals", 0, why)) return 1;
+  unsigned long long* info = nullptr;
+  sc.take(&info, 4);
+  if (sc.oom) { *why = no_memory("the validation"); return 1; }
+  HIPCHK(hipMemsetAsync(info, 0xff, sizeof(unsigned long long) * 4, st));
+  launch_csr_build_rows(st, P.row_ptr, P.rp64, n, info);
+  unsigned long long hinfo[4];
+  CHK(readback(st, hinfo, info, sizeof(hinfo)));
+  const int64_t rp0 = (int64_t)hinfo[1], rpn = (int64_t)hinfo[2];
+  if (rp0 != P.base) { *why = msg_first_offset(w, rp0, P.base); return 1; }
+  if (hinfo[0] != ~0ull) { *why = msg_decreases(w, (int64_t)hinfo[0] + P.base); return 1; }
+  P.nnz = rpn - P.base;
+  if (P.nnz > 0 && (!P.col_idx || !P.vals)) { *why = msg_null_entries(w); return 1; }
+  if (hinfo[3] != ~0ull) {
+    *why = std::string(w.row) + " " + std::to_string((int64_t)hinfo[3] + P.base) + " holds 2^32 " + w.items + " or more";
+    return 1;
+  }
+  if (P.nnz > 0 && (!device_array(e, P.col_idx, w.ci, ciw * (size_t)P.nnz, why) || !device_array(e, P.vals, "vals", P.item_bytes * (size_t)P.nnz, why)))
+    return 1;
+  int64_t* locate = nullptr;
+  sc.take(&P.mcount, (size_t)P.nloc); sc.take(&P.dcount, (size_t)n); sc.take(&P.dfirst, (size_t)n); sc.take(&locate, 2);
+  if (sc.oom) { *why = no_memory("the validation of " + std::to_string(n) + " " + w.rows); return 1; }
+  HIPCHK(hipMemsetAsync(P.mcount, 0, sizeof(int32_t) * std::max<int64_t>(P.nloc, 1), st));
+  HIPCHK(hipMemsetAsync(P.dcount, 0, sizeof(uint32_t) * std::max<int64_t>(n, 1), st));
+  HIPCHK(hipMemsetAsync(P.dfirst, 0xff, sizeof(unsigned long long) * std::max<int64_t>(n, 1), st));
+  launch_csr_build_check(st, P.row_ptr, P.rp64, P.col_idx, P.ci64, n, P.nnz, P.base, P.lower ? 1 : 0, P.r0, P.nloc, info + 3, P.mcount, P.dcount,
+                         P.dfirst);
+  CHK(readback(st, hinfo, info, sizeof(hinfo)));
+  if (hinfo[3] != ~0ull) {
+    const int64_t p = (int64_t)hinfo[3];
+    launch_csr_build_locate(st, P.row_ptr, P.rp64, P.col_idx, P.ci64, n, P.base, p, locate);
+    int64_t loc[2];
+    CHK(readback(st, loc, locate, sizeof(loc)));
+    *why = msg_bad_entry(w, n, P.base, p, loc[0], loc[1]);
+    return 1;
+  }
+  return 0;
+}
+
+// *lrp (kept with the operator) and rp = the int64 offsets of the canonical local rows
+int pattern_offsets_dev(E* e, BuildScratch& sc, const DevPattern& P, const SparseWords& w, int64_t** lrp, std::vector<int64_t>& rp, std::string* why) {
+  int64_t* tile_sums = nullptr;
+  sc.take(&tile_sums, (size_t)csr_build_scan_tiles(P.nloc));
+  if (sc.oom || !keep(lrp, (size_t)P.nloc + 1)) { *why = no_memory(std::string("the ") + w.row + " offsets of this rank"); return 1; }
+  launch_csr_build_offsets(e->stream, P.row_ptr, P.rp64, P.r0, P.nloc, P.mcount, *lrp, tile_sums);
+  rp.assign((size_t)P.nloc + 1, 0);
+  CHK(readback(e->stream, rp.data(), *lrp, sizeof(int64_t) * rp.size()));
+  return 0;
+}
+
+void pattern_scatter(hipStream_t st, const DevPattern& P, int64_t p_lo, int64_t p_hi, const int64_t* lrp, int32_t* ocol, double* oval, uint32_t* tie) {
+  launch_csr_build_scatter(st, P.row_ptr, P.rp64, P.col_idx, P.ci64, P.vals, P.n, p_lo, p_hi, P.base, P.lower ? 1 : 0, P.r0, P.nloc, lrp, P.mcount,
+                           ocol, oval, tie);
+}
+void pattern_scatter(hipStream_t st, const DevPattern& P, int64_t p_lo, int64_t p_hi, const int64_t* lrp, int32_t* ocol, uint64_t* osrc, uint32_t* tie) {
+  launch_csr_build_scatter(st, P.row_ptr, P.rp64, P.col_idx, P.ci64, P.n, p_lo, p_hi, P.base, P.lower ? 1 : 0, P.r0, P.nloc, lrp, P.mcount, ocol,
+                           osrc, tie);
+}
+
+// the canonical order: columns to ocol and payloads (values / block sources) to oval, every local row in the order of pattern_order
+template <class V>
+int pattern_order_dev(E* e, BuildScratch& sc, const DevPattern& P, const SparseWords& w, const int64_t* lrp, const std::vector<int64_t>& rp,
+                      int32_t* ocol, V* oval, std::string* why) {
+  hipStream_t st = e->stream;
+  const int64_t nloc = P.nloc, lnnz = rp[(size_t)nloc];
+  const size_t rpw = P.rp64 ? 8 : 4;
+  uint32_t* tie = nullptr;
+  uint8_t* flag = nullptr;
+  if (P.lower) sc.take(&tie, (size_t)lnnz);
+  sc.take(&flag, (size_t)nloc);
+  if (sc.oom) { *why = no_memory("sorting " + std::to_string(lnnz) + " " + w.items); return 1; }
+  // own entries: those of the local rows; mirrored entries (lower): any row of the matrix may send some
+  int64_t p_lo = 0, p_hi = P.nnz;
+  if (!P.lower && nloc > 0) {
+    int64_t ends[2] = {0, 0};
+    for (int s = 0; s < 2; ++s) {
+      const char* src = (const char*)P.row_ptr + rpw * (size_t)(s == 0 ? P.r0 : P.r0 + nloc);
+      CHK(readback(st, &ends[s], src, rpw));
+      if (!P.rp64) ends[s] = (int64_t)(int32_t)ends[s];
+    }
+    p_lo = ends[0] - P.base;
+    p_hi = ends[1] - P.base;
+  }
+  HIPCHK(hipMemsetAsync(P.mcount, 0, sizeof(int32_t) * std::max<int64_t>(nloc, 1), st));
+  HIPCHK(hipMemsetAsync(flag, 0, std::max<int64_t>(nloc, 1), st));
+  if (nloc > 0) pattern_scatter(st, P, p_lo, p_hi, lrp, ocol, oval, tie);
+  launch_csr_build_flag(st, lrp, nloc, lnnz, ocol, tie, flag);
+  launch_csr_build_sort_rows(st, lrp, nloc, flag, ocol, oval, tie);
+  // rows longer than one LDS tile that are out of order: tiles sorted, then merged (one row at a time)
+  const int64_t tile = csr_build_sort_tile();
+  int64_t longest = 0;
+  std::vector<int64_t> cand, longs_unsorted;
+  for (int64_t i = 0; i < nloc; ++i)
+    if (rp[(size_t)i + 1] - rp[(size_t)i] > tile) cand.push_back(i);
+  if (!cand.empty()) {
+    std::vector<uint8_t> hflag((size_t)nloc);
+    CHK(readback(st, hflag.data(), flag, (size_t)nloc));
+    for (int64_t i : cand)
+      if (hflag[(size_t)i]) { longs_unsorted.push_back(i); longest = std::max(longest, rp[(size_t)i + 1] - rp[(size_t)i]); }
+  }
+  if (!longs_unsorted.empty()) {
+    uint64_t *k0 = nullptr, *k1 = nullptr;
+    V *v0 = nullptr, *v1 = nullptr;
+    sc.take(&k0, (size_t)longest); sc.take(&k1, (size_t)longest); sc.take(&v0, (size_t)longest); sc.take(&v1, (size_t)longest);
+    if (sc.oom) { *why = no_memory(std::string("sorting a ") + w.row + " of " + std::to_string(longest) + " " + w.items); return 1; }
+    for (int64_t i : longs_unsorted)
+      launch_csr_build_sort_long(st, rp[(size_t)i], rp[(size_t)i + 1] - rp[(size_t)i], ocol, oval, tie, k0, v0, k1, v1);
+  }
+  return 0;
+}
+
+// a valid pattern: the previous operator goes, and the canonical offsets of this rank (s.rp, and rp on the host) are built in its place
+int pattern_begin_dev(const Entry& en, BuildScratch& sc, DevPattern& P, std::vector<int64_t>& rp, std::string* why) {
+  if (int rc = pattern_validate_dev(en.e, sc, P, en.w, why)) return rc;
+  CHK(operator_goes(en.e, en.which, true));
+  return pattern_offsets_dev(en.e, sc, P, en.w, &en.e->op[en.which].sp.rp, rp, why);
+}
+
+// the diagonal of the whole matrix on the device
+double* diag_scratch(BuildScratch& sc, int64_t n, std::string* why) {
+  double* d = nullptr;
+  sc.take(&d, (size_t)n);
+  if (sc.oom) *why = no_memory("the diagonal");
+  return d;
+}
+}  // namespace
+
+// Validation, canonical rows, diagonal and storage equal those of dav_set_operator_csr bit for bit; only the work list is built on the
+// host, over the canonical row offsets read back (8 (nloc + 1) bytes).
+extern "C" int dav_set_operator_csr_dev(dav_handle_t e, int which, const void* row_ptr, int row_ptr_bits, const void* col_idx, int col_bits,
+                                        const double* vals, int index_base, int triangle) {
+  CHK(entry_begin(e, which, "dav_set_operator_csr_dev"));
+  const Entry en{e, which, "dav_set_operator_csr_dev", CSR_WORDS};
+  const int bits[2] = {row_ptr_bits, col_bits};
+  std::string why = bad_arguments(en.w, e->n, false, 0, index_base, triangle, 0, bits, row_ptr);
+  if (!why.empty()) return en.refuse(why);
+  BuildScratch sc(e->stream);
+  DevPattern P{row_ptr, row_ptr_bits == 64, col_idx, col_bits == 64, vals, 8, e->n, e->row0, e->nloc, index_base, triangle == DAV_CSR_LOWER};
+  std::vector<int64_t> rp;
+  if (int rc = pattern_begin_dev(en, sc, P, rp, &why)) return en.step(rc, why);
+  SparseStore& s = e->op[which].sp;
+  const int64_t lnnz = rp.back();
+  if (!keep(&s.col, (size_t)lnnz) || !keep(&s.val, (size_t)lnnz)) return en.refuse(no_memory(stored(en.w, lnnz, 12 * lnnz + 8 * e->nloc)));
+  if (int rc = pattern_order_dev(e, sc, P, en.w, s.rp, rp, s.col, s.val, &why)) return en.step(rc, why);
+  double* diag = diag_scratch(sc, e->n, &why);
+  if (!diag) return en.refuse(why);
+  launch_csr_build_diag(e->stream, row_ptr, P.rp64, col_idx, P.ci64, vals, e->n, index_base, P.dcount, P.dfirst, diag);
+  std::vector<double> hdiag;
+  return sparse_commit(en, DAV_KIND_CSR, 1, 0, rp, hdiag, diag, no_memory(work_list(en.w, lnnz)));
+}
+
+// The index level is the CSR device build over the n / b block rows, local block rows = those that touch the slab, with the SOURCE of a
+// block (input position, mirrored or not) as payload; the values then move once (launch_bsr_build_gather).  Validation, canonical block
+// rows, values, diagonal and work list equal those of dav_set_operator_bsr bit for bit.
+extern "C" int dav_set_operator_bsr_dev(dav_handle_t e, int which, int block_size, const void* block_row_ptr, int row_ptr_bits,
+                                        const void* block_col_idx, int col_bits, const double* vals, int index_base, int triangle,
+                                        int block_layout) {
+  CHK(entry_begin(e, which, "dav_set_operator_bsr_dev"));
+  const Entry en{e, which, "dav_set_operator_bsr_dev", BSR_WORDS};
+  const int64_t n = e->n;
+  const int b = block_size, bits[2] = {row_ptr_bits, col_bits};
+  std::string why = bad_arguments(en.w, n, true, b, index_base, triangle, block_layout, bits, block_row_ptr);
+  if (!why.empty()) return en.refuse(why);
+  const int64_t nb = n / b, bb = (int64_t)b * b;
+  int64_t ib0, nbl;
+  local_block_rows(e, b, &ib0, &nbl);
+  BuildScratch sc(e->stream);
+  DevPattern P{block_row_ptr, row_ptr_bits == 64, block_col_idx, col_bits == 64, vals, 8 * (size_t)bb, nb, ib0, nbl, index_base,
+               triangle == DAV_CSR_LOWER};
+  std::vector<int64_t> rp;
+  if (int rc = pattern_begin_dev(en, sc, P, rp, &why)) return en.step(rc, why);
+  SparseStore& s = e->op[which].sp;
+  const int64_t lnnzb = rp.back();
+  uint64_t* src = nullptr;          // source of each canonical block: input block p << 1 | mirrored
+  sc.take(&src, (size_t)lnnzb);
+  if (sc.oom || !keep(&s.col, (size_t)lnnzb) || !keep(&s.val, (size_t)(lnnzb * bb)))
+    return en.refuse(no_memory(stored(en.w, lnnzb, lnnzb * (8 * bb + 12))));
+  if (int rc = pattern_order_dev(e, sc, P, en.w, s.rp, rp, s.col, src, &why)) return en.step(rc, why);
+  // the values: column-major per block, a mirrored block the transpose of its source
+  launch_bsr_build_gather(e->stream, b, src, lnnzb, vals, block_layout == DAV_BSR_ROW_MAJOR ? 1 : 0, s.val);
+  double* diag = diag_scratch(sc, n, &why);
+  if (!diag) return en.refuse(why);
+  launch_bsr_build_diag(e->stream, b, block_row_ptr, P.rp64, block_col_idx, P.ci64, vals, nb, index_base, P.dcount, P.dfirst, diag);
+  std::vector<double> hdiag;
+  return sparse_commit(en, DAV_KIND_BSR, b, ib0 * b - e->row0, rp, hdiag, diag, no_memory(work_list(en.w, lnnzb)));
+}

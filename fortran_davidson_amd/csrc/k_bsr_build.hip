@@ -1,4 +1,4 @@
-// Device build of a BSR operator from the caller's device arrays (dav_set_operator_bsr_dev, engine_operators.hip): the values.
+// Device build of a BSR operator from the caller's device arrays (dav_set_operator_bsr_dev, engine_sparse.hip): the values.
 //
 // The index level of a BSR matrix is a CSR pattern over its n / b block rows and is built by the kernels of k_csr_build.hip, which carry
 // the SOURCE of every block - input position p and whether the block is mirrored, src = p << 1 | tr - to its canonical place q.  Here the

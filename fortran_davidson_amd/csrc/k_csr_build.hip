@@ -1,4 +1,4 @@
-// Device build of a CSR operator from the caller's device arrays (dav_set_operator_csr_dev, engine_operators.hip).
+// Device build of a CSR operator from the caller's device arrays (dav_set_operator_csr_dev, engine_sparse.hip).
 //
 // The result is the canonical storage of the host entry, bit for bit: this rank's rows, own entries first, with DAV_CSR_LOWER the
 // mirrored strict lower entries, each row ordered by the key (column, position p in the caller's arrays).  Columns are below 2^31 and a

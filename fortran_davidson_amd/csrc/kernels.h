@@ -177,7 +177,7 @@ void launch_chunk_to_panel(hipStream_t st, const double* src, int64_t lds, int64
                            bool accumulate = false);
 
 // ---- K1c: CSR block product (k_spmm.hip) ----------------------------------------------------------------------------------------------
-// Y[rows of this rank, 0:kk] = A_csr * X.  Work list built on the host (engine_operators.hip: csr_build_items), one WAVE per item: a run
+// Y[rows of this rank, 0:kk] = A_csr * X.  Work list built on the host (engine_sparse.hip: sparse_build_items), one WAVE per item: a run
 // of at most CSR_ROWS consecutive whole rows with at most CSR_CHUNK entries together (slot < 0: written to the panel), or one chunk
 // of CSR_CHUNK entries of a longer row (slot >= 0: the partial row goes to part[slot][0:64]; launch_spmm_csr_finish adds a row's
 // chunks in chunk order).  Every row's sum depends only on its canonical entries, CSR_CHUNK and the launch's column groups.
@@ -253,7 +253,7 @@ void launch_bsr_build_diag(hipStream_t st, int bs, const void* rp, int rp64, con
 
 // ---- K1d: BSR block product on the matrix cores (k_bsrmm.hip) ------------------------------------------------------------------------
 // Y[rows of this rank, 0:kk] = A_bsr * X, uniform block size 1 <= b <= 16, blocks column-major on the device.  Work list built on the
-// host (engine_operators.hip: bsr_build_items) in the CSR item types over LOCAL block rows: a run of whole block rows of at most BSR_ROWS
+// host (engine_sparse.hip: sparse_build_items) in the CSR item types over LOCAL block rows: a run of whole block rows of at most BSR_ROWS
 // matrix rows and BSR_CHUNK blocks together (slot < 0), or one chunk of BSR_CHUNK blocks of a longer block row (slot >= 0: the partial
 // block row goes to part[slot][16][64]; launch_spmm_bsr_finish adds a block row's chunks in chunk order).  The rows written are the
 // local rows [0, nloc) of the block rows; the first row of local block row 0 is local row grow0 (<= 0).
