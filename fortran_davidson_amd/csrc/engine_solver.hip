@@ -602,6 +602,10 @@ extern "C" int dav_rr_ritz(dav_handle_t e, int m, int ncorr, int lowest, int met
   CHK(timed_end(e, slot));
   double info = 0.0;
   CHK(ritz_impl(e, m, ncorr, lowest, nullptr, 0, nullptr, method, resnorm, C, ldc, G, ldg, theta_out, &info));
+  if (info == (double)EIG_INFO_NOT_FINITE) return fail("dav_rr_ritz: projected matrix is not finite");
+  if (info == (double)EIG_INFO_NOT_CONVERGED)
+    return fail("dav_rr_ritz: the eigensolver of the projected problem (order " + std::to_string(m) + ") did not converge in " +
+                std::to_string(EIG_MAX_SWEEPS) + " sweeps");
   if (info < 0.0) return fail("dav_rr_ritz: the projected overlap matrix is not positive definite (pivot " + std::to_string((int)-info) + ")");
   if (sweeps_out) *sweeps_out = (int)info;
   return 0;

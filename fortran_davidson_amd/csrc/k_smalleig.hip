@@ -10,11 +10,25 @@
 // per step (two barrier-separated phases: rotation angles, then every 2 x 2 block of A updated from both sides at once),
 // m - 1 steps per sweep, until a whole sweep finds no |a_pq| > 1e-16 sqrt(|a_pp a_qq|); the projected matrices
 // of a Davidson basis are close to diagonal (after a restart exactly diagonal), so 3-6 sweeps suffice.  The symmetric matrix lives in LDS (column-major, odd
-// stride); the accumulated rotations too when both fit (m <= 96), else in global memory (L2).  Eigenvalues leave
-// ascending (ties by index), eigenvectors in the matching order.  One workgroup: the order is at most 128, the sweeps
-// are latency (barrier) bound, not throughput bound - measured against the host in docs/history/DESIGN_rounds_1_to_5.md section 10.
+// stride); the accumulated rotations too when both fit (2 (m|1) m doubles <= 150 KiB: m <= 97), else in global memory
+// (L2).  Eigenvalues leave ascending (ties by index), eigenvectors in the matching order.  One workgroup: the order is at
+// most 128, the sweeps are latency (barrier) bound, not throughput bound - measured against the host in
+// docs/history/DESIGN_rounds_1_to_5.md section 10.
+//
+// The two triangles of A are updated by different threads with differently associated products, so they drift apart by
+// rounding: eps |A| in the first sweeps, while the entries are still large.  The rotations are computed from the upper
+// triangle; what the lower one carries beyond it is never annihilated and leaks back through every 2 x 2 block that
+// straddles the diagonal.  Between numerically zero eigenvalues (a rank-deficient H: the eps |A| drift is as large as the
+// entries themselves) the iteration then never meets its criterion.  So after every sweep the upper triangle is copied
+// over the lower one: the drift of ONE sweep is relative to the entries of that sweep and harmless.
+//
+// Limits: entries beyond about 1e+-150 overflow / underflow the product a_pp a_qq of the criterion; a matrix with a
+// non-finite entry is refused (EIG_INFO_NOT_FINITE), not decomposed; the iteration is given up after EIG_MAX_SWEEPS
+// sweeps (EIG_INFO_NOT_CONVERGED) - docs/small_eig_spectra.md lists the sweeps that hard spectra take.
 #include "kernels.h"
 #include <algorithm>
+#include <cfloat>
+#include <cmath>
 
 namespace {
 constexpr int EIG_THREADS = 1024;
@@ -29,9 +43,14 @@ __device__ __forceinline__ void tournament_pair(int M, int s, int k, int* p, int
 }
 }  // namespace
 
-// H, S: device, column-major (ld), full symmetric m x m (S ignored unless gev).  On exit theta[0..m), Y (ldy) as above.
-// work: >= 2 * m * m doubles of global scratch.  info[0] = sweeps used, or -j if the Cholesky met a non-positive pivot j
-// (then nothing else is written).
+// H, S: device, column-major (ld), symmetric m x m, of which the UPPER triangle is read (like DSYEV / DSYGV 'U': the diagonal
+// blocks of a projection are Gram products whose two triangles differ by rounding; the result must not depend on how the
+// basis was cut into blocks).  S ignored unless gev.  On exit theta[0..m), Y (ldy) as above.
+// work: >= 2 * m * m doubles of global scratch.  info[0] = sweeps used (< EIG_MAX_SWEEPS), or negative:
+//   -j (1 <= j <= m)        the Cholesky met a non-positive (or NaN) pivot j
+//   EIG_INFO_NOT_FINITE     H, S or the reduced matrix has a NaN / Inf entry
+//   EIG_INFO_NOT_CONVERGED  a rotation was still pending after EIG_MAX_SWEEPS sweeps (theta and Y hold that last iterate)
+// After the first two theta[0..m) is NaN - the values of an earlier call must not pass for this one's - and Y is untouched.
 template <bool VLDS>
 __global__ __launch_bounds__(EIG_THREADS) void small_eig_kernel(const double* __restrict__ H, int64_t ldh, const double* __restrict__ S,
                                                                int64_t lds_, int m, int gev, double* __restrict__ theta,
@@ -50,14 +69,28 @@ __global__ __launch_bounds__(EIG_THREADS) void small_eig_kernel(const double* __
   // ---- load; generalized: reduce to the standard problem ------------------------------------------------------
   for (int e = tid; e < m * m; e += NT) {
     const int i = e % m, j = e / m;
-    As[i + j * la] = H[i + (int64_t)j * ldh];
+    As[i + j * la] = H[min(i, j) + (int64_t)max(i, j) * ldh];
   }
   if (tid == 0) flag = 0;
   __syncthreads();
   if (gev) {
     // Cholesky S = L L^T, right-looking, in global scratch (m steps, the whole workgroup updates the trailing block)
-    for (int e = tid; e < m * m; e += NT) Lg[e] = S[(e % m) + (int64_t)(e / m) * lds_];
+    bool bad = false;
+    for (int e = tid; e < m * m; e += NT) {
+      const int i = e % m, j = e / m;
+      const double v = S[min(i, j) + (int64_t)max(i, j) * lds_];
+      bad |= !(fabs(v) <= DBL_MAX);              // an Inf pivot would reduce to a finite matrix
+      Lg[e] = v;
+    }
+    if (bad) flag = EIG_INFO_NOT_FINITE;         // every writer stores the same value
     __syncthreads();
+    const int bad_s = flag;                      // latched, then a barrier: thread 0 may set the flag at the first pivot
+    __syncthreads();
+    if (bad_s != 0) {
+      for (int j = tid; j < m; j += NT) theta[j] = NAN;
+      if (tid == 0) info[0] = (double)bad_s;
+      return;
+    }
     for (int j = 0; j < m; ++j) {
       const double d = Lg[j + j * m];
       if (!(d > 0.0)) { if (tid == 0) flag = -(j + 1); }
@@ -74,7 +107,11 @@ __global__ __launch_bounds__(EIG_THREADS) void small_eig_kernel(const double* __
       }
       __syncthreads();
     }
-    if (flag != 0) { if (tid == 0) info[0] = (double)flag; return; }
+    if (flag != 0) {
+      for (int j = tid; j < m; j += NT) theta[j] = NAN;
+      if (tid == 0) info[0] = (double)flag;
+      return;
+    }
     // C = L^-1 H L^-T.  X = L^-1 H: forward substitution down the rows, all columns at once (thread = column)
     for (int i = 0; i < m; ++i) {
       for (int j = tid; j < m; j += NT) {
@@ -100,8 +137,21 @@ __global__ __launch_bounds__(EIG_THREADS) void small_eig_kernel(const double* __
     }
     __syncthreads();
   }
+  // a NaN compares false in the rotation test and in the ranking below: it would leave without a rotation, with several
+  // columns of rank 0 and the other theta never written.  Every entry is looked at: off the diagonal a NaN of a standard
+  // problem stays where it is
+  {
+    bool bad = false;
+    for (int e = tid; e < m * m; e += NT) bad |= !(fabs(As[(e % m) + (e / m) * la]) <= DBL_MAX);
+    if (bad) flag = EIG_INFO_NOT_FINITE;
+  }
   for (int e = tid; e < m * m; e += NT) Vs[(e % m) + (size_t)(e / m) * lv] = (e % m) == (e / m) ? 1.0 : 0.0;
   __syncthreads();
+  if (flag != 0) {                               // uniform: thread 0 resets the flag only after it has left this way itself
+    for (int j = tid; j < m; j += NT) theta[j] = NAN;
+    if (tid == 0) info[0] = (double)flag;
+    return;
+  }
 
   // ---- cyclic Jacobi ------------------------------------------------------------------------------------------------
   const int M = (m + 1) & ~1, half = M / 2;
@@ -114,7 +164,7 @@ __global__ __launch_bounds__(EIG_THREADS) void small_eig_kernel(const double* __
   const int ti = tid & (mp - 1), tk = tid >> lg;
   __shared__ int pair_p[64], pair_q[64];
   int sweeps = 0;
-  for (; sweeps < 30; ++sweeps) {
+  for (; sweeps < EIG_MAX_SWEEPS; ++sweeps) {
     if (tid == 0) flag = 0;
     __syncthreads();
     for (int s = 0; s < M - 1; ++s) {
@@ -179,6 +229,10 @@ __global__ __launch_bounds__(EIG_THREADS) void small_eig_kernel(const double* __
     const int rotated = flag;
     __syncthreads();
     if (rotated == 0) break;
+    // one triangle again (header): lower <- upper, the one the rotations are computed from.  The barrier that opens the
+    // next sweep orders these writes before its first step
+    if (ti < m)
+      for (int j = tk; j < ti; j += kstep) As[ti + j * la] = As[j + ti * la];
   }
 
   // ---- ascending order (ties by index), Y ---------------------------------------------------------------------------
@@ -211,7 +265,8 @@ __global__ __launch_bounds__(EIG_THREADS) void small_eig_kernel(const double* __
       }
     }
   }
-  if (tid == 0) info[0] = (double)sweeps;
+  // left by the cap, not by a sweep without a rotation: the caller must not take this for a decomposition
+  if (tid == 0) info[0] = sweeps < EIG_MAX_SWEEPS ? (double)sweeps : (double)EIG_INFO_NOT_CONVERGED;
 }
 
 size_t small_eig_work_doubles(int m) { return (size_t)2 * m * m + 64; }

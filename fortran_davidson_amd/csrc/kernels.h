@@ -266,6 +266,10 @@ void launch_spmm_bsr_finish(hipStream_t st, const CsrLong* longs, int nlong, con
                             int64_t grow0, int64_t nloc);
 
 // ---- device-side Rayleigh-Ritz (k_smalleig.hip): all eigenpairs of H y = theta y / H y = theta S y, order m <= 128 ------
+// info[0] of the kernel: sweeps used (0 .. EIG_MAX_SWEEPS - 1), -j for a non-positive Cholesky pivot j (1 .. 128), or one of
+constexpr int EIG_MAX_SWEEPS = 30;
+constexpr int EIG_INFO_NOT_FINITE = -1000;       // a NaN / Inf entry in H, S or the reduced matrix
+constexpr int EIG_INFO_NOT_CONVERGED = -2000;    // a rotation still pending after EIG_MAX_SWEEPS sweeps
 size_t small_eig_work_doubles(int m);
 bool launch_small_eig(hipStream_t st, const double* H, int64_t ldh, const double* S, int64_t lds, int m, bool gev, double* theta,
                       double* Y, int64_t ldy, double* work, double* info);

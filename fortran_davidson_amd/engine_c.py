@@ -616,6 +616,10 @@ class CEngine:
                                        None, C.c_int64(0), None, C.c_int64(0), C.byref(sweeps)))
         return theta, res, sweeps.value
 
+    def rr_restart(self, m, keep):
+        """collapse restart with the device-resident eigenvectors: V, W (and B V) <- their first `keep` Ritz combinations"""
+        self._chk(self.lib.dav_rr_restart(self.h, C.c_int(m), C.c_int(keep)))
+
     def rr_get(self, m, ncols):
         theta, Y = np.zeros(m), np.zeros((m, ncols), order="F")
         self._chk(self.lib.dav_rr_get(self.h, C.c_int(m), C.c_int(ncols), _dp(theta), _dp(Y), C.c_int64(m)))
