@@ -131,6 +131,12 @@ struct SparseStore {
   int64_t nrows = 0;                // local rows (block rows)
   int b = 0;                        // block size; 1 = CSR
   int64_t grow0 = 0;                // BSR: local row of the first row of local block row 0 (<= 0)
+  // kept only by a set call made with dav_keep_value_map on: what dav_update_operator_values needs to move new values into val and diag
+  uint64_t* src = nullptr;          // device: the value map, per entry (block) of this rank its position in the caller's vals << 1 | mirrored
+  int64_t* doff = nullptr;          // device: diagonal sources of the WHOLE matrix: n + 1 (n / b + 1) offsets into dpos
+  int64_t* dpos = nullptr;          // device: positions of the diagonal entries (blocks) in the caller's vals, row by row in input order
+  int64_t gcount = 0;               // entries (blocks) of the caller's vals
+  int triangle = 0, rowmaj = 0;     // of the set call: DAV_CSR_FULL / DAV_CSR_LOWER; BSR: the caller's blocks are row-major
 };
 
 struct OpDesc {
@@ -298,6 +304,7 @@ struct dav_engine {
   LocalGroup* lg = nullptr;       // loopback transport (tests); owned by rank 0
   ShmGroup* shm = nullptr;        // shared-memory transport (tests of the multi-process launch flow)
   OpDesc op[2];
+  int keep_map[2] = {0, 0};           // dav_keep_value_map: the next sparse set call of the slot keeps its value map
   std::vector<double> diag_host[2];
   std::vector<int64_t> basis_order;   // indices of the smallest diagonal entries of A (cache of dav_init_basis)
   // streaming ingest (dav_dense_begin .. dav_dense_end): two pinned row-major staging buffers + device twins

@@ -3,15 +3,18 @@
 // All four entries follow one structure: the PATTERN - row_ptr and col_idx over rows or block rows - is validated; the
 // canonical order of this rank's rows is built with a PAYLOAD per column index (CSR: the value of the entry; BSR: the source of the block,
 // input position << 1 | mirrored); BSR gathers the VALUES from the sources; the DIAGONAL is summed per kind; one COMMIT step builds the
-// work list and sets the operator.  Host and device entries produce the same arrays bit for bit.
+// work list and sets the operator.  Host and device entries produce the same arrays bit for bit.  With dav_keep_value_map on, CSR travels
+// with sources too and every entry keeps them (the value map) with the sources of the diagonal; dav_update_operator_values(_dev) then
+// repeats the VALUES and DIAGONAL steps alone on new numbers (kernels in k_sparse_refresh.hip).
 #include "engine_internal.h"
 
 void sparse_release(E* e, OpDesc& o) {
   SparseStore& s = o.sp;
-  if (!s.rp && !s.col && !s.val && !s.items && !s.longs && !s.part) return;
+  if (!s.rp && !s.col && !s.val && !s.items && !s.longs && !s.part && !s.src && !s.doff && !s.dpos) return;
   (void)hipStreamSynchronize(e->stream);         // applies in flight may still read the arrays
   pool_free(s.rp); pool_free(s.col); pool_free(s.val);
   pool_free(s.items); pool_free(s.longs); pool_free(s.part);
+  pool_free(s.src); pool_free(s.doff); pool_free(s.dpos);
   s = SparseStore();
 }
 
@@ -234,13 +237,28 @@ void pattern_order(const HostPattern& P, F payload, std::vector<int64_t>& rp, st
   }
 }
 
+// What a set call made with dav_keep_value_map on keeps besides the operator, as a host entry builds it: the value map of this rank's
+// entries (blocks) and the diagonal sources of the whole matrix (SparseStore::src, doff, dpos); gcount / triangle / rowmaj describe the
+// caller's vals.
+struct HostMap {
+  std::vector<uint64_t> src;
+  std::vector<int64_t> doff, dpos;
+  int64_t gcount = 0;
+  int triangle = 0, rowmaj = 0;
+};
+std::string map_memory(const SparseWords& w) { return no_memory(std::string("the value map of the ") + w.items + " of this rank"); }
+
 // the canonical arrays to the device (the engine's allocator; released when the operator is set again and at dav_destroy), then the commit
 int commit_host(const Entry& en, int kind, int b, int64_t grow0, const std::vector<int64_t>& rp, const std::vector<int32_t>& lcol,
-                const std::vector<double>& lval, std::vector<double>& diag, int64_t bytes) {
+                const std::vector<double>& lval, std::vector<double>& diag, int64_t bytes, const HostMap* map) {
   CHK(operator_goes(en.e, en.which, true));
   SparseStore& s = en.e->op[en.which].sp;
   const std::string oom = no_memory(stored(en.w, rp.back(), bytes));
   if (!upload(&s.rp, rp) || !upload(&s.col, lcol) || !upload(&s.val, lval)) return en.refuse(oom);
+  if (map) {
+    if (!upload(&s.src, map->src) || !upload(&s.doff, map->doff) || !upload(&s.dpos, map->dpos)) return en.refuse(map_memory(en.w));
+    s.gcount = map->gcount; s.triangle = map->triangle; s.rowmaj = map->rowmaj;
+  }
   return sparse_commit(en, kind, b, grow0, rp, diag, nullptr, oom);
 }
 }  // namespace
@@ -257,13 +275,29 @@ extern "C" int dav_set_operator_csr(dav_handle_t e, int which, const int64_t* ro
   std::vector<int64_t> rp;
   std::vector<int32_t> lcol;
   std::vector<double> lval;
-  pattern_order(P, [&](int64_t p, bool) { return vals[p]; }, rp, lcol, lval);
+  const bool keep_map = e->keep_map[which] != 0;
+  HostMap map;
+  if (keep_map) {          // the order with the source of an entry as payload (as BSR has it); the values then follow their sources
+    pattern_order(P, [](int64_t p, bool mirrored) { return (uint64_t)p << 1 | (uint64_t)mirrored; }, rp, lcol, map.src);
+    lval.resize(map.src.size());
+    for (size_t q = 0; q < lval.size(); ++q) lval[q] = vals[map.src[q] >> 1];
+    map.doff.assign((size_t)n + 1, 0);
+    map.gcount = row_ptr[n] - index_base;
+    map.triangle = triangle;
+  } else {
+    pattern_order(P, [&](int64_t p, bool) { return vals[p]; }, rp, lcol, lval);
+  }
   // the diagonal of the whole matrix, from the global arrays: duplicates summed in input order, a missing entry counts as 0
   std::vector<double> diag((size_t)n, 0.0);
-  for (int64_t i = 0; i < n; ++i)
+  for (int64_t i = 0; i < n; ++i) {
     for (int64_t p = row_ptr[i] - index_base; p < row_ptr[i + 1] - index_base; ++p)
-      if ((int64_t)col_idx[p] - index_base == i) diag[(size_t)i] += vals[p];
-  return commit_host(en, DAV_KIND_CSR, 1, 0, rp, lcol, lval, diag, 12 * rp.back() + 8 * e->nloc);
+      if ((int64_t)col_idx[p] - index_base == i) {
+        diag[(size_t)i] += vals[p];
+        if (keep_map) map.dpos.push_back(p);
+      }
+    if (keep_map) map.doff[(size_t)i + 1] = (int64_t)map.dpos.size();
+  }
+  return commit_host(en, DAV_KIND_CSR, 1, 0, rp, lcol, lval, diag, 12 * rp.back() + 8 * e->nloc, keep_map ? &map : nullptr);
 }
 
 extern "C" int dav_set_operator_bsr(dav_handle_t e, int which, int block_size, const int64_t* block_row_ptr, const int32_t* block_col_idx,
@@ -297,11 +331,24 @@ extern "C" int dav_set_operator_bsr(dav_handle_t e, int which, int block_size, c
   }
   // the diagonal of the whole matrix, from the diagonal blocks of the global arrays (duplicates summed in input order)
   std::vector<double> diag((size_t)n, 0.0);
-  for (int64_t I = 0; I < nb; ++I)
+  const bool keep_map = e->keep_map[which] != 0;
+  HostMap map;
+  if (keep_map) {
+    map.doff.assign((size_t)nb + 1, 0);
+    map.gcount = block_row_ptr[nb] - index_base;
+    map.triangle = triangle;
+    map.rowmaj = rowmaj ? 1 : 0;
+  }
+  for (int64_t I = 0; I < nb; ++I) {
     for (int64_t p = block_row_ptr[I] - index_base; p < block_row_ptr[I + 1] - index_base; ++p)
-      if ((int64_t)block_col_idx[p] - index_base == I)
+      if ((int64_t)block_col_idx[p] - index_base == I) {
         for (int m = 0; m < b; ++m) diag[(size_t)(I * b + m)] += entry(p, m, m);
-  return commit_host(en, DAV_KIND_BSR, b, ib0 * b - e->row0, rp, lcol, lval, diag, rp.back() * (8 * bb + 4));
+        if (keep_map) map.dpos.push_back(p);
+      }
+    if (keep_map) map.doff[(size_t)I + 1] = (int64_t)map.dpos.size();
+  }
+  if (keep_map) map.src.swap(src);          // the sources of the canonical blocks, as the order step left them
+  return commit_host(en, DAV_KIND_BSR, b, ib0 * b - e->row0, rp, lcol, lval, diag, rp.back() * (8 * bb + 4), keep_map ? &map : nullptr);
 }
 
 // ---- device arrays: the same steps on the GPU --------------------------------------------------------------------------------------------
@@ -496,6 +543,26 @@ double* diag_scratch(BuildScratch& sc, int64_t n, std::string* why) {
   if (sc.oom) *why = no_memory("the diagonal");
   return d;
 }
+
+// (dav_keep_value_map) the diagonal sources of the whole matrix from the counts and first positions of the check pass - the offsets by a
+// scan of the counts, then one thread per row (block row) writes its positions - and the description of the caller's vals
+int keep_diag_sources(const Entry& en, BuildScratch& sc, const DevPattern& P, int triangle, int rowmaj, std::string* why) {
+  E* e = en.e;
+  SparseStore& s = e->op[en.which].sp;
+  int64_t* tile_sums = nullptr;
+  sc.take(&tile_sums, (size_t)csr_build_scan_tiles(P.n));
+  if (sc.oom || !keep(&s.doff, (size_t)P.n + 1)) { *why = map_memory(en.w); return 1; }
+  launch_sparse_build_diag_counts(e->stream, P.dcount, P.n, s.doff);
+  launch_csr_build_scan(e->stream, s.doff + 1, P.n, tile_sums);
+  int64_t total = 0;
+  CHK(readback(e->stream, &total, s.doff + P.n, sizeof(total)));
+  if (!keep(&s.dpos, (size_t)total)) { *why = map_memory(en.w); return 1; }
+  launch_sparse_build_diag_sources(e->stream, P.row_ptr, P.rp64, P.col_idx, P.ci64, P.n, P.base, P.dcount, P.dfirst, s.doff, s.dpos);
+  s.gcount = P.nnz;
+  s.triangle = triangle;
+  s.rowmaj = rowmaj;
+  return 0;
+}
 }  // namespace
 
 // Validation, canonical rows, diagonal and storage equal those of dav_set_operator_csr bit for bit; only the work list is built on the
@@ -514,10 +581,19 @@ extern "C" int dav_set_operator_csr_dev(dav_handle_t e, int which, const void* r
   SparseStore& s = e->op[which].sp;
   const int64_t lnnz = rp.back();
   if (!keep(&s.col, (size_t)lnnz) || !keep(&s.val, (size_t)lnnz)) return en.refuse(no_memory(stored(en.w, lnnz, 12 * lnnz + 8 * e->nloc)));
-  if (int rc = pattern_order_dev(e, sc, P, en.w, s.rp, rp, s.col, s.val, &why)) return en.step(rc, why);
+  const bool keep_map = e->keep_map[which] != 0;
+  if (keep_map) {          // the order with the source of an entry as payload (as BSR has it); the values then follow their sources
+    if (!keep(&s.src, (size_t)lnnz)) return en.refuse(map_memory(en.w));
+    if (int rc = pattern_order_dev(e, sc, P, en.w, s.rp, rp, s.col, s.src, &why)) return en.step(rc, why);
+    launch_sparse_refresh_csr(e->stream, s.src, lnnz, vals, s.val);
+  } else {
+    if (int rc = pattern_order_dev(e, sc, P, en.w, s.rp, rp, s.col, s.val, &why)) return en.step(rc, why);
+  }
   double* diag = diag_scratch(sc, e->n, &why);
   if (!diag) return en.refuse(why);
   launch_csr_build_diag(e->stream, row_ptr, P.rp64, col_idx, P.ci64, vals, e->n, index_base, P.dcount, P.dfirst, diag);
+  if (keep_map)
+    if (int rc = keep_diag_sources(en, sc, P, triangle, 0, &why)) return en.step(rc, why);
   std::vector<double> hdiag;
   return sparse_commit(en, DAV_KIND_CSR, 1, 0, rp, hdiag, diag, no_memory(work_list(en.w, lnnz)));
 }
@@ -544,9 +620,11 @@ extern "C" int dav_set_operator_bsr_dev(dav_handle_t e, int which, int block_siz
   if (int rc = pattern_begin_dev(en, sc, P, rp, &why)) return en.step(rc, why);
   SparseStore& s = e->op[which].sp;
   const int64_t lnnzb = rp.back();
-  uint64_t* src = nullptr;          // source of each canonical block: input block p << 1 | mirrored
-  sc.take(&src, (size_t)lnnzb);
-  if (sc.oom || !keep(&s.col, (size_t)lnnzb) || !keep(&s.val, (size_t)(lnnzb * bb)))
+  const bool keep_map = e->keep_map[which] != 0;
+  uint64_t* src = nullptr;          // source of each canonical block: input block p << 1 | mirrored (dav_keep_value_map: stays with the operator)
+  if (!keep_map) sc.take(&src, (size_t)lnnzb);
+  else if (keep(&s.src, (size_t)lnnzb)) src = s.src;
+  if (!src || sc.oom || !keep(&s.col, (size_t)lnnzb) || !keep(&s.val, (size_t)(lnnzb * bb)))
     return en.refuse(no_memory(stored(en.w, lnnzb, lnnzb * (8 * bb + 12))));
   if (int rc = pattern_order_dev(e, sc, P, en.w, s.rp, rp, s.col, src, &why)) return en.step(rc, why);
   // the values: column-major per block, a mirrored block the transpose of its source
@@ -554,6 +632,82 @@ extern "C" int dav_set_operator_bsr_dev(dav_handle_t e, int which, int block_siz
   double* diag = diag_scratch(sc, n, &why);
   if (!diag) return en.refuse(why);
   launch_bsr_build_diag(e->stream, b, block_row_ptr, P.rp64, block_col_idx, P.ci64, vals, nb, index_base, P.dcount, P.dfirst, diag);
+  if (keep_map)
+    if (int rc = keep_diag_sources(en, sc, P, triangle, block_layout == DAV_BSR_ROW_MAJOR ? 1 : 0, &why)) return en.step(rc, why);
   std::vector<double> hdiag;
   return sparse_commit(en, DAV_KIND_BSR, b, ib0 * b - e->row0, rp, hdiag, diag, no_memory(work_list(en.w, lnnzb)));
+}
+
+// ---- new values on the kept pattern ------------------------------------------------------------------------------------------------------
+// The fifth entry of the shared structure: steps 3 (values) and 4 (diagonal) alone, over what a set call made with dav_keep_value_map on
+// left with the operator.  rp, col, the work list, the partial slots and the maps are read or left alone, never written.
+extern "C" int dav_keep_value_map(dav_handle_t e, int which, int on) {
+  if (!e) return fail("dav_keep_value_map: null engine");
+  if (which < 0 || which > 1) return fail("dav_keep_value_map: bad operator id");
+  e->keep_map[which] = on != 0 ? 1 : 0;
+  return 0;
+}
+
+namespace {
+// a refused update leaves the operator as it is: set, with its old values
+int update_refuse(const char* name, const std::string& msg) { return fail(std::string(name) + ": " + msg); }
+
+// "" = the operator can take new values: CSR or BSR, set with its value map
+std::string not_updatable(const OpDesc& o) {
+  if (o.kind == DAV_KIND_NONE) return "operator not set";
+  if (o.kind != DAV_KIND_CSR && o.kind != DAV_KIND_BSR)
+    return "the operator is not a CSR or BSR operator (only a sparse operator set after dav_keep_value_map(h, which, 1) takes new values)";
+  if (!o.sp.src || !o.sp.doff || !o.sp.dpos)
+    return "the operator was set without its value map: call dav_keep_value_map(h, which, 1) before the set call";
+  return "";
+}
+
+// vals: the caller's values in device memory, as long as the set call's
+int update_from_device(E* e, int which, const char* name, BuildScratch& sc, const double* vals) {
+  OpDesc& o = e->op[which];
+  const SparseStore& s = o.sp;
+  hipStream_t st = e->stream;
+  double* diag = nullptr;          // the diagonal of the whole matrix (o.diag holds the local rows)
+  sc.take(&diag, (size_t)e->n);
+  if (sc.oom) return update_refuse(name, no_memory("the diagonal"));
+  if (o.kind == DAV_KIND_CSR) launch_sparse_refresh_csr(st, s.src, s.nnz, vals, s.val);
+  else launch_bsr_build_gather(st, s.b, s.src, s.nnz, vals, s.rowmaj, s.val);
+  launch_sparse_refresh_diag(st, s.b, s.doff, s.dpos, vals, e->n, diag);
+  if (e->nloc > 0) HIPCHK(hipMemcpyAsync(o.diag, diag + e->row0, sizeof(double) * e->nloc, hipMemcpyDeviceToDevice, st));
+  // what depends on the numbers: the diagonal on the host and the start-vector order of A
+  if (which == DAV_OP_A) e->basis_order.clear();
+  e->diag_host[which].resize((size_t)e->n);
+  return readback(st, e->diag_host[which].data(), diag, sizeof(double) * (size_t)e->n);     // ends synchronised: vals is free again
+}
+}  // namespace
+
+extern "C" int dav_update_operator_values(dav_handle_t e, int which, const double* vals) {
+  const char* name = "dav_update_operator_values";
+  CHK(entry_begin(e, which, name));
+  const std::string why = not_updatable(e->op[which]);
+  if (!why.empty()) return update_refuse(name, why);
+  const SparseStore& s = e->op[which].sp;
+  const size_t count = (size_t)s.gcount * (size_t)s.b * (size_t)s.b;
+  if (count > 0 && !vals) return update_refuse(name, "null vals");
+  BuildScratch sc(e->stream);
+  double* dvals = nullptr;
+  sc.take(&dvals, count);
+  if (sc.oom) return update_refuse(name, no_memory("the " + std::to_string(count) + " values"));
+  if (count > 0) HIPCHK(hipMemcpyAsync(dvals, vals, sizeof(double) * count, hipMemcpyHostToDevice, e->stream));
+  return update_from_device(e, which, name, sc, dvals);
+}
+
+extern "C" int dav_update_operator_values_dev(dav_handle_t e, int which, const double* vals_dev) {
+  const char* name = "dav_update_operator_values_dev";
+  CHK(entry_begin(e, which, name));
+  std::string why = not_updatable(e->op[which]);
+  if (!why.empty()) return update_refuse(name, why);
+  const SparseStore& s = e->op[which].sp;
+  const size_t count = (size_t)s.gcount * (size_t)s.b * (size_t)s.b;
+  if (count > 0) {
+    if (!vals_dev) return update_refuse(name, "null vals");
+    if (!device_array(e, vals_dev, "vals", sizeof(double) * count, &why)) return update_refuse(name, why);
+  }
+  BuildScratch sc(e->stream);
+  return update_from_device(e, which, name, sc, vals_dev);
 }

@@ -371,11 +371,15 @@ void launch_csr_build_offsets(hipStream_t st, const void* rp, int rp64, int64_t 
                               int64_t* tile_sums) {
   cb_dispatch(rp64, 0, [&](auto r_, auto) { using RP = decltype(r_); hipLaunchKernelGGL(csr_build_lengths_kernel<RP>, dim3(cb_grid_stride(nloc)), dim3(CB_THREADS), 0, st, (const RP*)rp, r0, nloc,
                                  mcount, lrp); });
-  if (nloc <= 0) return;
-  const int64_t nt = csr_build_scan_tiles(nloc);
-  hipLaunchKernelGGL(csr_build_scan_sums_kernel, dim3((unsigned)nt), dim3(CB_THREADS), 0, st, lrp + 1, nloc, tile_sums);
+  launch_csr_build_scan(st, lrp + 1, nloc, tile_sums);
+}
+
+void launch_csr_build_scan(hipStream_t st, int64_t* x, int64_t m, int64_t* tile_sums) {
+  if (m <= 0) return;
+  const int64_t nt = csr_build_scan_tiles(m);
+  hipLaunchKernelGGL(csr_build_scan_sums_kernel, dim3((unsigned)nt), dim3(CB_THREADS), 0, st, x, m, tile_sums);
   hipLaunchKernelGGL(csr_build_scan_tiles_kernel, dim3(1), dim3(CB_THREADS), 0, st, tile_sums, nt);
-  hipLaunchKernelGGL(csr_build_scan_apply_kernel, dim3((unsigned)nt), dim3(CB_THREADS), 0, st, lrp + 1, nloc, tile_sums);
+  hipLaunchKernelGGL(csr_build_scan_apply_kernel, dim3((unsigned)nt), dim3(CB_THREADS), 0, st, x, m, tile_sums);
 }
 
 int64_t csr_build_scan_tiles(int64_t m) { return std::max<int64_t>(1, (m + SCAN_TILE - 1) / SCAN_TILE); }

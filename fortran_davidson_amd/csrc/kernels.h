@@ -216,6 +216,8 @@ void launch_csr_build_locate(hipStream_t st, const void* rp, int rp64, const voi
 void launch_csr_build_offsets(hipStream_t st, const void* rp, int rp64, int64_t r0, int64_t nloc, const int32_t* mcount, int64_t* lrp,
                               int64_t* tile_sums);
 int64_t csr_build_scan_tiles(int64_t m);
+// x[0..m) -> its inclusive prefix sums, in place (the scan of the offsets above); tile_sums holds csr_build_scan_tiles(m) values
+void launch_csr_build_scan(hipStream_t st, int64_t* x, int64_t m, int64_t* tile_sums);
 // entries [p_lo, p_hi): own entries of local rows and (lower) mirrored entries to the canonical rows, columns narrowed to int32 without
 // the base; fill (zero first) = slots taken per local row; tie (lower: required; full: nullptr) = offset of each entry in its source row
 void launch_csr_build_scatter(hipStream_t st, const void* rp, int rp64, const void* col, int ci64, const double* vals, int64_t n, int64_t p_lo,
@@ -250,6 +252,22 @@ void launch_bsr_build_gather(hipStream_t st, int bs, const uint64_t* src, int64_
 // +0.0 (dcount / dfirst of the check pass over the block rows; entry (m, m) sits at m b + m in either layout)
 void launch_bsr_build_diag(hipStream_t st, int bs, const void* rp, int rp64, const void* col, int ci64, const double* vals, int64_t nb,
                            int base, const uint32_t* dcount, const unsigned long long* dfirst, double* diag);
+
+// ---- K1e: new values on the kept pattern of a sparse operator (k_sparse_refresh.hip; dav_update_operator_values) --------------------
+// The value map src[q] = p << 1 | mirrored of every canonical local entry (block) q, p the position in the caller's vals, and the
+// diagonal sources of the whole matrix: dpos[doff[I] .. doff[I + 1]) = the positions of the diagonal entries (blocks) of row (block
+// row) I in input order.
+// CSR: val[q] = vals[src[q] >> 1] over the lnnz local entries (BSR: launch_bsr_build_gather); sparse_refresh_tile() entries per workgroup
+void launch_sparse_refresh_csr(hipStream_t st, const uint64_t* src, int64_t lnnz, const double* vals, double* val);
+int64_t sparse_refresh_tile();
+// diag[i] = +0.0 + entry (m, m), m = i mod bs, of the diagonal blocks of block row i / bs in input order, i < n (the whole matrix);
+// entry (m, m) of block p sits at p bs^2 + m bs + m in either block layout.  bs = 1: a CSR matrix
+void launch_sparse_refresh_diag(hipStream_t st, int bs, const int64_t* doff, const int64_t* dpos, const double* vals, int64_t n, double* diag);
+// the device set entries, after the check pass (dcount / dfirst of launch_csr_build_check over the n rows or block rows):
+// doff[0] = 0, doff[i + 1] = dcount[i] (then launch_csr_build_scan over doff + 1), and dpos behind the scanned offsets
+void launch_sparse_build_diag_counts(hipStream_t st, const uint32_t* dcount, int64_t n, int64_t* doff);
+void launch_sparse_build_diag_sources(hipStream_t st, const void* rp, int rp64, const void* col, int ci64, int64_t n, int base,
+                                      const uint32_t* dcount, const unsigned long long* dfirst, const int64_t* doff, int64_t* dpos);
 
 // ---- K1d: BSR block product on the matrix cores (k_bsrmm.hip) ------------------------------------------------------------------------
 // Y[rows of this rank, 0:kk] = A_bsr * X, uniform block size 1 <= b <= 16, blocks column-major on the device.  Work list built on the

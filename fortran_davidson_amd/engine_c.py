@@ -80,6 +80,11 @@ def is_torch_csr(t):
 def device_csr_tensors(row_ptr, col_idx, vals, n, device):
     """The checks of a CSR matrix in device tensors before any library call: int32 / int64 indices and float64 values (TypeError, never
     converted), contiguous tensors on cuda:`device` and n + 1 offsets (ValueError).  Returns (row_ptr_bits, col_bits)."""
+    return _device_csr_tensors(row_ptr, col_idx, vals, n, device)[:2]
+
+
+def _device_csr_tensors(row_ptr, col_idx, vals, n, device):
+    """device_csr_tensors, with the number of entries row_ptr gives as a third result"""
     import torch
     args = (("row_ptr", row_ptr, (torch.int32, torch.int64)), ("col_idx", col_idx, (torch.int32, torch.int64)),
             ("vals", vals, (torch.float64,)))
@@ -99,7 +104,7 @@ def device_csr_tensors(row_ptr, col_idx, vals, n, device):
     nnz = int(row_ptr[-1]) - int(row_ptr[0])          # two values read back: the kernels must not read past the tensors
     if col_idx.numel() < nnz or vals.numel() < nnz:
         raise ValueError(f"device CSR input: row_ptr says {nnz} entries, col_idx / vals hold {col_idx.numel()} / {vals.numel()}")
-    return (64 if row_ptr.dtype == torch.int64 else 32), (64 if col_idx.dtype == torch.int64 else 32)
+    return (64 if row_ptr.dtype == torch.int64 else 32), (64 if col_idx.dtype == torch.int64 else 32), nnz
 
 
 def torch_csr_parts(t):
@@ -222,6 +227,11 @@ def device_bsr_tensors(row_ptr, col_idx, vals, n, device):
     """The checks of a BSR matrix in device tensors before any library call: int32 / int64 indices and float64 values (TypeError, never
     converted); contiguous tensors on cuda:`device`, vals of shape (nnzb, b, b) with 1 <= b <= 16 dividing n, n / b + 1 offsets and
     enough block columns and blocks (ValueError).  Returns (b, row_ptr_bits, col_bits)."""
+    return _device_bsr_tensors(row_ptr, col_idx, vals, n, device)[:3]
+
+
+def _device_bsr_tensors(row_ptr, col_idx, vals, n, device):
+    """device_bsr_tensors, with the number of blocks row_ptr gives as a fourth result"""
     import torch
     args = (("row_ptr", row_ptr, (torch.int32, torch.int64), 1), ("col_idx", col_idx, (torch.int32, torch.int64), 1),
             ("vals", vals, (torch.float64,), 3))
@@ -248,7 +258,32 @@ def device_bsr_tensors(row_ptr, col_idx, vals, n, device):
     nnzb = int(row_ptr[-1]) - int(row_ptr[0])         # two values read back: the kernels must not read past the tensors
     if col_idx.numel() < nnzb or vals.shape[0] < nnzb:
         raise ValueError(f"device BSR input: row_ptr says {nnzb} blocks, col_idx / vals hold {col_idx.numel()} / {vals.shape[0]}")
-    return b, (64 if row_ptr.dtype == torch.int64 else 32), (64 if col_idx.dtype == torch.int64 else 32)
+    return b, (64 if row_ptr.dtype == torch.int64 else 32), (64 if col_idx.dtype == torch.int64 else 32), nnzb
+
+
+def update_values_array(vals, count, device=None, what="update_operator_values"):
+    """The checks of new values for a kept pattern before any library call: float64 (TypeError, never converted), contiguous, and - where
+    `count` (the values the set call saw) is known - exactly that many (ValueError); BSR blocks as (nnzb, b, b) or flat.  Returns
+    (flat numpy array, None) for host data (numpy, or a torch tensor on the CPU) or (None, torch tensor) for a tensor on cuda:`device`."""
+    if type(vals).__module__.startswith("torch"):
+        import torch
+        if vals.dtype != torch.float64:
+            raise TypeError(f"{what}: vals has dtype {vals.dtype}, expected torch.float64")
+        if vals.layout != torch.strided or not vals.is_contiguous():
+            raise ValueError(f"{what}: vals must be a contiguous tensor")
+        if count is not None and vals.numel() != count:
+            raise ValueError(f"{what}: the set call saw {count} values, vals holds {vals.numel()}")
+        if vals.device.type == "cpu":
+            return vals.numpy().reshape(-1), None
+        if vals.device.type != "cuda" or (device is not None and vals.device.index != device):
+            raise ValueError(f"{what}: vals lies on {vals.device}, the engine on cuda:{device}")
+        return None, vals
+    a = np.asarray(vals)
+    if a.dtype != np.float64:
+        raise TypeError(f"{what}: vals has dtype {a.dtype}, expected float64")
+    if count is not None and a.size != count:
+        raise ValueError(f"{what}: the set call saw {count} values, vals holds {a.size}")
+    return np.ascontiguousarray(a).reshape(-1), None
 
 
 def _f(a):
@@ -416,21 +451,25 @@ class CEngine:
         rp, ci, vv = csr_arrays(indptr, indices, data, self.n)
         ci_p = ci.ctypes.data_as(C.POINTER(C.c_int32)) if ci.size else (C.c_int32 * 1)()
         vv_p = _dp(vv) if vv.size else (C.c_double * 1)()
+        self._saw_values(which, None)
         self._chk(self.lib.dav_set_operator_csr(self.h, C.c_int(which), rp.ctypes.data_as(C.POINTER(C.c_int64)), ci_p, vv_p, C.c_int(base),
                                                 C.c_int(CSR_LOWER if lower else CSR_FULL)))
+        self._saw_values(which, int(rp[-1] - rp[0]))
 
     def set_operator_csr_dev(self, which, row_ptr, col_idx, vals, base=0, lower=False):
         """dav_set_operator_csr_dev: the matrix of set_operator_csr as torch tensors on the engine's device, built on the GPU - row_ptr
         (n + 1) and col_idx int32 or int64, vals float64, all contiguous.  Other dtypes are a TypeError (never converted).  Torch's
         current stream on the device is synchronised first, so work queued on it that writes the arrays is complete.  The engine's
         refusal is a DavidsonHipError; the operator is then unset."""
-        rpb, cib = device_csr_tensors(row_ptr, col_idx, vals, self.n, self.device)
+        rpb, cib, nnz = _device_csr_tensors(row_ptr, col_idx, vals, self.n, self.device)
         import torch
         torch.cuda.current_stream(row_ptr.device).synchronize()
+        self._saw_values(which, None)
         self._chk(self.lib.dav_set_operator_csr_dev(self.h, C.c_int(which), C.c_void_p(row_ptr.data_ptr()), C.c_int(rpb),
                                                     C.c_void_p(col_idx.data_ptr() or None), C.c_int(cib),
                                                     C.c_void_p(vals.data_ptr() or None), C.c_int(base),
                                                     C.c_int(CSR_LOWER if lower else CSR_FULL)))
+        self._saw_values(which, nnz)
 
     def set_operator_bsr(self, which, indptr, indices=None, data=None, base=0, lower=False, layout=BSR_ROW_MAJOR):
         """dav_set_operator_bsr: a symmetric matrix in BSR form with square blocks (the global arrays; indptr / indices count block
@@ -446,21 +485,51 @@ class CEngine:
         b, rp, ci, vv = bsr_arrays(indptr, indices, data, self.n, layout)
         ci_p = ci.ctypes.data_as(C.POINTER(C.c_int32)) if ci.size else (C.c_int32 * 1)()
         vv_p = _dp(vv) if vv.size else (C.c_double * 1)()
+        self._saw_values(which, None)
         self._chk(self.lib.dav_set_operator_bsr(self.h, C.c_int(which), C.c_int(b), rp.ctypes.data_as(C.POINTER(C.c_int64)), ci_p, vv_p,
                                                 C.c_int(base), C.c_int(CSR_LOWER if lower else CSR_FULL), C.c_int(layout)))
+        self._saw_values(which, int(rp[-1] - rp[0]) * b * b)
 
     def set_operator_bsr_dev(self, which, row_ptr, col_idx, vals, base=0, lower=False, layout=BSR_ROW_MAJOR):
         """dav_set_operator_bsr_dev: the matrix of set_operator_bsr as torch tensors on the engine's device, built on the GPU - row_ptr
         (n / b + 1) and col_idx int32 or int64, vals float64 of shape (nnzb, b, b), all contiguous.  Other dtypes are a TypeError (never
         converted).  Torch's current stream on the device is synchronised first, so work queued on it that writes the arrays is
         complete.  The engine's refusal is a DavidsonHipError; the operator is then unset."""
-        b, rpb, cib = device_bsr_tensors(row_ptr, col_idx, vals, self.n, self.device)
+        b, rpb, cib, nnzb = _device_bsr_tensors(row_ptr, col_idx, vals, self.n, self.device)
         import torch
         torch.cuda.current_stream(row_ptr.device).synchronize()
+        self._saw_values(which, None)
         self._chk(self.lib.dav_set_operator_bsr_dev(self.h, C.c_int(which), C.c_int(b), C.c_void_p(row_ptr.data_ptr()), C.c_int(rpb),
                                                     C.c_void_p(col_idx.data_ptr() or None), C.c_int(cib),
                                                     C.c_void_p(vals.data_ptr() or None), C.c_int(base),
                                                     C.c_int(CSR_LOWER if lower else CSR_FULL), C.c_int(layout)))
+        self._saw_values(which, nnzb * b * b)
+
+    def _saw_values(self, which, count):
+        """the number of values the sparse set call of operator `which` saw (None: unknown - a refused call, or one not made here)"""
+        self._value_counts = getattr(self, "_value_counts", {})
+        self._value_counts[which] = count
+
+    def keep_value_map(self, which, on=True):
+        """dav_keep_value_map: a sticky switch per operator; the NEXT sparse set call of `which` also keeps where every stored value came
+        from (8 bytes per entry or block of this rank, 16 per row or block row), which update_operator_values needs.  No effect on an
+        operator that is already set."""
+        self._chk(self.lib.dav_keep_value_map(self.h, C.c_int(which), C.c_int(1 if on else 0)))
+
+    def update_operator_values(self, which, vals):
+        """dav_update_operator_values / dav_update_operator_values_dev: new values on the kept pattern of a CSR or BSR operator set after
+        keep_value_map(which) - `vals` as long and in the order (BSR: block layout; (nnzb, b, b) or flat) of the vals of that set call.
+        A numpy array (or a torch tensor on the CPU) goes through the host entry; a torch tensor on the engine's device through the
+        device entry, after torch's current stream on the device has been synchronised.  float64 only (TypeError, never converted); a
+        length other than what the set call saw is a ValueError before the engine is called.  The engine's refusal - no value map, not
+        a sparse operator - is a DavidsonHipError, and the operator keeps its old values."""
+        host, dev = update_values_array(vals, getattr(self, "_value_counts", {}).get(which), self.device)
+        if dev is not None:
+            import torch
+            torch.cuda.current_stream(dev.device).synchronize()
+            self._chk(self.lib.dav_update_operator_values_dev(self.h, C.c_int(which), C.c_void_p(dev.data_ptr() or None)))
+        else:
+            self._chk(self.lib.dav_update_operator_values(self.h, C.c_int(which), _dp(host) if host.size else (C.c_double * 1)()))
 
     def get_diagonal(self, which):
         d = np.zeros(self.n)

@@ -7,7 +7,8 @@ module davidson_c_api
   use davidson, only: generalized_eigensolver
   use davidson_device
   use davidson_free, only: free_matmul
-  use davidson_sparse, only: csr_matrix, bsr_matrix, engine_set_sparse, engine_set_sparse_device, engine_set_block_sparse_device
+  use davidson_sparse, only: csr_matrix, bsr_matrix, engine_set_sparse, engine_set_sparse_device, engine_set_block_sparse_device, &
+       engine_keep_value_map, engine_update_sparse_values, engine_update_sparse_values_device
   use lapack_wrapper
   use array_utils
   implicit none
@@ -335,6 +336,41 @@ contains
          row_major=row_major /= 0, row_ptr_bits=int(rp_bits), col_bits=int(col_bits), stat=st)
     stat = int(st, c_int)
   end function fd_engine_set_block_sparse_device
+
+  !> engine_keep_value_map(eng, which, on): the next sparse set call of operator `which` keeps its value map
+  subroutine fd_engine_keep_value_map(p, which, on) bind(C, name="fd_engine_keep_value_map")
+    type(c_ptr), value :: p
+    integer(c_int), value :: which, on
+    type(davidson_engine), pointer :: eng
+    call c_f_pointer(p, eng)
+    call engine_keep_value_map(eng, int(which), on /= 0)
+  end subroutine fd_engine_keep_value_map
+
+  !> engine_update_sparse_values(eng, which, values) with the count values of the set call (BSR: the blocks one after the other, each
+  !> in the order the set door gave them - Fortran order for fd_engine_set_block_sparse)
+  subroutine fd_engine_update_values(p, which, vals, count) bind(C, name="fd_engine_update_values")
+    type(c_ptr), value :: p
+    integer(c_int), value :: which
+    integer(c_int64_t), value :: count
+    real(c_double), intent(in) :: vals(count)
+    type(davidson_engine), pointer :: eng
+    call c_f_pointer(p, eng)
+    call engine_update_sparse_values(eng, int(which), vals)
+  end subroutine fd_engine_update_values
+
+  !> engine_update_sparse_values_device(eng, which, vals, stat) with a device array: returns the engine's status (0 = updated; otherwise
+  !> dav_last_error says why and the operator keeps its old values) instead of stopping the process
+  function fd_engine_update_values_device(p, which, vals) result(stat) bind(C, name="fd_engine_update_values_device")
+    type(c_ptr), value :: p
+    integer(c_int), value :: which
+    type(c_ptr), value :: vals
+    integer(c_int) :: stat
+    type(davidson_engine), pointer :: eng
+    integer :: st
+    call c_f_pointer(p, eng)
+    call engine_update_sparse_values_device(eng, int(which), vals, stat=st)
+    stat = int(st, c_int)
+  end function fd_engine_update_values_device
 
   !> kind 0: dense generated in HBM, 1: hashed matrix-free operator, 2: harness operator, 3: identity
   subroutine fd_engine_set_operator(p, which, kind, seed, sparsity, use_diag_val, diag_val) &

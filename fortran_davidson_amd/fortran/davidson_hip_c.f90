@@ -199,6 +199,29 @@ module davidson_hip_c
        integer(c_int), value :: index_base, triangle, block_layout
        integer(c_int) :: ierr
      end function
+     !> sticky switch per operator slot: the next sparse set call keeps its value map (dav_update_operator_values needs it)
+     function dav_keep_value_map(h, which, on) bind(C, name="dav_keep_value_map") result(ierr)
+       import :: c_ptr, c_int
+       type(c_ptr), value :: h
+       integer(c_int), value :: which, on
+       integer(c_int) :: ierr
+     end function
+     !> new values on the kept pattern of a CSR / BSR operator: vals as long and in the order (and block layout) of the set call's
+     function dav_update_operator_values(h, which, vals) bind(C, name="dav_update_operator_values") result(ierr)
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: h
+       integer(c_int), value :: which
+       real(c_double), intent(in) :: vals(*)
+       integer(c_int) :: ierr
+     end function
+     !> the same from device memory of the engine's device
+     function dav_update_operator_values_dev(h, which, vals_dev) bind(C, name="dav_update_operator_values_dev") result(ierr)
+       import :: c_ptr, c_int
+       type(c_ptr), value :: h
+       integer(c_int), value :: which
+       type(c_ptr), value :: vals_dev
+       integer(c_int) :: ierr
+     end function
      !> a symmetric matrix in CSR form, global host arrays (ABI 109); index_base 1 = Fortran numbering of rows and columns
      function dav_set_operator_csr(h, which, row_ptr, col_idx, vals, index_base, triangle) bind(C, name="dav_set_operator_csr") &
           result(ierr)

@@ -10,6 +10,7 @@ module davidson_sparse
   implicit none
   private
   public :: csr_matrix, bsr_matrix, engine_set_sparse, engine_set_sparse_device, engine_set_block_sparse_device
+  public :: engine_keep_value_map, engine_update_sparse_values, engine_update_sparse_values_device
 
   !> A symmetric real matrix of order n in CSR form, 1-based: the entries of row i are col_idx / values(row_ptr(i) : row_ptr(i+1) - 1).
   !> lower = .true.: only the entries with column <= row are given (the engine mirrors the strict lower part); .false.: every nonzero
@@ -51,7 +52,74 @@ module davidson_sparse
      module procedure engine_set_sparse_bsr
   end interface engine_set_sparse
 
+  !> engine_update_sparse_values(eng, which, values): new values on the kept pattern of a sparse operator set after
+  !> engine_keep_value_map(eng, which, .true.) - values(:) as the values of the csr_matrix (or of the device array) of that set call,
+  !> values(b, b, nnzb) as those of the bsr_matrix
+  interface engine_update_sparse_values
+     module procedure engine_update_sparse_values_csr
+     module procedure engine_update_sparse_values_bsr
+  end interface engine_update_sparse_values
+
 contains
+
+  !> Sticky switch of operator A (which = 1) or B (which = 2): with on = .true. the NEXT engine_set_sparse / engine_set_sparse_device /
+  !> engine_set_block_sparse_device call for that operator also keeps where every stored value came from (8 bytes per entry or block of
+  !> this rank, 16 per row or block row of the matrix), so that engine_update_sparse_values can move new numbers into the kept pattern.
+  !> It has no effect on an operator that is already set.
+  subroutine engine_keep_value_map(eng, which, on)
+    type(davidson_engine), intent(inout) :: eng
+    integer, intent(in) :: which
+    logical, intent(in) :: on
+    call check_dav(dav_keep_value_map(eng%h, int(which - 1, c_int), merge(1_c_int, 0_c_int, on)), "dav_keep_value_map")
+  end subroutine engine_keep_value_map
+
+  !> New values of operator A (which = 1) or B (which = 2), a sparse operator set after engine_keep_value_map: values has the length and
+  !> order of the values of the set call (for a BSR operator its blocks one after the other, each as the set call had them).  The
+  !> pattern is not touched; values, diagonal, applies and solves equal bit for bit what a fresh engine_set_sparse with these values
+  !> gives.  The array is free again when the call returns.
+  subroutine engine_update_sparse_values_csr(eng, which, values)
+    type(davidson_engine), intent(inout) :: eng
+    integer, intent(in) :: which
+    real(dp), intent(in) :: values(:)
+    real(dp) :: nothing(1)
+    if (size(values) > 0) then
+       call check_dav(dav_update_operator_values(eng%h, int(which - 1, c_int), values), "dav_update_operator_values")
+    else
+       nothing = 0.0_dp
+       call check_dav(dav_update_operator_values(eng%h, int(which - 1, c_int), nothing), "dav_update_operator_values")
+    end if
+  end subroutine engine_update_sparse_values_csr
+
+  !> The same for a BSR operator set from a bsr_matrix: values(m, k, p) the entry (m, k) of block p, as bsr_matrix has them
+  subroutine engine_update_sparse_values_bsr(eng, which, values)
+    type(davidson_engine), intent(inout) :: eng
+    integer, intent(in) :: which
+    real(dp), intent(in) :: values(:, :, :)
+    real(dp) :: nothing(1)
+    if (size(values) > 0) then
+       call check_dav(dav_update_operator_values(eng%h, int(which - 1, c_int), values), "dav_update_operator_values")
+    else
+       nothing = 0.0_dp
+       call check_dav(dav_update_operator_values(eng%h, int(which - 1, c_int), nothing), "dav_update_operator_values")
+    end if
+  end subroutine engine_update_sparse_values_bsr
+
+  !> The same from DEVICE memory of the engine's device (vals as the vals of engine_set_sparse_device /
+  !> engine_set_block_sparse_device, complete when the call is made and free again when it returns).  stat present: a refused update
+  !> returns its non-zero status here (dav_last_error says why; the operator keeps its old values), otherwise the program stops.
+  subroutine engine_update_sparse_values_device(eng, which, vals, stat)
+    type(davidson_engine), intent(inout) :: eng
+    integer, intent(in) :: which
+    type(c_ptr), intent(in) :: vals
+    integer, intent(out), optional :: stat
+    integer(c_int) :: ierr
+    ierr = dav_update_operator_values_dev(eng%h, int(which - 1, c_int), vals)
+    if (present(stat)) then
+       stat = int(ierr)
+    else
+       call check_dav(ierr, "dav_update_operator_values_dev")
+    end if
+  end subroutine engine_update_sparse_values_device
 
   function new_csr_matrix(n, row_ptr, col_idx, values, lower) result(a)
     integer, intent(in) :: n

@@ -16,8 +16,8 @@ import ctypes as C
 import numpy as np
 
 from ._lib import fortran_lib, hip_lib
-from .engine_c import (CEngine, DavidsonHipError, check_bsr, check_csr, device_bsr_tensors, device_csr_tensors, is_torch_bsr, is_torch_csr,
-                       torch_bsr_parts, torch_csr_parts)
+from .engine_c import (CEngine, DavidsonHipError, _device_bsr_tensors, _device_csr_tensors, check_bsr, check_csr, device_bsr_tensors,
+                       device_csr_tensors, is_torch_bsr, is_torch_csr, torch_bsr_parts, torch_csr_parts, update_values_array)
 
 _METHOD = {"DPR": 0, "GJD": 1}
 _CB = C.CFUNCTYPE(None, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
@@ -230,20 +230,31 @@ class DavidsonEngine:
         assert a.shape == (self.n, self.n)
         self.lib.fd_engine_set_dense(self.p, C.c_int(which), _dp(a))
 
-    def set_sparse(self, which, indptr, indices=None, data=None, lower=False):
+    def _keep_map(self, which, keep_map):
+        """the switch of the set call that follows (Fortran: engine_keep_value_map); what update_values knew of the operator goes"""
+        self._kept = getattr(self, "_kept", {})
+        self._kept.pop(which, None)
+        self.lib.fd_engine_keep_value_map(self.p, C.c_int(which), C.c_int(1 if keep_map else 0))
+
+    def set_sparse(self, which, indptr, indices=None, data=None, lower=False, keep_map=False):
         """Operator A (which=1) or B (which=2) as a symmetric matrix in CSR form, 0-based (Fortran: engine_set_sparse): three arrays,
         or `indptr` an object with .tocsr(), or a torch.sparse_csr_tensor - one on the engine's GPU is built there (Fortran:
         engine_set_sparse_device; a refused matrix raises DavidsonHipError and leaves the operator unset).  lower=True: only the
-        entries with column <= row are given."""
+        entries with column <= row are given.  keep_map=True: the operator also keeps where its values came from (Fortran:
+        engine_keep_value_map), so that update_values can replace them on the kept pattern."""
         a = indptr if indices is None and data is None else (indptr, indices, data)
         if _is_device_csr(a):
-            return self._set_sparse_device(which, *torch_csr_parts(a), lower=lower)
+            return self._set_sparse_device(which, *torch_csr_parts(a), lower=lower, keep_map=keep_map)
         _, rp, ci, vv = _sparse_input(a, self.n, lower)
+        self._keep_map(which, keep_map)
         self.lib.fd_engine_set_sparse(self.p, C.c_int(which), C.c_int(self.n), _i64(rp), _i32(ci), _dp(vv), C.c_int(0),
                                       C.c_int(1 if lower else 0))
+        if keep_map:
+            self._kept[which] = {"count": int(rp[-1] - rp[0]), "b": 1, "fortran_blocks": False}
 
-    def _set_sparse_device(self, which, row_ptr, col_idx, vals, lower=False):
-        rpb, cib = device_csr_tensors(row_ptr, col_idx, vals, self.n, self.device)
+    def _set_sparse_device(self, which, row_ptr, col_idx, vals, lower=False, keep_map=False):
+        rpb, cib, nnz = _device_csr_tensors(row_ptr, col_idx, vals, self.n, self.device)
+        self._keep_map(which, keep_map)
         import torch
         torch.cuda.current_stream(row_ptr.device).synchronize()
         st = self.lib.fd_engine_set_sparse_device(self.p, C.c_int(which), C.c_int(self.n), C.c_void_p(row_ptr.data_ptr()), C.c_int(rpb),
@@ -251,21 +262,28 @@ class DavidsonEngine:
                                                   C.c_void_p(vals.data_ptr() or None), C.c_int(0), C.c_int(1 if lower else 0))
         if st != 0:
             raise DavidsonHipError(hip_lib().dav_last_error().decode())
+        if keep_map:
+            self._kept[which] = {"count": nnz, "b": 1, "fortran_blocks": False}
 
-    def set_block_sparse(self, which, indptr, indices=None, data=None, lower=False):
+    def set_block_sparse(self, which, indptr, indices=None, data=None, lower=False, keep_map=False):
         """Operator A (which=1) or B (which=2) as a symmetric matrix in BSR form, 0-based (Fortran: engine_set_sparse with a bsr_matrix):
         three arrays - data (nnzb, b, b), row-major blocks - or `indptr` an object with .blocksize (a scipy bsr_matrix), or a
         torch.sparse_bsr_tensor - one on the engine's GPU is built there (Fortran: engine_set_block_sparse_device; a refused matrix
-        raises DavidsonHipError and leaves the operator unset).  lower=True: only the blocks with block column <= block row are given."""
+        raises DavidsonHipError and leaves the operator unset).  lower=True: only the blocks with block column <= block row are given.
+        keep_map=True: as for set_sparse; update_values then takes the blocks as this call does, (nnzb, b, b) row-major."""
         a = indptr if indices is None and data is None else (indptr, indices, data)
         if _is_device_bsr(a):
-            return self._set_block_sparse_device(which, *torch_bsr_parts(a), lower=lower)
+            return self._set_block_sparse_device(which, *torch_bsr_parts(a), lower=lower, keep_map=keep_map)
         b, rp, ci, vv = _bsr_input(a, self.n, lower)
+        self._keep_map(which, keep_map)
         self.lib.fd_engine_set_block_sparse(self.p, C.c_int(which), C.c_int(self.n), C.c_int(b), _i64(rp), _i32(ci), _dp(vv), C.c_int(0),
                                             C.c_int(1 if lower else 0))
+        if keep_map:       # the Fortran door took the blocks in Fortran order: an update transposes them the same way
+            self._kept[which] = {"count": int(rp[-1] - rp[0]) * b * b, "b": b, "fortran_blocks": True}
 
-    def _set_block_sparse_device(self, which, row_ptr, col_idx, vals, lower=False):
-        b, rpb, cib = device_bsr_tensors(row_ptr, col_idx, vals, self.n, self.device)
+    def _set_block_sparse_device(self, which, row_ptr, col_idx, vals, lower=False, keep_map=False):
+        b, rpb, cib, nnzb = _device_bsr_tensors(row_ptr, col_idx, vals, self.n, self.device)
+        self._keep_map(which, keep_map)
         import torch
         torch.cuda.current_stream(row_ptr.device).synchronize()
         st = self.lib.fd_engine_set_block_sparse_device(self.p, C.c_int(which), C.c_int(self.n), C.c_int(b), C.c_void_p(row_ptr.data_ptr()),
@@ -274,6 +292,35 @@ class DavidsonEngine:
                                                         C.c_int(1))
         if st != 0:
             raise DavidsonHipError(hip_lib().dav_last_error().decode())
+        if keep_map:
+            self._kept[which] = {"count": nnzb * b * b, "b": b, "fortran_blocks": False}
+
+    def update_values(self, which, data):
+        """New values of operator A (which=1) or B (which=2) on its kept pattern (Fortran: engine_update_sparse_values /
+        engine_update_sparse_values_device): the operator was set by set_sparse / set_block_sparse with keep_map=True, and `data` is the
+        data of that call with new numbers - for BSR (nnzb, b, b) row-major blocks, or the same flat.  A numpy array (or a CPU tensor)
+        goes through the host entry, a torch tensor on the engine's GPU through the device entry; either works whichever way the
+        operator was set.  float64 only (TypeError); a wrong length is a ValueError, an operator set without keep_map=True a
+        DavidsonHipError - all before the engine is called, and the operator keeps its values.  Diagonal, applies and solves then equal
+        bit for bit those of a fresh set call with `data`."""
+        kept = getattr(self, "_kept", {}).get(which)
+        if kept is None:
+            raise DavidsonHipError(f"update_values: operator {which} was not set with keep_map=True (dav_keep_value_map): it keeps no "
+                                   "value map")
+        host, dev = update_values_array(data, kept["count"], self.device, "update_values")
+        b = kept["b"]
+        if dev is not None:
+            import torch
+            if kept["fortran_blocks"] and b > 1:
+                dev = dev.reshape(-1, b, b).transpose(1, 2).contiguous()
+            torch.cuda.current_stream(dev.device).synchronize()
+            st = self.lib.fd_engine_update_values_device(self.p, C.c_int(which), C.c_void_p(dev.data_ptr() or None))
+            if st != 0:
+                raise DavidsonHipError(hip_lib().dav_last_error().decode())
+            return
+        if kept["fortran_blocks"] and b > 1:
+            host = np.ascontiguousarray(host.reshape(-1, b, b).transpose(0, 2, 1)).reshape(-1)
+        self.lib.fd_engine_update_values(self.p, C.c_int(which), _dp(host) if host.size else (C.c_double * 1)(), C.c_int64(host.size))
 
     def set_correction_policy(self, policy):
         """"all" = the reference's policy (default); "unconverged" = opt-in: correct only the wanted pairs

@@ -273,6 +273,30 @@ int dav_set_operator_bsr(dav_handle_t h, int which, int block_size, const int64_
 int dav_set_operator_bsr_dev(dav_handle_t h, int which, int block_size, const void* block_row_ptr, int row_ptr_bits /* 32 | 64 */,
                              const void* block_col_idx, int col_bits /* 32 | 64 */, const double* vals, int index_base /* 0 or 1 */,
                              int triangle, int block_layout);
+/* New values on the kept pattern of a sparse operator - the loop of an SCF iteration, a parameter scan, a time step, a re-assembly on a
+ * fixed mesh, where the matrix keeps its pattern and only its numbers change.  Purely additive within ABI 109; without
+ * dav_keep_value_map the four set entries above do, store and cost exactly what they did.
+ * dav_keep_value_map is a sticky switch per operator slot (default 0), read by the four sparse set entries when they are called; it has
+ * no effect on an operator that is already set.  With it on, a set call also keeps the VALUE MAP - per entry (CSR) or block (BSR) of this
+ * rank the position it came from in the caller's vals and whether it is a mirrored image: 8 bytes each - and the DIAGONAL SOURCES of the
+ * whole matrix - the positions of the diagonal entries (blocks) in input order: 16 bytes per row (block row) - all released with the
+ * operator.  The operator built is bit for bit the one built without the switch.
+ * dav_update_operator_values takes vals of the LENGTH, ORDER and (BSR) BLOCK LAYOUT of the vals of the set call that built the operator
+ * - the global array on every rank, host memory - and moves the numbers to where that call put them: the stored values (a mirrored block
+ * transposed) and the diagonal (duplicates summed in input order from +0.0, a missing entry +0.0), on the device and for
+ * dav_get_diagonal / dav_init_basis / the DPR preconditioner.  Nothing of the pattern is validated, sorted, allocated or written again,
+ * and the result - values, diagonal, applies, solves - equals bit for bit what a fresh set call with these vals builds.  Scratch: the
+ * device copy of vals and n doubles, from the engine's allocator, released before the call returns; if it cannot be had the call fails
+ * and the operator keeps its old values.  dav_update_operator_values_dev takes the same array from DEVICE memory of the engine's device,
+ * complete when the call is made (a caller that writes it on a stream of its own synchronises first); the pointer is checked before
+ * anything is launched, as dav_set_operator_csr_dev checks its arrays: a null pointer, pageable / pinned / managed memory, another
+ * device or an allocation shorter than 8 bytes per value is refused.  Both calls return after the engine has stopped reading vals.
+ * Refused with a message (dav_last_error): an operator that is not CSR or BSR, or one set without the map - the message names
+ * dav_keep_value_map.  Unlike a refused set call, a refused update leaves the operator SET and usable with its old values.  A changed
+ * pattern is a set call. */
+int dav_keep_value_map(dav_handle_t h, int which, int on);
+int dav_update_operator_values(dav_handle_t h, int which, const double* vals);
+int dav_update_operator_values_dev(dav_handle_t h, int which, const double* vals_dev);
 int dav_get_diagonal(dav_handle_t h, int which, double* diag_out /* n, global */);
 
 /* ---- the per-iteration hot path ---------------------------------------------------------------- */
