@@ -459,6 +459,7 @@ int create_impl(E* e, int device, int64_t n, int max_cols, int gev, int rank, in
   const size_t off_norm = carve(dev_total, sizeof(double) * (size_t)(e->nloc_pad / PG_ROWS) * e->cols_alloc);
   e->h0_cap = std::min(e->cols_alloc, 128);
   const size_t off_h0 = carve(dev_total, sizeof(double) * 2 * (size_t)e->h0_cap * e->h0_cap);
+  const size_t off_gflags = carve(dev_total, sizeof(unsigned long long) * (size_t)guess_flag_words(e->cols_alloc));
   size_t off_sm[N_SMALL], off_smh[N_SMALL];
   for (int i = 0; i < N_SMALL; ++i) off_sm[i] = carve(dev_total, sizeof(double) * e->small_doubles);
   const size_t off_gramh = carve(host_total, sizeof(double) * e->gram_doubles);
@@ -495,6 +496,7 @@ int create_impl(E* e, int device, int64_t n, int max_cols, int gev, int rank, in
   e->agree_pin = (double*)(e->arena_host + off_agree);
   e->h0_dev = (double*)(e->arena + off_h0);
   e->h0_host = (double*)(e->arena_host + off_h0h);
+  e->guess_flags = (unsigned long long*)(e->arena + off_gflags);
   for (int i = 0; i < N_SMALL; ++i) {
     e->sm[i].dev = (double*)(e->arena + off_sm[i]);
     e->sm[i].host = (double*)(e->arena_host + off_smh[i]);
@@ -665,6 +667,7 @@ extern "C" int dav_panel_unit_column(dav_handle_t e, int panel, int col, int k) 
   CHK(check_panel(e, panel, col, 1));
   if (k < 0) return fail("dav_panel_unit_column: bad index");
   if ((size_t)k >= e->basis_order.size()) return DAV_NO_SUCH_ENTRY;       // not an error: the caller falls back to another direction
+  if (panel == DAV_PANEL_X) guess_drop(e);
   const int64_t idx = e->basis_order[(size_t)k];
   int64_t* slot = e->idx_dev + (e->cols_alloc - 1);                        // (dav_init_basis uses the front of idx_dev; stream order keeps them apart)
   HIPCHK(hipMemcpyAsync(slot, &idx, sizeof(int64_t), hipMemcpyHostToDevice, e->stream));
@@ -678,6 +681,7 @@ extern "C" int dav_panel_put(dav_handle_t e, int panel, int c0, int k, const dou
   CHK(bind(e));
   CHK(check_panel(e, panel, c0, k));
   if (ld < e->n) return fail("dav_panel_put: leading dimension too small");
+  if (panel == DAV_PANEL_X) guess_drop(e);
   if (e->nloc > 0) {
     HIPCHK(hipMemcpy2DAsync(panel_ptr(e, panel, c0), sizeof(double) * e->ldp, in + e->row0, sizeof(double) * ld,
                             sizeof(double) * e->nloc, (size_t)k, hipMemcpyHostToDevice, e->stream));

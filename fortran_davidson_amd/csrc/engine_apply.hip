@@ -642,6 +642,7 @@ int apply_impl(E* e, int which, int src_panel, int c0, int k, int dst_panel, int
 extern "C" int dav_apply(dav_handle_t e, int which, int src_panel, int c0, int k, int dst_panel, int d0) {
   if (which < 0 || which > 1) return fail("dav_apply: bad operator id");
   CHK(bind(e));
+  if (dst_panel == DAV_PANEL_X) guess_drop(e);
   return apply_impl(e, which, src_panel, c0, k, dst_panel, d0, true);
 }
 
@@ -651,6 +652,7 @@ extern "C" int dav_apply_inner(dav_handle_t e, int which, int src_panel, int c0,
   CHK(bind(e));
   CHK(check_panel(e, src_panel, c0, k));
   CHK(check_panel(e, dst_panel, d0, k));
+  if (dst_panel == DAV_PANEL_X) guess_drop(e);
   return apply_ptr(e, which, panel_ptr(e, src_panel, c0), k, panel_ptr(e, dst_panel, d0), false, true);
 }
 

@@ -220,6 +220,7 @@ struct CollTrial {
   std::string message[3];
 };
 
+enum { GUESS_NONE = 0, GUESS_ONE_SHOT = 1, GUESS_RESULT = 2 };
 struct Watchdog;
 struct dav_engine {
   Tune tune;
@@ -325,6 +326,13 @@ struct dav_engine {
   int ev_used = 0, ev_open = 0;
   int timing_level = 1;           // 0 = nothing, 1 = block matvec only, 2 = every phase
   bool lazy_x = false;            // dav_set_lazy_ritz_vectors: the Ritz phases compute X only for GJD
+  // Warm start (engine_guess.hip).  A guess lives in the X panel, columns [0, guess_cols), wherever it came from - the host, the
+  // device, the last solve - and this is all the engine remembers of it: how many columns, and whether a caller staged them
+  // (consumed by dav_init_basis_guess) or a solve left them (offered only while dav_keep_result_as_guess is on).  Every call that
+  // writes X outside these entries drops it (guess_drop); setting or updating an operator does not.
+  int guess_cols = 0, guess_tag = GUESS_NONE;
+  int keep_result = 0;            // dav_keep_result_as_guess (sticky)
+  unsigned long long* guess_flags = nullptr;   // device: word 0 = a non-finite entry was seen, words 1.. = one "has a non-zero" bit per column
 };
 typedef dav_engine E;
 
@@ -447,6 +455,9 @@ OpParams op_params(const OpDesc& o);
 int operator_goes(E* e, int which, bool unset = false);
 // ---- engine_sparse.hip -----------------------------------------------------------------------------------
 void sparse_release(E* e, OpDesc& o);
+bool device_array(E* e, const void* p, const char* name, size_t bytes, std::string* why);
+// ---- engine_guess.hip ------------------------------------------------------------------------------------
+static inline void guess_drop(E* e) { e->guess_cols = 0; e->guess_tag = GUESS_NONE; }    // X is about to be written
 // ---- engine_apply.hip ------------------------------------------------------------------------------------
 bool inner_f32_tiles(E* e, OpDesc& o);
 bool sym_wide_enabled(const E* e);
@@ -466,4 +477,5 @@ int ritz_impl(E* e, int m, int ncorr, int lowest, const double* Y, int64_t ldy, 
                      double* resnorm, double* C, int64_t ldc, double* G, int64_t ldg, double* theta_out,
                      double* info_out);
 int restart_contract(E* e, int m, int keep, const double* Mdev, int64_t ldm);
+void basis_order_ensure(E* e, int ncols);
 #pragma GCC visibility pop

@@ -193,13 +193,11 @@ extern "C" int dav_project_ortho(dav_handle_t e, int m, int k, double* H_raw, in
 }
 
 // ---- K6 -----------------------------------------------------------------------------------------
-extern "C" int dav_init_basis(dav_handle_t e, int ncols, int64_t* idx_out) {
-  CHK(bind(e));
-  if (ncols <= 0 || ncols > e->max_cols || ncols > e->n) return fail("dav_init_basis: bad column count");
+// The order the start vectors come from (dav_init_basis, dav_init_basis_guess, dav_panel_unit_column): stable selection of the smallest
+// diagonal entries of A (ties -> lower index first); a property of the resident operator, so it is kept until the diagonal changes
+// (repeated solves on one engine).  Operator A must be set.
+void basis_order_ensure(E* e, int ncols) {
   const std::vector<double>& d = e->diag_host[DAV_OP_A];
-  if (d.empty()) return fail("dav_init_basis: operator A not set");
-  // stable selection of the ncols smallest diagonal entries (ties -> lower index first); a property of the
-  // resident operator, so it is kept until the diagonal changes (repeated solves on one engine)
   if ((int)e->basis_order.size() < ncols) {
     std::vector<int64_t> all((size_t)e->n);
     std::iota(all.begin(), all.end(), 0);
@@ -209,6 +207,13 @@ extern "C" int dav_init_basis(dav_handle_t e, int ncols, int64_t* idx_out) {
     all.resize(keep);
     e->basis_order.swap(all);
   }
+}
+extern "C" int dav_init_basis(dav_handle_t e, int ncols, int64_t* idx_out) {
+  CHK(bind(e));
+  if (ncols <= 0 || ncols > e->max_cols || ncols > e->n) return fail("dav_init_basis: bad column count");
+  const std::vector<double>& d = e->diag_host[DAV_OP_A];
+  if (d.empty()) return fail("dav_init_basis: operator A not set");
+  basis_order_ensure(e, ncols);
   // the tickets of the last-workgroup finishes start every solve from zero (a launch that died half-way must not leave a count behind)
   HIPCHK(hipMemsetAsync(e->counters, 0, sizeof(unsigned) * (GRAM_MAX_COUNTERS + 8), e->stream));
   std::vector<int64_t> order(e->basis_order.begin(), e->basis_order.begin() + ncols);
@@ -304,6 +309,7 @@ int ritz_impl(E* e, int m, int ncorr, int lowest, const double* Y, int64_t ldy, 
   // correction does not read them (DPR, or no correction at all)
   int nx = method == DAV_METHOD_GJD ? ncorr : lowest;
   if (!(e->lazy_x && method != DAV_METHOD_GJD && !dev)) {
+    guess_drop(e);
     PanelGemmArgs a{};
     a.P1 = panel_ptr(e, DAV_PANEL_V, 0); a.ld1 = e->ldp; a.p1 = m; a.M1 = dY; a.tp1 = ldm_y;
     a.p2 = 0;
@@ -387,6 +393,7 @@ extern "C" int dav_ritz_residual_correction(dav_handle_t e, int m, int lowest, c
 extern "C" int dav_panel_select(dav_handle_t e, int panel, int c0, int nsel, const int* sel) {
   CHK(bind(e));
   if (nsel < 0 || (nsel > 0 && !sel)) return fail("dav_panel_select: bad arguments");
+  if (panel == DAV_PANEL_X) guess_drop(e);
   for (int i = 0; i < nsel; ++i) {
     if (sel[i] < i || (i > 0 && sel[i] <= sel[i - 1])) return fail("dav_panel_select: indices must be ascending");
     CHK(check_panel(e, panel, c0 + sel[i], 1));
@@ -480,6 +487,7 @@ extern "C" int dav_panel_transform(dav_handle_t e, int src_panel, int s0, int p,
   CHK(check_panel(e, dst_panel, d0, q));
   if (p <= 0 || q <= 0 || ldm < p) return fail("dav_panel_transform: bad shape");
   if (q > e->cols_alloc) return fail("dav_panel_transform: too many output columns");
+  if (dst_panel == DAV_PANEL_X) guess_drop(e);
   int64_t ld_m;
   CHK(small_upload_image(e, 3, M, ldm, p, q, &ld_m));
   int slot;

@@ -355,7 +355,6 @@ extern "C" int dav_set_operator_bsr(dav_handle_t e, int which, int block_size, c
 // Both entries build the index level with the kernels of k_csr_build.hip - over the rows of a CSR matrix with the value of an entry as
 // payload, over the block rows of a BSR matrix with the source of a block.  Each step returns 0, or non-zero with *why set (the caller
 // refuses the matrix with that message) or *why empty (a HIP failure, already recorded by fail()).
-namespace {
 // a caller's pointer: device memory of this engine's device, large enough where the runtime can tell (before any launch)
 bool device_array(E* e, const void* p, const char* name, size_t bytes, std::string* why) {
   hipPointerAttribute_t at{};
@@ -380,6 +379,7 @@ bool device_array(E* e, const void* p, const char* name, size_t bytes, std::stri
   return true;
 }
 
+namespace {
 // scratch of a build: released on every way out, after the stream has finished with it
 struct BuildScratch {
   hipStream_t st;

@@ -294,3 +294,11 @@ bool launch_small_eig(hipStream_t st, const double* H, int64_t ldh, const double
 void launch_rr_scatter(hipStream_t st, const double* blk, int mt, int k, int c0, double* Hd, int64_t ld);
 void launch_rr_pack(hipStream_t st, const double* Y, int64_t ld, const double* theta, int m, int q, int ldm, int qpad, double* Ypk,
                     double* Y2pk, double* theta_pk, const double* info, double* result_tail);
+// ---- k_guess.hip: ingest of an initial guess -----------------------------------------------------------------------------------------------
+// dst[0:nrows, c] = src[0:nrows, c] (bit for bit), dst[nrows:nrows + npad, c] = +0.0 for c < ncols; flags (guess_flag_words(ncols) words,
+// zeroed by the caller before the first launch of a guess): word 0 |= 1 when an entry is Inf or NaN, word 1 + c / 64 |= 1 << c % 64 when
+// column c holds a non-zero.  16-byte lanes when guess_ingest_wide says both sides allow them, 8-byte lanes otherwise.
+int guess_flag_words(int ncols);
+bool guess_ingest_wide(const double* src, int64_t ldx, const double* dst, int64_t ldd);
+void launch_guess_ingest(hipStream_t st, const double* src, int64_t ldx, int64_t nrows, int ncols, int64_t npad, double* dst, int64_t ldd,
+                         unsigned long long* flags);

@@ -286,6 +286,37 @@ def update_values_array(vals, count, device=None, what="update_operator_values")
     return np.ascontiguousarray(a).reshape(-1), None
 
 
+def guess_array(x, n, device=None, what="set_guess"):
+    """The checks of an initial guess before any library call: float64 (TypeError, never converted), two-dimensional - one column per
+    vector; a one-dimensional array is one column - with n rows (ValueError).  Returns (Fortran-ordered numpy array, None) for host data
+    (numpy, or a torch tensor on the CPU) or (None, (tensor, ldx, ncols)) for a torch tensor on cuda:`device`: a column-major view or
+    copy whose columns lie ldx doubles apart."""
+    if type(x).__module__.startswith("torch"):
+        import torch
+        if x.dtype != torch.float64:
+            raise TypeError(f"{what}: x has dtype {x.dtype}, expected torch.float64")
+        if x.dim() == 1:
+            x = x.reshape(-1, 1)
+        if x.dim() != 2 or x.shape[0] != n or x.shape[1] < 1:
+            raise ValueError(f"{what}: x must have shape ({n}, ncols), it has {tuple(x.shape)}")
+        if x.device.type == "cpu":
+            return np.asfortranarray(x.numpy()), None
+        if x.device.type != "cuda" or (device is not None and x.device.index != device):
+            raise ValueError(f"{what}: x lies on {x.device}, the engine on cuda:{device}")
+        ncols = x.shape[1]
+        if not (x.stride(0) == 1 and (ncols == 1 or x.stride(1) >= n)):
+            x = x.t().contiguous().t()                 # column-major copy
+        return None, (x, n if ncols == 1 else x.stride(1), ncols)
+    a = np.asarray(x)
+    if a.dtype != np.float64:
+        raise TypeError(f"{what}: x has dtype {a.dtype}, expected float64")
+    if a.ndim == 1:
+        a = a.reshape(-1, 1)
+    if a.ndim != 2 or a.shape[0] != n or a.shape[1] < 1:
+        raise ValueError(f"{what}: x must have shape ({n}, ncols), it has {a.shape}")
+    return np.asfortranarray(a), None
+
+
 def _f(a):
     return np.asfortranarray(a, dtype=np.float64)
 
@@ -541,6 +572,49 @@ class CEngine:
         idx = np.zeros(ncols, dtype=np.int64)
         self._chk(self.lib.dav_init_basis(self.h, C.c_int(ncols), idx.ctypes.data_as(C.POINTER(C.c_int64))))
         return idx
+
+    # -- warm start
+    def set_guess(self, x):
+        """dav_set_guess / dav_set_guess_dev: the columns of x (n rows) become the staged guess of the next solve.  A numpy array (or a
+        torch tensor on the CPU) goes through the host entry; a torch tensor on the engine's device through the device entry, after
+        torch's current stream on the device has been synchronised.  float64 only (TypeError, never converted); a wrong row count is a
+        ValueError before the engine is called.  The engine's refusal - too many columns, an entry that is not finite, a column that is
+        entirely zero - is a DavidsonHipError, and a guess staged earlier stays staged."""
+        host, dev = guess_array(x, self.n, self.device)
+        if dev is not None:
+            import torch
+            t, ld, ncols = dev
+            torch.cuda.current_stream(t.device).synchronize()
+            self._chk(self.lib.dav_set_guess_dev(self.h, C.c_void_p(t.data_ptr() or None), C.c_int64(ld), C.c_int(ncols)))
+        else:
+            self._chk(self.lib.dav_set_guess(self.h, _dp(host), C.c_int64(host.shape[0]), C.c_int(host.shape[1])))
+
+    def set_guess_raw(self, x, ldx, ncols):
+        """dav_set_guess with an explicit leading dimension: x a one-dimensional float64 array holding x(ldx, ncols) column-major"""
+        a = np.ascontiguousarray(x, dtype=np.float64)
+        self._chk(self.lib.dav_set_guess(self.h, _dp(a), C.c_int64(ldx), C.c_int(ncols)))
+
+    def set_guess_dev_raw(self, dev_ptr, ldx, ncols):
+        """dav_set_guess_dev with a raw device pointer (e.g. a torch tensor's data_ptr() plus an offset) and leading dimension"""
+        self._chk(self.lib.dav_set_guess_dev(self.h, C.c_void_p(dev_ptr), C.c_int64(ldx), C.c_int(ncols)))
+
+    def keep_result_as_guess(self, on=True):
+        """dav_keep_result_as_guess: sticky; while on, the Ritz vectors a solve leaves in X are the staged guess of the next solve"""
+        self._chk(self.lib.dav_keep_result_as_guess(self.h, C.c_int(1 if on else 0)))
+
+    def guess_columns(self):
+        """dav_guess_columns: staged guess columns, 0 = none"""
+        g = C.c_int(0)
+        self._chk(self.lib.dav_guess_columns(self.h, C.byref(g)))
+        return g.value
+
+    def init_basis_guess(self, ncols):
+        """dav_init_basis_guess: (idx, g) - the staged columns in V[:, 0:g), unit vectors behind them (idx: 0 for a guess column, the
+        1-based position for a unit column); no images: orthonormalise, then expand(0, ncols) and project(0, ncols)"""
+        idx = np.zeros(ncols, dtype=np.int64)
+        g = C.c_int(0)
+        self._chk(self.lib.dav_init_basis_guess(self.h, C.c_int(ncols), idx.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(g)))
+        return idx, g.value
 
     def apply(self, which, src_panel, c0, k, dst_panel, d0):
         self._chk(self.lib.dav_apply(self.h, C.c_int(which), C.c_int(src_panel), C.c_int(c0), C.c_int(k),

@@ -29,7 +29,8 @@ module davidson_device
        engine_set_correction_policy, &
        engine_generate_diagonal_dominant, engine_set_hashed_operator, engine_set_harness_operator, &
        engine_set_identity, engine_set_device_operator, engine_comm_unique_id, engine_comm_init, &
-       generalized_eigensolver_device, davidson_device_loop, basis_capacity, davidson_free_buffers
+       generalized_eigensolver_device, generalized_eigensolver_device_guess, device_solve_impl, davidson_device_loop, basis_capacity, davidson_free_buffers, &
+       engine_set_initial_vectors, engine_set_initial_vectors_device, engine_keep_result_as_guess, stage_initial_vectors
 
   !> The N-long side of the block orthonormalisation (davidson_ortho: ortho_backend) on the engine's panels: K2 Gram launches, K3
   !> block updates, replacement columns written into the basis panel
@@ -53,11 +54,22 @@ module davidson_device
 
 contains
 
+  !> initial_vectors= of the front ends: the leading columns of x that a start basis of 2 * lowest columns (and the engine) can hold
+  subroutine stage_initial_vectors(eng, x, lowest)
+    type(davidson_engine), intent(inout) :: eng
+    real(dp), dimension(:, :), intent(in) :: x
+    integer, intent(in) :: lowest
+    integer :: g
+    g = min(size(x, 2), 2 * lowest, eng%max_cols)
+    if (g >= 1) call engine_set_initial_vectors(eng, x(:, 1:g))
+  end subroutine stage_initial_vectors
+
   !> Solve with the operators already resident behind `eng` (third specific of the generic).
   !> Argument meaning as generalized_eigensolver_dense; `eigenvectors` is optional so that a
   !> benchmark can leave the Ritz vectors on the device.
-  subroutine generalized_eigensolver_device(eng, eigenvalues, eigenvectors, lowest, method, max_iterations, &
-       tolerance, iters, max_dim_sub)
+  !> (the body of generalized_eigensolver_device and of its _guess twin; initial_vectors present: engine_set_initial_vectors first)
+  subroutine device_solve_impl(eng, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, initial_vectors)
     type(davidson_engine), intent(inout) :: eng
     integer, intent(in) :: lowest
     real(dp), dimension(lowest), intent(out) :: eigenvalues
@@ -67,6 +79,7 @@ contains
     real(dp), intent(in) :: tolerance
     integer, intent(out) :: iters
     integer, intent(in), optional :: max_dim_sub
+    real(dp), dimension(:, :), intent(in), optional :: initial_vectors
     integer :: max_dim
     max_dim = 10 * lowest
     if (present(max_dim_sub)) max_dim = max_dim_sub
@@ -74,6 +87,7 @@ contains
        print *, "generalized_eigensolver: engine created for a narrower basis than lowest/max_dim_sub need"
        error stop
     end if
+    if (present(initial_vectors)) call stage_initial_vectors(eng, initial_vectors, lowest)
     ! stored matrix: the dense driver's sticky convergence flags (src/davidson.f90:176); matrix-free operator A:
     ! the matrix-free driver's all-at-once test (:416)
     call davidson_device_loop(eng%h, eng%n, lowest, method, max_iterations, tolerance, iters, max_dim, &
@@ -83,7 +97,41 @@ contains
        call check_dav(dav_panel_get(eng%h, DAV_PANEL_X, 0_c_int, int(lowest, c_int), eigenvectors, &
             int(size(eigenvectors, 1), c_int64_t)), "dav_panel_get")
     end if
+  end subroutine device_solve_impl
+
+  !> The specific of the generic with the reference's argument list (device_solve_impl does the work).
+  subroutine generalized_eigensolver_device(eng, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub)
+    integer, intent(in) :: lowest
+    type(davidson_engine), intent(inout) :: eng
+    real(dp), dimension(:, :), intent(out), optional :: eigenvectors
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    call device_solve_impl(eng, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub)
   end subroutine generalized_eigensolver_device
+
+  !> The same with initial_vectors= (keyword; not in the reference): the solve starts from these columns instead of unit vectors.
+  !> A specific of its own, so that the one above keeps the reference's argument list - and its binary interface - exactly.
+  subroutine generalized_eigensolver_device_guess(eng, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, initial_vectors)
+    integer, intent(in) :: lowest
+    type(davidson_engine), intent(inout) :: eng
+    real(dp), dimension(:, :), intent(out), optional :: eigenvectors
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    real(dp), dimension(:, :), intent(in) :: initial_vectors
+    call device_solve_impl(eng, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub, initial_vectors)
+  end subroutine generalized_eigensolver_device_guess
 
   !> The outer loop (control flow of src/davidson.f90:138-229 / :375-441) on a prepared engine.
   !> sticky = .true. reproduces the dense path's sticky convergence flags (:176), .false. the
@@ -110,6 +158,7 @@ contains
 
     integer :: m, kt, i, j, cap, initial_dimension, meth, inner, phase, pol, ncorr, nvec, nrestart, opass
     integer :: refresh_every
+    integer(c_int) :: nstaged, nguess
     integer(c_int), allocatable :: sel(:)
     integer(c_int) :: sweeps
     logical :: drr
@@ -171,12 +220,30 @@ contains
     ! dav_agree_next ride on all-reduces whose element count they determine - ranks that differ in `lowest` or `max_dim` would enter
     ! those with different counts) whenever they differ from what the engine verified last: the first solve always, repeated solves
     ! with the same inputs never (dav_agree_inputs); a single rank: a no-op
+    ! (the staged guess columns are an input like the others: a rank that differs stops with the message instead of hanging its peers)
+    call check_dav(dav_guess_columns(h, nstaged), "dav_guess_columns")
     call check_dav(dav_agree_inputs(h, [real(n, dp), real(lowest, dp), real(max_dim, dp), real(max_iterations, dp), tolerance, &
-         real(pol, dp), real(meth, dp), merge(1.0_dp, 0.0_dp, sticky), merge(1.0_dp, 0.0_dp, gev)], 9_c_int), "dav_agree_inputs")
+         real(pol, dp), real(meth, dp), merge(1.0_dp, 0.0_dp, sticky), merge(1.0_dp, 0.0_dp, gev), real(nstaged, dp)], 10_c_int), &
+         "dav_agree_inputs")
 
-    ! 1. initial basis: unit vectors at the lowest diagonal entries; W0 = A*V0
     m = initial_dimension
     t0 = tick()
+    if (nstaged > 0) then
+       ! 1w. warm start: the staged guess columns first, unit vectors at the lowest diagonal entries behind them; the block is made
+       ! Euclidean-orthonormal like every block that joins the basis (a B-orthonormal guess is simply re-orthonormalised; dependent or
+       ! duplicate columns - also one that equals a fill unit vector - are completed by the rules of davidson_ortho), swept and
+       ! projected: from here on the loop runs from the basis it finds, whatever the method, the policy or where the operators live
+       call check_dav(dav_init_basis_guess(h, int(m, c_int), idx, nguess), "dav_init_basis_guess")
+       call block_orthonormalise(dev, n, 0, m)
+       call check_dav(dav_expand(h, 0_c_int, int(m, c_int)), "dav_expand")
+       if (host_ops) call apply_host_block(h, n, 0, m, fun_a, fun_b)
+       if (drr) then
+          call check_dav(dav_project_dev(h, 0_c_int, int(m, c_int)), "dav_project")
+       else
+          call check_dav(dav_project(h, 0_c_int, int(m, c_int), hm, ld, sm, ld), "dav_project")
+       end if
+    else
+    ! 1. initial basis: unit vectors at the lowest diagonal entries; W0 = A*V0
     call check_dav(dav_init_basis(h, int(m, c_int), idx), "dav_init_basis")
     if (host_ops) call apply_host_block(h, n, 0, m, fun_a, fun_b)
     ! 2. projected matrices
@@ -184,6 +251,7 @@ contains
        call check_dav(dav_project_dev(h, 0_c_int, int(m, c_int)), "dav_project")
     else
        call check_dav(dav_project(h, 0_c_int, int(m, c_int), hm, ld, sm, ld), "dav_project")
+    end if
     end if
     call lap(phase_s, t0, 1)
 
@@ -452,6 +520,9 @@ contains
     end if
     if (present(phase_seconds)) phase_seconds = phase_s
     call check_dav(dav_set_lazy_ritz_vectors(h, 0_c_int), "dav_set_lazy_ritz_vectors")
+    ! X columns 1..lowest now hold the Ritz vectors this solve returns: what the next solve starts from when the caller asked for that
+    ! (dav_keep_result_as_guess).  (A locking solve that ran out of iterations may not have assembled them.)
+    if (done .or. pol /= POLICY_LOCKING) call check_dav(dav_mark_result_as_guess(h, int(lowest, c_int)), "dav_mark_result_as_guess")
 
   contains
 
@@ -882,18 +953,20 @@ module davidson_dense
   use davidson_device
   implicit none
   private
-  public :: generalized_eigensolver_dense
+  public :: generalized_eigensolver_dense, generalized_eigensolver_dense_guess
 
 contains
 
   !> Dense front-end, argument list of the reference (src/davidson.f90:51-52, :74-83): the matrices
   !> are uploaded to HBM, solved there and everything is released before returning (the reference
   !> keeps no state across calls either, src/davidson.f90:238-244).
-  subroutine generalized_eigensolver_dense(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
-       tolerance, iters, max_dim_sub, second_matrix)
+  !> (the body of the specific below and of its _guess twin, which passes initial_vectors)
+  subroutine dense_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix, initial_vectors)
     integer, intent(in) :: lowest
     real(dp), dimension(:, :), intent(in) :: matrix
     real(dp), dimension(:, :), intent(in), optional :: second_matrix
+    real(dp), dimension(:, :), intent(in), optional :: initial_vectors
     real(dp), dimension(lowest), intent(out) :: eigenvalues
     real(dp), dimension(:, :), intent(out) :: eigenvectors
     integer, intent(in) :: max_iterations
@@ -932,8 +1005,8 @@ contains
     call engine_set_dense(eng, 1, matrix)
     if (present(second_matrix)) call engine_set_dense(eng, 2, second_matrix)
     t(3) = wall()
-    call generalized_eigensolver_device(eng, eigenvalues, eigenvectors, lowest, method, max_iterations, &
-         tolerance, iters, max_dim)
+    call device_solve_impl(eng, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+         tolerance, iters, max_dim, initial_vectors)
     t(4) = wall()
     call engine_destroy(eng)
     t(5) = wall()
@@ -957,7 +1030,43 @@ contains
       on = (stat == 0 .and. length > 0)
     end function dense_verbose
 
+  end subroutine dense_solve_impl
+
+  !> The specific of the generic with the reference's argument list (dense_solve_impl does the work).
+  subroutine generalized_eigensolver_dense(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix)
+    integer, intent(in) :: lowest
+    real(dp), dimension(:, :), intent(in) :: matrix
+    real(dp), dimension(:, :), intent(in), optional :: second_matrix
+    real(dp), dimension(:, :), intent(out) :: eigenvectors
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    call dense_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub, second_matrix)
   end subroutine generalized_eigensolver_dense
+
+  !> The same with initial_vectors= (keyword; not in the reference): the solve starts from these columns instead of unit vectors.
+  !> A specific of its own, so that the one above keeps the reference's argument list - and its binary interface - exactly.
+  subroutine generalized_eigensolver_dense_guess(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix, initial_vectors)
+    integer, intent(in) :: lowest
+    real(dp), dimension(:, :), intent(in) :: matrix
+    real(dp), dimension(:, :), intent(in), optional :: second_matrix
+    real(dp), dimension(:, :), intent(out) :: eigenvectors
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    real(dp), dimension(:, :), intent(in) :: initial_vectors
+    call dense_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub, second_matrix, initial_vectors)
+  end subroutine generalized_eigensolver_dense_guess
 
 end module davidson_dense
 
@@ -969,7 +1078,7 @@ module davidson_free
   use davidson_device
   implicit none
   private
-  public :: generalized_eigensolver_free, free_matmul
+  public :: generalized_eigensolver_free, generalized_eigensolver_free_guess, free_matmul
 
 contains
 
@@ -979,9 +1088,11 @@ contains
   !> (the reference re-applies both operators to the whole basis each iteration, :378-379).
   !> As in the reference the problem is always generalized and the correction always DPR (:428),
   !> and convergence is tested on all pairs at once (:416).
-  subroutine generalized_eigensolver_free(fun_matrix_gemv, eigenvalues, ritz_vectors, lowest, method, &
-       max_iterations, tolerance, iters, max_dim_sub, fun_second_matrix_gemv)
+  !> (the body of the specific below and of its _guess twin, which passes initial_vectors)
+  subroutine free_solve_impl(fun_matrix_gemv, eigenvalues, ritz_vectors, lowest, method, &
+       max_iterations, tolerance, iters, max_dim_sub, fun_second_matrix_gemv, initial_vectors)
     integer, intent(in) :: lowest
+    real(dp), dimension(:, :), intent(in), optional :: initial_vectors
     real(dp), dimension(lowest), intent(out) :: eigenvalues
     real(dp), dimension(:, :), intent(out) :: ritz_vectors
     integer, intent(in) :: max_iterations
@@ -1016,12 +1127,69 @@ contains
     call engine_create(eng, n, lowest, max_dim, .true., env_device())
     call check_dav(dav_set_operator_host(eng%h, DAV_OP_A, diag_a), "dav_set_operator_host")
     call check_dav(dav_set_operator_host(eng%h, DAV_OP_B, diag_b), "dav_set_operator_host")
+    if (present(initial_vectors)) call stage_initial_vectors(eng, initial_vectors, lowest)
     call davidson_device_loop(eng%h, n, lowest, method, max_iterations, tolerance, iters, max_dim, .true., &
          .false., eigenvalues, fun_matrix_gemv, fun_second_matrix_gemv, eng%policy, eng%device_rr)
     call check_dav(dav_panel_get(eng%h, DAV_PANEL_X, 0_c_int, int(lowest, c_int), ritz_vectors, &
          int(size(ritz_vectors, 1), c_int64_t)), "dav_panel_get")
     call engine_destroy(eng)
+  end subroutine free_solve_impl
+
+  !> The specific of the generic with the reference's argument list (free_solve_impl does the work).
+  subroutine generalized_eigensolver_free(fun_matrix_gemv, eigenvalues, ritz_vectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, fun_second_matrix_gemv)
+    integer, intent(in) :: lowest
+    real(dp), dimension(:, :), intent(out) :: ritz_vectors
+    integer, intent(in), optional :: max_dim_sub
+    interface
+       function fun_matrix_gemv(input_vect) result(output_vect)
+         use numeric_kinds, only: dp
+         real(dp), dimension(:, :), intent(in) :: input_vect
+         real(dp), dimension(size(input_vect, 1), size(input_vect, 2)) :: output_vect
+       end function fun_matrix_gemv
+       function fun_second_matrix_gemv(input_vect) result(output_vect)
+         use numeric_kinds, only: dp
+         real(dp), dimension(:, :), intent(in) :: input_vect
+         real(dp), dimension(size(input_vect, 1), size(input_vect, 2)) :: output_vect
+       end function fun_second_matrix_gemv
+    end interface
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    call free_solve_impl(fun_matrix_gemv, eigenvalues, ritz_vectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub, fun_second_matrix_gemv)
   end subroutine generalized_eigensolver_free
+
+  !> The same with initial_vectors= (keyword; not in the reference): the solve starts from these columns instead of unit vectors.
+  !> A specific of its own, so that the one above keeps the reference's argument list - and its binary interface - exactly.
+  subroutine generalized_eigensolver_free_guess(fun_matrix_gemv, eigenvalues, ritz_vectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, fun_second_matrix_gemv, initial_vectors)
+    integer, intent(in) :: lowest
+    real(dp), dimension(:, :), intent(out) :: ritz_vectors
+    integer, intent(in), optional :: max_dim_sub
+    interface
+       function fun_matrix_gemv(input_vect) result(output_vect)
+         use numeric_kinds, only: dp
+         real(dp), dimension(:, :), intent(in) :: input_vect
+         real(dp), dimension(size(input_vect, 1), size(input_vect, 2)) :: output_vect
+       end function fun_matrix_gemv
+       function fun_second_matrix_gemv(input_vect) result(output_vect)
+         use numeric_kinds, only: dp
+         real(dp), dimension(:, :), intent(in) :: input_vect
+         real(dp), dimension(size(input_vect, 1), size(input_vect, 2)) :: output_vect
+       end function fun_second_matrix_gemv
+    end interface
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    real(dp), dimension(:, :), intent(in) :: initial_vectors
+    call free_solve_impl(fun_matrix_gemv, eigenvalues, ritz_vectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub, fun_second_matrix_gemv, initial_vectors)
+  end subroutine generalized_eigensolver_free_guess
 
   !> Diagonal of an operator known only through its block apply: same N unit-vector probes as
   !> extract_diagonal_free (src/davidson.f90:490-523), sent through the callback 64 at a time.
@@ -1087,15 +1255,16 @@ module davidson_csr
   use davidson_sparse
   implicit none
   private
-  public :: generalized_eigensolver_sparse, generalized_eigensolver_bsr
+  public :: generalized_eigensolver_sparse, generalized_eigensolver_bsr, generalized_eigensolver_sparse_guess, generalized_eigensolver_bsr_guess
 
 contains
 
   !> Sparse front-end: the argument list of generalized_eigensolver_dense with csr_matrix operators (module davidson_sparse).  The
   !> matrices go to HBM as CSR rows, are solved there with the engine's CSR kernel and are released before returning.
-  subroutine generalized_eigensolver_sparse(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
-       tolerance, iters, max_dim_sub, second_matrix)
+  subroutine sparse_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix, initial_vectors)
     integer, intent(in) :: lowest
+    real(dp), dimension(:, :), intent(in), optional :: initial_vectors
     type(csr_matrix), intent(in) :: matrix
     type(csr_matrix), intent(in), optional :: second_matrix
     real(dp), dimension(lowest), intent(out) :: eigenvalues
@@ -1114,16 +1283,53 @@ contains
     call engine_create(eng, matrix%n, lowest, max_dim, present(second_matrix), env_device())
     call engine_set_sparse(eng, 1, matrix)
     if (present(second_matrix)) call engine_set_sparse(eng, 2, second_matrix)
-    call generalized_eigensolver_device(eng, eigenvalues, eigenvectors, lowest, method, max_iterations, &
-         tolerance, iters, max_dim)
+    call device_solve_impl(eng, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+         tolerance, iters, max_dim, initial_vectors)
     call engine_destroy(eng)
+  end subroutine sparse_solve_impl
+
+  !> The specific of the generic with the reference's argument list (sparse_solve_impl does the work).
+  subroutine generalized_eigensolver_sparse(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix)
+    integer, intent(in) :: lowest
+    type(csr_matrix), intent(in) :: matrix
+    type(csr_matrix), intent(in), optional :: second_matrix
+    real(dp), dimension(:, :), intent(out) :: eigenvectors
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    call sparse_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub, second_matrix)
   end subroutine generalized_eigensolver_sparse
+
+  !> The same with initial_vectors= (keyword; not in the reference): the solve starts from these columns instead of unit vectors.
+  !> A specific of its own, so that the one above keeps the reference's argument list - and its binary interface - exactly.
+  subroutine generalized_eigensolver_sparse_guess(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix, initial_vectors)
+    integer, intent(in) :: lowest
+    type(csr_matrix), intent(in) :: matrix
+    type(csr_matrix), intent(in), optional :: second_matrix
+    real(dp), dimension(:, :), intent(out) :: eigenvectors
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    real(dp), dimension(:, :), intent(in) :: initial_vectors
+    call sparse_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub, second_matrix, initial_vectors)
+  end subroutine generalized_eigensolver_sparse_guess
 
   !> Block-sparse front-end: the same argument list with bsr_matrix operators (module davidson_sparse).  The matrices go to HBM as
   !> blocks, are solved there with the engine's matrix-core BSR kernel and are released before returning.
-  subroutine generalized_eigensolver_bsr(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
-       tolerance, iters, max_dim_sub, second_matrix)
+  subroutine bsr_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix, initial_vectors)
     integer, intent(in) :: lowest
+    real(dp), dimension(:, :), intent(in), optional :: initial_vectors
     type(bsr_matrix), intent(in) :: matrix
     type(bsr_matrix), intent(in), optional :: second_matrix
     real(dp), dimension(lowest), intent(out) :: eigenvalues
@@ -1142,24 +1348,63 @@ contains
     call engine_create(eng, matrix%n, lowest, max_dim, present(second_matrix), env_device())
     call engine_set_sparse(eng, 1, matrix)
     if (present(second_matrix)) call engine_set_sparse(eng, 2, second_matrix)
-    call generalized_eigensolver_device(eng, eigenvalues, eigenvectors, lowest, method, max_iterations, &
-         tolerance, iters, max_dim)
+    call device_solve_impl(eng, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+         tolerance, iters, max_dim, initial_vectors)
     call engine_destroy(eng)
+  end subroutine bsr_solve_impl
+
+  !> The specific of the generic with the reference's argument list (bsr_solve_impl does the work).
+  subroutine generalized_eigensolver_bsr(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix)
+    integer, intent(in) :: lowest
+    type(bsr_matrix), intent(in) :: matrix
+    type(bsr_matrix), intent(in), optional :: second_matrix
+    real(dp), dimension(:, :), intent(out) :: eigenvectors
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    call bsr_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub, second_matrix)
   end subroutine generalized_eigensolver_bsr
+
+  !> The same with initial_vectors= (keyword; not in the reference): the solve starts from these columns instead of unit vectors.
+  !> A specific of its own, so that the one above keeps the reference's argument list - and its binary interface - exactly.
+  subroutine generalized_eigensolver_bsr_guess(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix, initial_vectors)
+    integer, intent(in) :: lowest
+    type(bsr_matrix), intent(in) :: matrix
+    type(bsr_matrix), intent(in), optional :: second_matrix
+    real(dp), dimension(:, :), intent(out) :: eigenvectors
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    real(dp), dimension(:, :), intent(in) :: initial_vectors
+    call bsr_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub, second_matrix, initial_vectors)
+  end subroutine generalized_eigensolver_bsr_guess
 
 end module davidson_csr
 
 
 module davidson
   use numeric_kinds, only: dp
-  use davidson_dense, only: generalized_eigensolver_dense
-  use davidson_free, only: generalized_eigensolver_free
-  use davidson_device, only: generalized_eigensolver_device, davidson_free_buffers
+  use davidson_dense, only: generalized_eigensolver_dense, generalized_eigensolver_dense_guess
+  use davidson_free, only: generalized_eigensolver_free, generalized_eigensolver_free_guess
+  use davidson_device, only: generalized_eigensolver_device, generalized_eigensolver_device_guess, davidson_free_buffers, engine_set_initial_vectors, &
+       engine_set_initial_vectors_device, engine_keep_result_as_guess
   use davidson_sparse, only: csr_matrix, bsr_matrix
-  use davidson_csr, only: generalized_eigensolver_sparse, generalized_eigensolver_bsr
+  use davidson_csr, only: generalized_eigensolver_sparse, generalized_eigensolver_bsr, generalized_eigensolver_sparse_guess, &
+       generalized_eigensolver_bsr_guess
   implicit none
   private
-  public :: generalized_eigensolver, davidson_free_buffers, csr_matrix, bsr_matrix
+  public :: generalized_eigensolver, davidson_free_buffers, csr_matrix, bsr_matrix, engine_set_initial_vectors, &
+       engine_set_initial_vectors_device, engine_keep_result_as_guess
 
   !> Generic of the reference (src/davidson.f90:601-625), resolved by the first argument: a matrix,
   !> a block-apply procedure, (new) a device-resident `davidson_engine`, or (new) a sparse `csr_matrix` / `bsr_matrix`.
@@ -1169,6 +1414,11 @@ module davidson
      procedure generalized_eigensolver_device
      procedure generalized_eigensolver_sparse
      procedure generalized_eigensolver_bsr
+     procedure generalized_eigensolver_dense_guess
+     procedure generalized_eigensolver_free_guess
+     procedure generalized_eigensolver_device_guess
+     procedure generalized_eigensolver_sparse_guess
+     procedure generalized_eigensolver_bsr_guess
   end interface generalized_eigensolver
 
 end module davidson

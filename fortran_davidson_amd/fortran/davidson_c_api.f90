@@ -372,6 +372,122 @@ contains
     stat = int(st, c_int)
   end function fd_engine_update_values_device
 
+  !> engine_set_initial_vectors(eng, x, stat) with x(n, ncols): returns the engine's status (0 = staged; otherwise dav_last_error says
+  !> why and a guess staged earlier stays staged) instead of stopping the process
+  function fd_engine_set_initial_vectors(p, x, ncols) result(stat) bind(C, name="fd_engine_set_initial_vectors")
+    type(c_ptr), value :: p
+    integer(c_int), value :: ncols
+    real(c_double), intent(in), target :: x(*)
+    integer(c_int) :: stat
+    type(davidson_engine), pointer :: eng
+    real(c_double), pointer :: xx(:, :)
+    integer :: st
+    call c_f_pointer(p, eng)
+    call c_f_pointer(c_loc(x), xx, [eng%n, int(ncols)])
+    call engine_set_initial_vectors(eng, xx, stat=st)
+    stat = int(st, c_int)
+  end function fd_engine_set_initial_vectors
+
+  !> engine_set_initial_vectors_device(eng, ptr, ldx, ncols, stat): the same from device memory, status returned
+  function fd_engine_set_initial_vectors_device(p, ptr, ldx, ncols) result(stat) bind(C, name="fd_engine_set_initial_vectors_device")
+    type(c_ptr), value :: p, ptr
+    integer(c_int), value :: ldx, ncols
+    integer(c_int) :: stat
+    type(davidson_engine), pointer :: eng
+    integer :: st
+    call c_f_pointer(p, eng)
+    call engine_set_initial_vectors_device(eng, ptr, int(ldx), int(ncols), stat=st)
+    stat = int(st, c_int)
+  end function fd_engine_set_initial_vectors_device
+
+  !> engine_keep_result_as_guess(eng, on)
+  subroutine fd_engine_keep_result_as_guess(p, on) bind(C, name="fd_engine_keep_result_as_guess")
+    type(c_ptr), value :: p
+    integer(c_int), value :: on
+    type(davidson_engine), pointer :: eng
+    call c_f_pointer(p, eng)
+    call engine_keep_result_as_guess(eng, on /= 0)
+  end subroutine fd_engine_keep_result_as_guess
+
+  !> The one-call front ends with initial_vectors= : x0(n, g) is the guess; everything else as in the doors they extend.
+  subroutine fd_dense_solve_guess(n, a, has_b, b, lowest, method, max_it, tol, max_dim, g, x0, evals, evecs, iters) &
+       bind(C, name="fd_dense_solve_guess")
+    integer(c_int), value :: n, has_b, lowest, method, max_it, max_dim, g
+    real(c_double), value :: tol
+    real(c_double), intent(in) :: a(n, n), b(n, *), x0(n, g)
+    real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
+    integer(c_int), intent(out) :: iters
+    integer :: it, md
+    md = max_dim
+    if (md < 0) md = 10 * lowest
+    if (has_b /= 0) then
+       call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, md, b(:, 1:n), initial_vectors=x0)
+    else
+       call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, md, initial_vectors=x0)
+    end if
+    iters = it
+  end subroutine fd_dense_solve_guess
+
+  subroutine fd_sparse_solve_guess(n, rp, col, vals, has_b, rpb, colb, valsb, base, lower, lowest, method, max_it, tol, max_dim, g, x0, &
+       evals, evecs, iters) bind(C, name="fd_sparse_solve_guess")
+    integer(c_int), value :: n, has_b, base, lower, lowest, method, max_it, max_dim, g
+    integer(c_int64_t), intent(in) :: rp(n + 1), rpb(*)
+    integer(c_int32_t), intent(in) :: col(*), colb(*)
+    real(c_double), intent(in) :: vals(*), valsb(*), x0(n, g)
+    real(c_double), value :: tol
+    real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
+    integer(c_int), intent(out) :: iters
+    type(csr_matrix) :: a, b
+    integer :: it, md
+    md = max_dim
+    if (md < 0) md = 10 * lowest
+    a = csr_from_c(n, rp, col, vals, base, lower)
+    if (has_b /= 0) then
+       b = csr_from_c(n, rpb, colb, valsb, base, lower)
+       call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, md, b, initial_vectors=x0)
+    else
+       call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, md, initial_vectors=x0)
+    end if
+    iters = it
+  end subroutine fd_sparse_solve_guess
+
+  subroutine fd_bsr_solve_guess(n, b, rp, col, vals, has_b, rpb, colb, valsb, base, lower, lowest, method, max_it, tol, max_dim, g, x0, &
+       evals, evecs, iters) bind(C, name="fd_bsr_solve_guess")
+    integer(c_int), value :: n, b, has_b, base, lower, lowest, method, max_it, max_dim, g
+    integer(c_int64_t), intent(in) :: rp(*), rpb(*)
+    integer(c_int32_t), intent(in) :: col(*), colb(*)
+    real(c_double), intent(in) :: vals(*), valsb(*), x0(n, g)
+    real(c_double), value :: tol
+    real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
+    integer(c_int), intent(out) :: iters
+    type(bsr_matrix) :: a, bm
+    integer :: it, md
+    md = max_dim
+    if (md < 0) md = 10 * lowest
+    a = bsr_from_c(n, b, rp, col, vals, base, lower)
+    if (has_b /= 0) then
+       bm = bsr_from_c(n, b, rpb, colb, valsb, base, lower)
+       call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, md, bm, initial_vectors=x0)
+    else
+       call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, md, initial_vectors=x0)
+    end if
+    iters = it
+  end subroutine fd_bsr_solve_guess
+
+  subroutine fd_free_solve_guess(n, fa, fb, lowest, max_it, tol, max_dim, g, x0, evals, evecs, iters) bind(C, name="fd_free_solve_guess")
+    integer(c_int), value :: n, lowest, max_it, max_dim, g
+    type(c_funptr), value :: fa, fb
+    real(c_double), value :: tol
+    real(c_double), intent(in) :: x0(n, g)
+    real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
+    integer(c_int), intent(out) :: iters
+    integer :: it
+    call c_f_procpointer(fa, cb_a)
+    call c_f_procpointer(fb, cb_b)
+    call generalized_eigensolver(apply_cb_a, evals, evecs, lowest, "DPR", max_it, tol, it, max_dim, apply_cb_b, initial_vectors=x0)
+    iters = it
+  end subroutine fd_free_solve_guess
+
   !> kind 0: dense generated in HBM, 1: hashed matrix-free operator, 2: harness operator, 3: identity
   subroutine fd_engine_set_operator(p, which, kind, seed, sparsity, use_diag_val, diag_val) &
        bind(C, name="fd_engine_set_operator")

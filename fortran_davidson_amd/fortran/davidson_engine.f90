@@ -11,7 +11,8 @@ module davidson_engine_setup
   public :: davidson_engine, engine_create, engine_destroy, engine_set_dense, engine_set_storage, fits_as_full_rows, engine_set_device_rr, &
        engine_set_inner_precision, engine_read_matrix, engine_dense_begin, engine_dense_put_rows, engine_dense_end, &
        engine_set_correction_policy, engine_generate_diagonal_dominant, engine_set_hashed_operator, engine_set_harness_operator, &
-       engine_set_identity, engine_set_device_operator, engine_comm_unique_id, engine_comm_init, davidson_free_buffers
+       engine_set_identity, engine_set_device_operator, engine_comm_unique_id, engine_comm_init, davidson_free_buffers, &
+       engine_set_initial_vectors, engine_set_initial_vectors_device, engine_keep_result_as_guess
 
   !> Handle of a device-resident problem: operators A (and B) plus all work panels in HBM.
   type :: davidson_engine
@@ -322,5 +323,52 @@ contains
     end if
     call check_dav(dav_set_operator_device(eng%h, int(which - 1, c_int), fn, ctx, diag), "dav_set_operator_device")
   end subroutine engine_set_device_operator
+
+  !> Warm start: the next solve on this engine begins from the columns of x (n rows; the whole array on every rank) instead of unit
+  !> vectors - the eigenvectors of the previous step of an SCF iteration, a parameter scan, a time loop.  The columns need not be
+  !> orthonormal (nor B-orthonormal) or independent; of a guess wider than the start basis, 2 * lowest, the leading columns are used.
+  !> One-shot: the solve consumes it.  stat present: a refused guess - more columns than the engine's basis holds, an entry that is not
+  !> finite, a column that is entirely zero - returns its non-zero status here (dav_last_error says why; a guess staged earlier
+  !> stays staged), otherwise the program stops.
+  subroutine engine_set_initial_vectors(eng, x, stat)
+    type(davidson_engine), intent(inout) :: eng
+    real(dp), dimension(:, :), contiguous, intent(in) :: x
+    integer, intent(out), optional :: stat
+    integer(c_int) :: ierr
+    if (size(x, 1) /= eng%n) then
+       print *, "engine_set_initial_vectors: x must have ", eng%n, " rows"
+       error stop
+    end if
+    ierr = dav_set_guess(eng%h, x, int(size(x, 1), c_int64_t), int(size(x, 2), c_int))
+    if (present(stat)) then
+       stat = int(ierr)
+    else
+       call check_dav(ierr, "dav_set_guess")
+    end if
+  end subroutine engine_set_initial_vectors
+
+  !> The same with x(ldx, ncols) in device memory of the engine's device, complete when the call is made and free again when it
+  !> returns (the engine checks the pointer before it launches anything).
+  subroutine engine_set_initial_vectors_device(eng, ptr, ldx, ncols, stat)
+    type(davidson_engine), intent(inout) :: eng
+    type(c_ptr), intent(in) :: ptr
+    integer, intent(in) :: ldx, ncols
+    integer, intent(out), optional :: stat
+    integer(c_int) :: ierr
+    ierr = dav_set_guess_dev(eng%h, ptr, int(ldx, c_int64_t), int(ncols, c_int))
+    if (present(stat)) then
+       stat = int(ierr)
+    else
+       call check_dav(ierr, "dav_set_guess_dev")
+    end if
+  end subroutine engine_set_initial_vectors_device
+
+  !> Sticky switch (default off): while it is on, every solve on this engine starts from the Ritz vectors the previous solve left in
+  !> HBM - nothing is copied - as long as nothing else has written that panel since.  Setting or updating an operator keeps them.
+  subroutine engine_keep_result_as_guess(eng, on)
+    type(davidson_engine), intent(inout) :: eng
+    logical, intent(in) :: on
+    call check_dav(dav_keep_result_as_guess(eng%h, merge(1_c_int, 0_c_int, on)), "dav_keep_result_as_guess")
+  end subroutine engine_keep_result_as_guess
 
 end module davidson_engine_setup

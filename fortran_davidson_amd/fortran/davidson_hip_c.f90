@@ -268,6 +268,54 @@ module davidson_hip_c
        integer(c_int64_t), intent(out) :: idx(*)
        integer(c_int) :: ierr
      end function
+     !> warm start: x(ldx, ncols) on the host (the whole array on every rank) becomes the staged guess, X columns [0, ncols)
+     function dav_set_guess(h, x, ldx, ncols) bind(C, name="dav_set_guess") result(ierr)
+       import :: c_ptr, c_int, c_int64_t, c_double
+       type(c_ptr), value :: h
+       real(c_double), intent(in) :: x(*)
+       integer(c_int64_t), value :: ldx
+       integer(c_int), value :: ncols
+       integer(c_int) :: ierr
+     end function
+     !> the same from device memory of the engine's device
+     function dav_set_guess_dev(h, x_dev, ldx, ncols) bind(C, name="dav_set_guess_dev") result(ierr)
+       import :: c_ptr, c_int, c_int64_t
+       type(c_ptr), value :: h
+       type(c_ptr), value :: x_dev
+       integer(c_int64_t), value :: ldx
+       integer(c_int), value :: ncols
+       integer(c_int) :: ierr
+     end function
+     !> sticky switch: the Ritz vectors a solve leaves in X count as the guess of the next solve
+     function dav_keep_result_as_guess(h, on) bind(C, name="dav_keep_result_as_guess") result(ierr)
+       import :: c_ptr, c_int
+       type(c_ptr), value :: h
+       integer(c_int), value :: on
+       integer(c_int) :: ierr
+     end function
+     !> the driver's record, when its loop ends, that X columns [0, ncols) hold its Ritz vectors
+     function dav_mark_result_as_guess(h, ncols) bind(C, name="dav_mark_result_as_guess") result(ierr)
+       import :: c_ptr, c_int
+       type(c_ptr), value :: h
+       integer(c_int), value :: ncols
+       integer(c_int) :: ierr
+     end function
+     !> staged guess columns (0 = none)
+     function dav_guess_columns(h, ncols) bind(C, name="dav_guess_columns") result(ierr)
+       import :: c_ptr, c_int
+       type(c_ptr), value :: h
+       integer(c_int), intent(out) :: ncols
+       integer(c_int) :: ierr
+     end function
+     !> warm counterpart of dav_init_basis: staged columns first, unit vectors behind them; no images, no H0
+     function dav_init_basis_guess(h, ncols, idx, nguess) bind(C, name="dav_init_basis_guess") result(ierr)
+       import :: c_ptr, c_int, c_int64_t
+       type(c_ptr), value :: h
+       integer(c_int), value :: ncols
+       integer(c_int64_t), intent(out) :: idx(*)
+       integer(c_int), intent(out) :: nguess
+       integer(c_int) :: ierr
+     end function
      function dav_apply(h, which, src_panel, c0, k, dst_panel, d0) bind(C, name="dav_apply") result(ierr)
        import :: c_ptr, c_int
        type(c_ptr), value :: h

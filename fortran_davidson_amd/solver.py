@@ -17,7 +17,7 @@ import numpy as np
 
 from ._lib import fortran_lib, hip_lib
 from .engine_c import (CEngine, DavidsonHipError, _device_bsr_tensors, _device_csr_tensors, check_bsr, check_csr, device_bsr_tensors,
-                       device_csr_tensors, is_torch_bsr, is_torch_csr, torch_bsr_parts, torch_csr_parts, update_values_array)
+                       device_csr_tensors, guess_array, is_torch_bsr, is_torch_csr, torch_bsr_parts, torch_csr_parts, update_values_array)
 
 _METHOD = {"DPR": 0, "GJD": 1}
 _CB = C.CFUNCTYPE(None, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
@@ -31,8 +31,25 @@ def _f(a):
     return np.asfortranarray(a, dtype=np.float64)
 
 
+def _initial_vectors(x, n, lowest):
+    """initial_vectors= of the one-call front ends, checked here because their Fortran doors stop the process on a refused guess:
+    float64 (TypeError), n rows, finite entries, no column that is entirely zero (ValueError).  Of a guess wider than the start basis
+    (2 * lowest columns) the leading columns are used.  Returns a Fortran-ordered host array."""
+    host, dev = guess_array(x, n, None, "initial_vectors")
+    if dev is not None:
+        host = np.asfortranarray(dev[0].cpu().numpy())
+    host = np.asfortranarray(host[:, :2 * lowest])
+    if not np.isfinite(host).all():
+        raise ValueError("initial_vectors: x holds an entry that is not finite (Inf or NaN)")
+    zero = np.flatnonzero(~(host != 0.0).any(axis=0))
+    if zero.size:
+        raise ValueError(f"initial_vectors: column {int(zero[0])} of x (counted from 0) is entirely zero")
+    return host
+
+
 def generalized_eigensolver(matrix, lowest, method, max_iterations, tolerance, max_dim_sub=None,
-                            second_matrix=None):
+                            second_matrix=None, initial_vectors=None):
+    """initial_vectors (n, g): the solve starts from these columns instead of unit vectors (Fortran: initial_vectors=)."""
     lib = fortran_lib()
     iters = C.c_int(-1)
     evals = np.zeros(lowest)
@@ -44,6 +61,13 @@ def generalized_eigensolver(matrix, lowest, method, max_iterations, tolerance, m
     n = a.shape[0]
     evecs = np.zeros((n, lowest), order="F")
     b = _f(second_matrix) if second_matrix is not None else np.zeros((1, 1), order="F")
+    if initial_vectors is not None:
+        x0 = _initial_vectors(initial_vectors, n, lowest)
+        lib.fd_dense_solve_guess(C.c_int(n), _dp(a), C.c_int(0 if second_matrix is None else 1), _dp(b), C.c_int(lowest),
+                                 C.c_int(_METHOD.get(method, 2)), C.c_int(max_iterations), C.c_double(tolerance),
+                                 C.c_int(-1 if max_dim_sub is None else max_dim_sub), C.c_int(x0.shape[1]), _dp(x0), _dp(evals),
+                                 _dp(evecs), C.byref(iters))
+        return evals, evecs, iters.value
     lib.fd_dense_solve(C.c_int(n), _dp(a), C.c_int(0 if second_matrix is None else 1), _dp(b), C.c_int(lowest),
                        C.c_int(_METHOD.get(method, 2)), C.c_int(max_iterations), C.c_double(tolerance),
                        C.c_int(-1 if max_dim_sub is None else max_dim_sub), _dp(evals), _dp(evecs), C.byref(iters))
@@ -77,12 +101,13 @@ def _is_device_csr(a):
 
 
 def generalized_eigensolver_sparse(indptr, indices, data, lowest, method, max_iterations, tolerance, max_dim_sub=None, second=None,
-                                   lower=False):
+                                   lower=False, initial_vectors=None):
     """`call generalized_eigensolver(a_csr, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters [, max_dim_sub]
     [, b_csr])` (the csr_matrix specific of module davidson) with A in CSR form, 0-based: three arrays, or `indptr` an object with
     .tocsr() and indices = data = None.  `second`: B the same way - a tuple (indptr, indices, data) or an object with .tocsr().  Either
     may also be a torch.sparse_csr_tensor; one on the GPU is built there (DavidsonEngine.set_sparse on the tensor's device).
-    lower=True: only the entries with column <= row are given, for A and B.  Returns (eigenvalues, eigenvectors, iters)."""
+    lower=True: only the entries with column <= row are given, for A and B.  initial_vectors (n, g): the solve starts from these
+    columns instead of unit vectors.  Returns (eigenvalues, eigenvectors, iters)."""
     a = indptr if indices is None and data is None else (indptr, indices, data)
     if _is_device_csr(a) or _is_device_csr(second):
         # a matrix in device memory: an engine of its own, built on the GPU (DavidsonEngine.set_sparse)
@@ -92,7 +117,7 @@ def generalized_eigensolver_sparse(indptr, indices, data, lowest, method, max_it
             eng.set_sparse(1, a, lower=lower)
             if second is not None:
                 eng.set_sparse(2, second, lower=lower)
-            return eng.solve(method, max_iterations, tolerance)
+            return eng.solve(method, max_iterations, tolerance, initial_vectors=initial_vectors)
     n, rp, ci, vv = _sparse_input(a, None, lower)
     if second is not None:
         _, rpb, cib, vvb = _sparse_input(second, n, lower)
@@ -101,6 +126,14 @@ def generalized_eigensolver_sparse(indptr, indices, data, lowest, method, max_it
     evals = np.zeros(lowest)
     evecs = np.zeros((n, lowest), order="F")
     iters = C.c_int(-1)
+    if initial_vectors is not None:
+        x0 = _initial_vectors(initial_vectors, n, lowest)
+        fortran_lib().fd_sparse_solve_guess(C.c_int(n), _i64(rp), _i32(ci), _dp(vv), C.c_int(0 if second is None else 1), _i64(rpb),
+                                            _i32(cib), _dp(vvb), C.c_int(0), C.c_int(1 if lower else 0), C.c_int(lowest),
+                                            C.c_int(_METHOD.get(method, 2)), C.c_int(max_iterations), C.c_double(tolerance),
+                                            C.c_int(-1 if max_dim_sub is None else max_dim_sub), C.c_int(x0.shape[1]), _dp(x0),
+                                            _dp(evals), _dp(evecs), C.byref(iters))
+        return evals, evecs, iters.value
     fortran_lib().fd_sparse_solve(C.c_int(n), _i64(rp), _i32(ci), _dp(vv), C.c_int(0 if second is None else 1), _i64(rpb), _i32(cib),
                                   _dp(vvb), C.c_int(0), C.c_int(1 if lower else 0), C.c_int(lowest), C.c_int(_METHOD.get(method, 2)),
                                   C.c_int(max_iterations), C.c_double(tolerance), C.c_int(-1 if max_dim_sub is None else max_dim_sub),
@@ -130,13 +163,14 @@ def _is_device_bsr(a):
 
 
 def generalized_eigensolver_bsr(indptr, indices, data, lowest, method, max_iterations, tolerance, max_dim_sub=None, second=None,
-                                lower=False, n=None):
+                                lower=False, n=None, initial_vectors=None):
     """`call generalized_eigensolver(a_bsr, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters [, max_dim_sub]
     [, b_bsr])` (the bsr_matrix specific of module davidson) with A in BSR form, 0-based: three arrays - data (nnzb, b, b), row-major
     blocks - or `indptr` an object with .indptr / .indices / .data / .blocksize (a scipy bsr_matrix) and indices = data = None.
     `second`: B the same way, with the same block size.  Either may also be a torch.sparse_bsr_tensor; one on the GPU is built there
     (DavidsonEngine.set_block_sparse on the tensor's device).  lower=True: only the blocks with block column <= block row are given,
-    for A and B.  n: the order (default: block rows x b).  Returns (eigenvalues, eigenvectors, iters)."""
+    for A and B.  n: the order (default: block rows x b).  initial_vectors (n, g): the solve starts from these columns instead of unit
+    vectors.  Returns (eigenvalues, eigenvectors, iters)."""
     a = indptr if indices is None and data is None else (indptr, indices, data)
     if _is_device_bsr(a) or _is_device_bsr(second):
         # a matrix in device memory: an engine of its own, built on the GPU (DavidsonEngine.set_block_sparse)
@@ -150,7 +184,7 @@ def generalized_eigensolver_bsr(indptr, indices, data, lowest, method, max_itera
             eng.set_block_sparse(1, a, lower=lower)
             if second is not None:
                 eng.set_block_sparse(2, second, lower=lower)
-            return eng.solve(method, max_iterations, tolerance)
+            return eng.solve(method, max_iterations, tolerance, initial_vectors=initial_vectors)
     b, rp, ci, vv = _bsr_input(a, n, lower)
     n = (rp.size - 1) * b
     if second is not None:
@@ -162,6 +196,14 @@ def generalized_eigensolver_bsr(indptr, indices, data, lowest, method, max_itera
     evals = np.zeros(lowest)
     evecs = np.zeros((n, lowest), order="F")
     iters = C.c_int(-1)
+    if initial_vectors is not None:
+        x0 = _initial_vectors(initial_vectors, n, lowest)
+        fortran_lib().fd_bsr_solve_guess(C.c_int(n), C.c_int(b), _i64(rp), _i32(ci), _dp(vv), C.c_int(0 if second is None else 1),
+                                         _i64(rpb), _i32(cib), _dp(vvb), C.c_int(0), C.c_int(1 if lower else 0), C.c_int(lowest),
+                                         C.c_int(_METHOD.get(method, 2)), C.c_int(max_iterations), C.c_double(tolerance),
+                                         C.c_int(-1 if max_dim_sub is None else max_dim_sub), C.c_int(x0.shape[1]), _dp(x0),
+                                         _dp(evals), _dp(evecs), C.byref(iters))
+        return evals, evecs, iters.value
     fortran_lib().fd_bsr_solve(C.c_int(n), C.c_int(b), _i64(rp), _i32(ci), _dp(vv), C.c_int(0 if second is None else 1), _i64(rpb),
                                _i32(cib), _dp(vvb), C.c_int(0), C.c_int(1 if lower else 0), C.c_int(lowest), C.c_int(_METHOD.get(method, 2)),
                                C.c_int(max_iterations), C.c_double(tolerance), C.c_int(-1 if max_dim_sub is None else max_dim_sub),
@@ -170,8 +212,9 @@ def generalized_eigensolver_bsr(indptr, indices, data, lowest, method, max_itera
 
 
 def generalized_eigensolver_free(fun_matrix_gemv, n, lowest, method, max_iterations, tolerance, max_dim_sub,
-                                 fun_second_matrix_gemv):
-    """Matrix-free specific with numpy callbacks X(n,k) -> Y(n,k) (reference: src/davidson.f90:277-337)."""
+                                 fun_second_matrix_gemv, initial_vectors=None):
+    """Matrix-free specific with numpy callbacks X(n,k) -> Y(n,k) (reference: src/davidson.f90:277-337).  initial_vectors (n, g): the
+    solve starts from these columns instead of unit vectors."""
     lib = fortran_lib()
 
     def wrap(fn):
@@ -185,6 +228,12 @@ def generalized_eigensolver_free(fun_matrix_gemv, n, lowest, method, max_iterati
     evals = np.zeros(lowest)
     evecs = np.zeros((n, lowest), order="F")
     iters = C.c_int(-1)
+    if initial_vectors is not None:
+        x0 = _initial_vectors(initial_vectors, n, lowest)
+        lib.fd_free_solve_guess(C.c_int(n), fa, fb, C.c_int(lowest), C.c_int(max_iterations), C.c_double(tolerance),
+                                C.c_int(10 * lowest if max_dim_sub is None else max_dim_sub), C.c_int(x0.shape[1]), _dp(x0), _dp(evals),
+                                _dp(evecs), C.byref(iters))
+        return evals, evecs, iters.value
     lib.fd_free_solve(C.c_int(n), fa, fb, C.c_int(lowest), C.c_int(max_iterations), C.c_double(tolerance),
                       C.c_int(10 * lowest if max_dim_sub is None else max_dim_sub), _dp(evals), _dp(evecs),
                       C.byref(iters))
@@ -364,7 +413,39 @@ class DavidsonEngine:
         """The caller's own operator as a block apply on device memory (engine_set_device_operator; which = 1 / 2)."""
         self.c.set_operator_device(which - 1, fn, ctx, diag)
 
-    def solve(self, method="DPR", max_iterations=1000, tolerance=1e-8, want_vectors=True):
+    def set_initial_vectors(self, x):
+        """The next solve starts from the columns of x (n rows) instead of unit vectors (Fortran: engine_set_initial_vectors /
+        engine_set_initial_vectors_device): a numpy array goes through the host entry, a torch tensor on the engine's GPU through the
+        device entry.  One-shot.  float64 only (TypeError); a wrong row count is a ValueError before any engine call; the engine's
+        refusal - an entry that is not finite, a column that is entirely zero - a DavidsonHipError, and a guess staged earlier stays
+        staged.  Of a guess wider than the start basis (2 * lowest columns) the leading columns are used."""
+        host, dev = guess_array(x, self.n, self.device, "initial_vectors")
+        width = 2 * self.lowest                 # (the engine's basis always holds the start basis)
+        if dev is not None:
+            import torch
+            t, ld, ncols = dev
+            torch.cuda.current_stream(t.device).synchronize()
+            st = self.lib.fd_engine_set_initial_vectors_device(self.p, C.c_void_p(t.data_ptr() or None), C.c_int(ld),
+                                                               C.c_int(min(ncols, width)))
+        else:
+            host = np.asfortranarray(host[:, :width])
+            st = self.lib.fd_engine_set_initial_vectors(self.p, _dp(host), C.c_int(host.shape[1]))
+        if st != 0:
+            raise DavidsonHipError(hip_lib().dav_last_error().decode())
+
+    def keep_result_as_guess(self, on=True):
+        """Sticky (Fortran: engine_keep_result_as_guess): while on, every solve starts from the Ritz vectors the previous solve on this
+        engine left in HBM - nothing is copied; update_values and the set calls keep them."""
+        self.lib.fd_engine_keep_result_as_guess(self.p, C.c_int(1 if on else 0))
+
+    def solve(self, method="DPR", max_iterations=1000, tolerance=1e-8, want_vectors=True, initial_vectors=None, reuse_vectors=None):
+        """initial_vectors: see set_initial_vectors (a one-shot guess for this solve).  reuse_vectors: True / False turns
+        keep_result_as_guess on / off before the solve (sticky), None leaves it as it is; with it on and no initial_vectors the solve
+        starts from the previous solve's Ritz vectors when they are still in place."""
+        if reuse_vectors is not None:
+            self.keep_result_as_guess(bool(reuse_vectors))
+        if initial_vectors is not None:
+            self.set_initial_vectors(initial_vectors)
         evals = np.zeros(self.lowest)
         evecs = np.zeros((self.n, self.lowest) if want_vectors else (1, 1), order="F")
         iters = C.c_int(-1)

@@ -304,6 +304,40 @@ int dav_get_diagonal(dav_handle_t h, int which, double* diag_out /* n, global */
  * array_utils.f90:136-160): V0 = unit vectors at the ncols smallest diagonal entries (stable order),
  * W0 = A*V0 (and B*V0).  idx_out[ncols] receives the 1-based positions.  Sets m = ncols. */
 int dav_init_basis(dav_handle_t h, int ncols, int64_t* idx_out);
+/* Warm start: a solve that begins from vectors the caller has - the eigenvectors of the previous step of an SCF iteration, a parameter
+ * scan, a time loop - instead of the unit vectors of dav_init_basis.  Purely additive within ABI 109 and opt-in: with nothing staged no
+ * existing entry does anything it did not do before, and a solve is bit for bit what it was.
+ * ONE MECHANISM: a staged guess is the X panel, columns [0, g), wherever it came from, and the engine remembers only g and whether a
+ * caller staged it or a solve left it.  Any call that writes the X panel outside these entries (dav_panel_put / dav_panel_transform /
+ * dav_panel_select / dav_panel_unit_column / dav_apply into X, a Ritz phase, dav_ritz_vectors) drops it; setting, re-setting or
+ * updating an operator does NOT - that is the use case.
+ * dav_set_guess takes x(ldx, ncols), column-major, ldx >= n, host memory, the WHOLE array on every rank (a rank keeps its rows);
+ * dav_set_guess_dev the same array in device memory of the engine's device, complete when the call is made (a caller that writes it on
+ * a stream of its own synchronises first): the pointer is checked before anything is launched, as dav_set_operator_csr_dev checks its
+ * arrays - null, pageable / pinned / managed memory, another device or an allocation shorter than 8 (ldx (ncols - 1) + n) bytes is
+ * refused, the message names x_dev - and the call returns synchronised with the engine's stream: x_dev may be freed at once.  Both run
+ * the engine's ingest kernel over this rank's rows - one pass that moves the values bit for bit, zeroes the pad rows and decides, by bit
+ * tests and without any tolerance, whether the guess is taken.  Refused, with a message (dav_last_error): ncols < 1, ncols > max_cols,
+ * ldx < n, a null pointer, an entry that is not finite, a column that is entirely zero (the first such column is named, counted from 0;
+ * -0.0 is zero); several ranks combine what they saw, so all refuse or all accept.  A refused call leaves the engine, the X panel and a
+ * guess staged earlier as they were (the scratch panel S is overwritten by either call).  The columns need not be orthonormal, nor
+ * B-orthonormal, nor independent: the driver orthonormalises the start basis and completes dependent columns with unit vectors.
+ * dav_keep_result_as_guess is a sticky switch (default 0): while it is on, the Ritz vectors a driver's solve left in X columns
+ * [0, lowest) - recorded by the driver with dav_mark_result_as_guess(h, lowest) when its loop ends, whatever the switch says; nothing is
+ * copied - count as the staged guess of the next solve, as long as no call has written X since.  dav_guess_columns: how many columns
+ * are staged (0 = none: a guess a solve left counts only while the switch is on).
+ * dav_init_basis_guess is the warm counterpart of dav_init_basis: g = min(staged, ncols) staged columns go to V columns [0, g), the
+ * first ncols - g unit vectors of dav_init_basis's order (smallest diagonal entries of A, the same cache) to [g, ncols); idx_out[i] = 0
+ * for a guess column, the 1-based position for a unit column; *nguess = g; sets m = ncols.  It computes no images and leaves nothing
+ * for the H0 shortcut of dav_project: the caller orthonormalises V[:, 0:ncols) and then calls dav_expand(h, 0, ncols) and
+ * dav_project(h, 0, ncols), as after a restart refresh.  A guess a caller staged is consumed; one a solve left stays offered; the
+ * switch is left alone.  Guesses wider than the start basis: the leading ncols columns are used. */
+int dav_set_guess(dav_handle_t h, const double* x, int64_t ldx, int ncols);
+int dav_set_guess_dev(dav_handle_t h, const double* x_dev, int64_t ldx, int ncols);
+int dav_keep_result_as_guess(dav_handle_t h, int on);
+int dav_mark_result_as_guess(dav_handle_t h, int ncols);
+int dav_guess_columns(dav_handle_t h, int* ncols);
+int dav_init_basis_guess(dav_handle_t h, int ncols, int64_t* idx_out, int* nguess);
 /* K1 - replaces lapack_matmul('N','N', matrix, V) (src/davidson.f90:131,223 inner;
  * lapack_wrapper.f90:279-328): dst[:, d0:d0+k] = Op(which) * src[:, c0:c0+k]. */
 int dav_apply(dav_handle_t h, int which, int src_panel, int c0, int k, int dst_panel, int d0);
