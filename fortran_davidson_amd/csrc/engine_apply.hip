@@ -21,41 +21,90 @@ bool inner_f32_tiles(E* e, OpDesc& o) {
   return true;
 }
 
-// The super-row sweep of one launch: stored fp64 tiles, two block rows per workgroup and more than 8 columns run the
-// one-wave-per-SIMD kernel (k_matvec_symw.hip: 32 columns per workgroup, or 16 for a block of <= 16); generated operators,
-// the fp32 copy and the k <= 8 schedule (R = 4, 4x4x4 MFMA) stay on matvec_sym9_kernel.
-// Tune::sym_wide (DAV_SYM_WIDE at dav_create) = 2 (default): the one-wave-per-SIMD kernel for more than 8 columns, 1: for more
-// than 16 only, 0: never (A/B runs)
-bool sym_wide_enabled(const E* e) { return e->tune.sym_wide > 1; }   // ... for 9-16 columns too
-
-void sym9_sweep(E* e, int R, const OpDesc& o, bool use32, const SymSet& set, const SymPlan* pl, const double* xt, int kk, double* slabD,
-                double* slabT, int npair, int64_t dstride, int64_t tstride) {
-  const int wide = e->tune.sym_wide;
-  if (o.kind == DAV_KIND_DENSE && !use32 && wide > 0 && ((R == 2 && (kk > 16 || wide > 1)) || (R == 4 && kk > 8 && kk <= 16))) {
-    const int nbw = kk > 16 ? 2 : 1;
-    launch_matvec_symw(e->stream, nbw, R == 4, false, o.a, set.row_off, e->sym_nb, pl->items, pl->nitems, pl->zslot_begin, xt, kk, slabD, slabT,
-                       (npair + nbw - 1) / nbw, e->xt_group_stride, dstride, tstride);
-    return;
+// the sweep of launch L (engine_operators.hip: sym_launch): partials into the slabs, [groups x direct][groups x transposed]
+static double* sym_slab_t(const E* e, const SymLaunch& L) { return e->sym_slab + (int64_t)L.ngroups * L.dstride; }
+static void sym_sweep(E* e, const SymLaunch& L, const OpDesc& o, const SymSet& set, const double* xt) {
+  if (L.nitems == 0) return;             // a rank can be left without a block row (more ranks than groups of block rows)
+  const SymPlan* pl = L.plan;
+  const void* tiles = L.use32 ? (const void*)o.a32 : (const void*)o.a;
+  double *slabD = e->sym_slab, *slabT = sym_slab_t(e, L);
+  const int64_t xs = e->xt_group_stride, ds = L.dstride, ts = L.tstride;
+  switch (L.family) {
+    case SYM_ROW_STORED:
+      return launch_matvec_sym(e->stream, o.a, set.row_off, set.items, set.nitems, xt, L.kk, slabD, slabT, L.ngroups, xs, ds, ts);
+    case SYM_ROW_GENERATED:
+      return launch_matvec_sym_generated(e->stream, op_params(o), e->n, set.items, set.nitems, xt, L.kk, slabD, slabT, L.ngroups, xs, ds, ts);
+    case SYM_SUPER:
+      return launch_matvec_sym9(e->stream, L.R, o.kind != DAV_KIND_DENSE, tiles, L.use32, set.row_off, o.kind != DAV_KIND_DENSE ? op_params(o) : OpParams{},
+                                e->n, e->sym_nb, pl->items, pl->nitems, pl->zslot_begin, xt, L.kk, slabD, slabT, L.nwg, xs, ds, ts, e->tune.sym_mfma4 != 0);
+    case SYM_WIDE:
+    case SYM_WIDE_F32:
+      return launch_matvec_symw(e->stream, L.nbw, L.tall, L.use32, tiles, set.row_off, e->sym_nb, pl->items, pl->nitems, pl->zslot_begin, xt, L.kk, slabD, slabT, L.nwg, xs, ds, ts);
+    case SYM_WIDE_GENERATED:
+      return launch_matvec_symw_generated(e->stream, op_params(o), e->n, e->sym_nb, pl->items, pl->nitems, pl->zslot_begin, xt, L.kk, slabD, slabT, L.nwg, xs, ds, ts);
   }
-  // the hashed operator at 17-32 columns per launch: the wide kernel's generating variant - one generated entry feeds the MFMAs of
-  // both 16-column groups (Tune::sym_gen_wide = 0: two groups of the 16-column kernel, every entry generated twice)
-  // (round 6: the reference's matrix-free test operator in its polynomial form too - GEN = 2 / 3 of that kernel)
-  if ((o.kind == DAV_KIND_HASHED || (o.kind == DAV_KIND_HARNESS && !o.harness_libm)) && R == 2 && kk > 16 && wide > 0 && e->tune.sym_gen_wide) {
-    launch_matvec_symw_generated(e->stream, op_params(o), e->n, e->sym_nb, pl->items, pl->nitems, pl->zslot_begin, xt, kk, slabD, slabT,
-                                 (npair + 1) / 2, e->xt_group_stride, dstride, tstride);
-    return;
-  }
-  // fp32 tiles (mixed-precision inner sweeps, up to 16 columns): the wide kernel's fp32 variant; Tune::sym_wide32 = 0: the two-wave kernel
-  if (o.kind == DAV_KIND_DENSE && use32 && wide > 1 && e->tune.sym_wide32 && R == 2 && kk <= 16) {
-    launch_matvec_symw(e->stream, 1, false, true, o.a32, set.row_off, e->sym_nb, pl->items, pl->nitems, pl->zslot_begin, xt, kk, slabD, slabT,
-                       npair, e->xt_group_stride, dstride, tstride);
-    return;
-  }
-  launch_matvec_sym9(e->stream, R, o.kind != DAV_KIND_DENSE, use32 ? (const void*)o.a32 : (const void*)o.a, use32, set.row_off,
-                     o.kind != DAV_KIND_DENSE ? op_params(o) : OpParams{}, e->n, e->sym_nb, pl->items, pl->nitems, pl->zslot_begin, xt, kk,
-                     slabD, slabT, npair, e->xt_group_stride, dstride, tstride, e->tune.sym_mfma4 != 0);
 }
 
+// ---- the steps around a sweep ---------------------------------------------------------------------------------------------------
+static void count_apply(E* e, int which, int kk) { if (which == DAV_OP_A) { e->st.applies += 1; e->st.apply_cols += kk; } }
+
+// operand step: kk source columns packed into the 16-column groups of Xt and - gather - those of all ranks in one grouped all-gather
+static int pack_operand(E* e, const double* src, int kk, bool gather) {
+  launch_pack_xt(e->stream, src, e->ldp, e->nloc, e->nslab, kk, e->xt, e->xt_group_stride, e->row0);
+  if (!gather) return 0;
+  const int ngroups = (kk + 15) / 16;
+  CollGroup grp(e);
+  CHK(grp.begin(5, 8.0 * (double)e->nslab * 16 * ngroups * e->nranks));
+  for (int g = 0; g < ngroups; ++g)
+    CHK(coll_allgather(e, e->xt + g * e->xt_group_stride + e->row0 * 16, e->xt + g * e->xt_group_stride, (size_t)e->nslab * 16));
+  return grp.end("all-gather of the new block", e->stream);
+}
+
+// The fixed-order sums of launch L's partials, one per 16-column group: into panel columns from `out` on (chunk_rows = 0) or into
+// the reduce-scatter layout (chunk_rows = nslab: [group][rank][column][row of the rank's slab])
+static void sym_reduce_groups(E* e, const SymLaunch& L, const SymSet& set, const int64_t* owned, double* out, int64_t chunk_rows, bool accumulate) {
+  const int64_t total_rows = (int64_t)e->nranks * e->nslab;
+  const double* slabT = sym_slab_t(e, L);
+  for (int g = 0; g < L.ngroups; ++g) {
+    const int kg = std::min(16, L.kk - 16 * g);
+    const double *d = e->sym_slab + g * L.dstride, *t = slabT + g * L.tstride;
+    double* og = out + (size_t)g * 16 * (size_t)(chunk_rows ? total_rows : e->ldp);
+    if (L.plan)
+      launch_sym9_reduce(e->stream, d, t, L.plan->row_begin, L.plan->zslot_begin, owned, L.plan->next_owned, L.R, e->sym_nb, e->nloc, kg, og, e->ldp,
+                         chunk_rows, total_rows, accumulate);
+    else
+      launch_sym_reduce(e->stream, d, t, set.row_begin, owned, e->sym_nb, e->nloc, kg, og, e->ldp, chunk_rows, total_rows, accumulate);
+  }
+}
+
+// several ranks: this rank's partial of the whole product and the summed chunk, 64 columns each
+static int ensure_sym_wpart(E* e) {
+  if (e->sym_wpart) return 0;
+  HIPCHK(pool_malloc(&e->sym_wpart, sizeof(double) * (size_t)e->nranks * (size_t)e->nslab * 64));
+  HIPCHK(pool_malloc(&e->sym_wrecv, sizeof(double) * (size_t)e->nslab * 64));
+  return 0;
+}
+
+// The partials of kk columns in sym_wpart summed over the ranks - one reduce-scatter per 16 columns in ONE group (h0: an all-reduce
+// of h0_count doubles is a member of it) - and every rank's rows of the sums into its panel columns
+static int sym_scatter_to_panel(E* e, int kk, double* dst, bool accumulate, const char* what, double* h0 = nullptr, size_t h0_count = 0) {
+  const size_t wstride = (size_t)e->nranks * (size_t)e->nslab * 16, rstride = (size_t)e->nslab * 16;
+  const int ngroups = (kk + 15) / 16;
+  CollGroup grp(e);
+  CHK(grp.begin(6, 8.0 * (double)e->nslab * kk * e->nranks));
+  for (int g = 0; g < ngroups; ++g)
+    CHK(coll_reduce_scatter(e, e->sym_wpart + g * wstride, e->sym_wrecv + g * rstride, (size_t)e->nslab * std::min(16, kk - 16 * g)));
+  if (h0) CHK(coll_allreduce(e, h0, h0_count));
+  CHK(grp.end(what, e->stream));
+  for (int g = 0; g < ngroups; ++g)
+    launch_chunk_to_panel(e->stream, e->sym_wrecv + g * rstride, e->nslab, e->nloc, e->nloc_pad, std::min(16, kk - 16 * g), dst + (int64_t)(16 * g) * e->ldp, e->ldp, accumulate);
+  return 0;
+}
+
+// stored bytes one sweep reads: the whole triangle dealt out over the ranks, or - a part of an operator - the set's own tiles
+static double sym_stored_bytes(const E* e, const OpDesc& o, const SymSet& set, bool partial, bool use32) {
+  return o.kind != DAV_KIND_DENSE ? 0.0 : (use32 ? 4.0 : 8.0) * (partial ? (double)set.ntiles * SYM_TB * SYM_TB : 0.5 * (double)e->n * ((double)e->n + 1.0) / e->nranks);
+}
 
 // Symmetric sweep of k > 32 columns over several ranks with RCCL, chunks of 32 columns software-pipelined over two streams:
 //   comm stream:  gather(0)            gather(1)   scatter(0)   gather(2)   scatter(1) ...
@@ -63,7 +112,7 @@ void sym9_sweep(E* e, int R, const OpDesc& o, bool use32, const SymSet& set, con
 // i.e. the all-gather of chunk i + 1 and the reduce-scatter of chunk i - 1 run under the sweep of chunk i.  Xt column groups,
 // the partial-product buffer and the receive buffer alternate with the chunk parity.  Same kernels, same sums, same result as
 // the serial path (which the test transports and single-chunk applies keep using).
-int apply_sym_overlapped(E* e, int which, OpDesc& o, const double* src, int k, double* dst, bool timed, bool inner) {
+static int apply_sym_overlapped(E* e, int which, OpDesc& o, const double* src, int k, double* dst, bool timed, bool inner) {
   const int step = 32;
   const int nchunks = (k + step - 1) / step;
   if (!e->ov_ready) {
@@ -105,13 +154,11 @@ int apply_sym_overlapped(E* e, int which, OpDesc& o, const double* src, int k, d
   // (they synchronise the host); what the multi-rank RCCL run cannot be rehearsed for on a one-GPU box is only the overlap itself
   const bool tt = has_test_transport(e);
   hipStream_t cs = tt ? e->stream : e->comm_stream;
-  const bool use32 = false;                            // chunks of 32 columns: the fp64 tiles on the wide kernel (see apply_ptr)
-  const int R = 2;                                     // 32-column chunks: the paired two-block-row schedule
-  const SymPlan* pl = &e->sym.plan[0];
-  const int64_t dstride = (int64_t)pl->nitems * R * 16 * SYM_TB, tstride = pl->zslots * 16 * SYM_TB;
-  if (sym_ensure_slabs(e, (size_t)2 * (size_t)(dstride + tstride) + 1) != 0) return 2;   // serial path: it degrades 4 -> 2 -> 1 column groups
+  // chunks of 32 columns: fp64 tiles, the paired two-block-row schedule (the caller's wide_block); a narrower last chunk keeps it
+  const SymLaunch wide = sym_launch(e, o, e->sym, step, false);
+  if (sym_ensure_slabs(e, (size_t)2 * (size_t)(wide.dstride + wide.tstride) + 1) != 0) return 2;   // serial path: it degrades 4 -> 2 -> 1 column groups
   int slot = -1;
-  const double stored = o.kind == DAV_KIND_DENSE ? (use32 ? 4.0 : 8.0) * 0.5 * (double)e->n * ((double)e->n + 1.0) / e->nranks : 0.0;
+  const double stored = sym_stored_bytes(e, o, e->sym, false, false);
   if (timed) CHK(timed_begin(e, which == DAV_OP_A ? 0 : 2, stored * nchunks + 16.0 * (double)e->n * k, &slot));
   auto cols = [&](int i) { return std::min(step, k - i * step); };
   auto xt_of = [&](int i) { return e->xt + (size_t)(i & 1) * 2 * e->xt_group_stride; };
@@ -142,20 +189,16 @@ int apply_sym_overlapped(E* e, int which, OpDesc& o, const double* src, int k, d
   CHK(pack_and_gather(0));
   for (int i = 0; i < nchunks; ++i) {
     const int p = i & 1, kk = cols(i), npair = (kk + 15) / 16;
+    const SymLaunch L = sym_launch(e, o, e->sym, kk, false, wide.R);
     if (i + 1 < nchunks) CHK(pack_and_gather(i + 1));         // Xt groups of the other parity: last read by the sweep of chunk i - 1
     HIPCHK(hipStreamWaitEvent(e->stream, e->ov_gathered[p], 0));
     int kslot = -1;
     if (timed && which == DAV_OP_A) CHK(timed_begin(e, 4, 2.0 * (double)e->n * (double)e->n * kk / e->nranks, &kslot));
-    double* slabT = e->sym_slab + (int64_t)npair * dstride;
-    if (pl->nitems > 0)
-      sym9_sweep(e, R, o, use32, e->sym, pl, xt_of(i), kk, e->sym_slab, slabT, npair, dstride, tstride);
+    sym_sweep(e, L, o, e->sym, xt_of(i));
     CHK(timed_end(e, kslot));
     // partial of the whole product of this chunk (the buffer of this parity was last read by the reduce-scatter of chunk
     // i - 2, whose completion the main stream waited for when it finished chunk i - 2 below)
-    for (int g = 0; g < npair; ++g)
-      launch_sym9_reduce(e->stream, e->sym_slab + g * dstride, slabT + g * tstride, pl->row_begin, pl->zslot_begin, e->sym.row_off, pl->next_owned, R,
-                         e->sym_nb, e->nloc, std::min(16, kk - 16 * g), e->sym_wpart2[p] + (size_t)g * (size_t)total_rows * 16, e->ldp,
-                         e->nslab, total_rows);
+    sym_reduce_groups(e, L, e->sym, e->sym.row_off, e->sym_wpart2[p], e->nslab, false);
     HIPCHK(hipEventRecord(e->ov_reduced[p], e->stream));
     HIPCHK(hipStreamWaitEvent(cs, e->ov_reduced[p], 0));
     {
@@ -172,16 +215,13 @@ int apply_sym_overlapped(E* e, int which, OpDesc& o, const double* src, int k, d
     }
     HIPCHK(hipEventRecord(e->ov_scattered[p], cs));
     if (i >= 1) CHK(to_panel(i - 1));                      // the previous chunk's rows of W, while this chunk's reduce-scatter runs
-    if (which == DAV_OP_A) { e->st.applies += 1; e->st.apply_cols += kk; }
+    count_apply(e, which, kk);
   }
   CHK(to_panel(nchunks - 1));
   CHK(timed_end(e, slot));
   HIPCHK(hipGetLastError());
   return 0;
 }
-
-static int apply_sym_set(E* e, int which, OpDesc& o, const SymSet& set, bool partial, bool accumulate, const double* src, int k, double* dst,
-                         bool timed, bool inner);
 
 // ---- which way do the collectives of a wide block go?  (round 6) ---------------------------------------------------------------
 // Three ways exist (all three give the sweep's kernels the same operands and sum their partial products in a fixed order):
@@ -312,140 +352,81 @@ static int coll_path_trial(E* e, int which, OpDesc& o, const SymSet& set, const 
 // The symmetric-tiled sweep of the block rows of `set` of operator view `o` (stored tiles at o.a / generated entries):
 // dst[:, 0:k] (+)= Op * src[:, 0:k].  partial: `set` is not all of the rank's block rows (an operator swept in two parts: its
 // resident and its generated block rows); accumulate: the result is added to dst.
-static int apply_sym_set(E* e, int which, OpDesc& o, const SymSet& set, bool partial, bool accumulate, const double* src, int k, double* dst,
-                         bool timed, bool inner) {
-  {
-    // symmetric-tiled sweep: every off-diagonal tile read (or generated) once, used twice.  16 columns per workgroup; 32
-    // columns per launch as paired workgroups that share their tile reads through the memory-side cache.
-    // Several ranks: each sweeps the block rows it stores against the all-gathered block and holds a partial of the
-    // WHOLE product; one reduce-scatter per 16 columns sums the partials and leaves every rank its row slab.
-    // pairing shares the READS of stored tiles: nothing to share when the entries are generated
-    // ... except where the generating variant of the wide kernel shares the GENERATED entries between two groups (hashed operator,
-    // two-block-row schedule)
-    const bool gen_wide = (o.kind == DAV_KIND_HASHED || (o.kind == DAV_KIND_HARNESS && !o.harness_libm)) && e->tune.sym_gen_wide && e->tune.sym_wide > 0 &&
-                          sym_schedule(e, 32, false) == 2;
-    int step = (e->tune.sym_pair && !e->sym_no_pair && (o.kind == DAV_KIND_DENSE || gen_wide)) ? 32 : 16;
-    // several ranks - or a communicator on a single rank (DAVIDSON_FORCE_RCCL=1: the GPU tests run the all-gather and the
-    // reduce-scatter of this path through RCCL on a one-GPU box)
-    const bool multi = e->nranks > 1 || has_comm(e);
-    const bool pair_ok = step == 32;
-    // Opt-in (Tune::sym_overlap, DAV_SYM_OVERLAP=1 at dav_create): the collectives of a block wider than 32 columns run on a second
-    // stream under the sweeps of its 32-column chunks.  All collectives of that pipeline are issued on the ONE communication stream in
-    // the same order on every rank, ordered against the engine's stream by events, so no two collectives of the communicator are
-    // ever in flight together.  Off by default: it has never run over more than one RCCL rank (round-4 advisor); the default below
-    // keeps every collective on the engine's stream in program order.
-    const bool wide_block = !partial && pair_ok && k > 32 && o.kind == DAV_KIND_DENSE && sym_schedule(e, 32, true) == 2;
-    // Round 6: which way the collectives of a wide block go is decided by the engine itself, once, at the first such block over a
-    // real communicator of several ranks (coll_path_trial below) - unless the environment forced a path at dav_create
-    if (wide_block && e->comm && e->nranks > 1 && e->coll_path == COLL_PATH_UNDECIDED && !inner) return coll_path_trial(e, which, o, set, src, k, dst, timed);
-    if (e->tune.sym_overlap != 0 && wide_block && (e->comm || has_test_transport(e))) {
-      const int rc = apply_sym_overlapped(e, which, o, src, k, dst, timed, inner);
-      if (rc != 2) return rc;                          // 2: its streams / buffers / slabs could not be set up - serial path below
-    }
-    // 64 columns (the widest expansion of the doubling policy below a basis of 128) as FOUR column groups in one launch on
-    // the super-row kernels: the four workgroups of a work item share every tile read through their XCD's L2.  Same box,
-    // N=200000, k=64: two paired launches 102.6 ms, one launch of four groups 93.6 ms (56.9 TFLOP/s).  Tune::sym_quad = 0: off.
-    // Several ranks (round 5): the same launch between ONE all-gather and ONE reduce-scatter of all four column groups - a block of
-    // 64 columns costs two collectives, not four.
-    if (e->tune.sym_quad && pair_ok && o.kind == DAV_KIND_DENSE && k >= 64 && !inner && !e->sym_no_quad && sym_schedule(e, 32, true) == 2) step = 64;
-    if (multi && !e->sym_wpart) {
-      HIPCHK(pool_malloc(&e->sym_wpart, sizeof(double) * (size_t)e->nranks * (size_t)e->nslab * 64));
-      HIPCHK(pool_malloc(&e->sym_wrecv, sizeof(double) * (size_t)e->nslab * 64));
-    }
-    const int64_t* owned = (multi || partial) ? set.row_off : nullptr;
-    const int64_t total_rows = (int64_t)e->nranks * e->nslab;
-    for (int c = 0; c < k; c += step) {
-      int kk = std::min(step, k - c);
-      int npair = (kk + 15) / 16;
-      // fp32 tiles (inner sweeps of the GJD correction, opt-in) where the sweep is bound by bytes: up to 16 columns.  Wider ones
-      // are bound by the fp64 matrix pipe either way, and the one-wave-per-SIMD kernel on the fp64 tiles is the faster of the two
-      const bool use32 = inner && kk <= 16 && inner_f32_tiles(e, o);
-      int R = sym_schedule(e, kk, o.kind == DAV_KIND_DENSE && !use32);      // (the harness operator runs the super-row kernels too since round 5)
-      if (use32 && R == 1) R = 2;            // the fp32 tiles are read by the super-row kernels only
-      const SymPlan* pl = R > 1 ? &set.plan[R == 4 ? 1 : 0] : nullptr;
-      const int64_t dstride = R > 1 ? (int64_t)pl->nitems * R * 16 * SYM_TB : (int64_t)set.nitems * 16 * SYM_TB;
-      const int64_t tstride = R > 1 ? pl->zslots * 16 * SYM_TB : (int64_t)e->sym_nb * (e->sym_nb - 1) / 2 * 16 * SYM_TB;
-      while (sym_ensure_slabs(e, (size_t)npair * (size_t)(dstride + tstride) + 1) != 0) {
-        // not enough memory for this many column groups per launch: fewer from here on (4 -> 2 -> 1) - on ONE rank.  Several ranks
-        // must issue the same collectives: a rank that quietly fell back to narrower launches would leave its peers in theirs
-        if (npair < 2) return 1;
-        if (e->nranks > 1) return fail("symmetric sweep: no room for the partial-sum slabs of a " + std::to_string(16 * npair) +
-                                       "-column launch on rank " + std::to_string(e->rank) + " (DAV_SYM_QUAD=0 / DAV_SYM_PAIR=0 on every rank select narrower launches)");
-        if (npair > 2) { e->sym_no_quad = true; step = 32; kk = 32; npair = 2; }
-        else { e->sym_no_pair = true; step = 16; kk = 16; npair = 1; }
-      }
-      int slot = -1, kslot = -1;
-      // stored bytes of this part: the whole triangle dealt out over the ranks, or - a part of an operator - the set's own tiles
-      const double stored = o.kind == DAV_KIND_DENSE ? (use32 ? 4.0 : 8.0) * (partial ? (double)set.ntiles * SYM_TB * SYM_TB
-                                                                                        : 0.5 * (double)e->n * ((double)e->n + 1.0) / e->nranks) : 0.0;
-      double bytes = stored + 16.0 * (double)e->n * kk;
-      // end to end: everything that turns the source columns into W - packing, (all-gather,) the sweep, the fixed-order sum(, reduce-scatter)
-      if (timed) CHK(timed_begin(e, which == DAV_OP_A ? 0 : 2, bytes, &slot));
-      launch_pack_xt(e->stream, src + (int64_t)c * e->ldp, e->ldp, e->nloc, e->nslab, kk, e->xt, e->xt_group_stride, e->row0);
-      if (multi) {
-        CollGroup grp(e);
-        CHK(grp.begin(5, 8.0 * (double)e->nslab * 16 * npair * e->nranks));
-        for (int g = 0; g < npair; ++g) {
-          double* base = e->xt + g * e->xt_group_stride;
-          CHK(coll_allgather(e, base + e->row0 * 16, base, (size_t)e->nslab * 16));
-        }
-        CHK(grp.end("all-gather of the new block", e->stream));
-      }
-      if (timed && which == DAV_OP_A) CHK(timed_begin(e, 4, 2.0 * (double)e->n * (double)e->n * kk / e->nranks, &kslot));
-      if (timed && which == DAV_OP_B) {
-        // the second operator's sweep kernels by what they read (level 2): stored tiles -> bytes, generated block rows -> entries
-        // evaluated (once per 16 columns; once per 32 where the generating variant of the wide kernel runs)
-        const double tiles_entries = (double)set.ntiles * SYM_TB * SYM_TB;
-        const bool gen_shared = (o.kind == DAV_KIND_HASHED || (o.kind == DAV_KIND_HARNESS && !o.harness_libm)) && R == 2 && kk > 16 && e->tune.sym_wide > 0 && e->tune.sym_gen_wide;
-        if (o.kind == DAV_KIND_DENSE) CHK(timed_begin(e, 8, (use32 ? 4.0 : 8.0) * tiles_entries + 16.0 * (double)e->n * kk, &kslot));
-        else CHK(timed_begin(e, 9, tiles_entries * (gen_shared ? (npair + 1) / 2 : npair), &kslot));
-        if (kslot >= 0) e->ev_flops[kslot] = 4.0 * tiles_entries * kk;          // every stored / generated entry is used twice
-      }
-      double* slabT = e->sym_slab + (int64_t)npair * dstride;
-      const int nitems = R > 1 ? pl->nitems : set.nitems;
-      if (nitems > 0) {                      // a rank can be left without a block row (more ranks than groups of block rows)
-        if (R > 1)
-          sym9_sweep(e, R, o, use32, set, pl, e->xt, kk, e->sym_slab, slabT, npair, dstride, tstride);
-        else if (o.kind != DAV_KIND_DENSE)
-          launch_matvec_sym_generated(e->stream, op_params(o), e->n, set.items, set.nitems, e->xt, kk, e->sym_slab, slabT, npair,
-                                      e->xt_group_stride, dstride, tstride);
-        else
-          launch_matvec_sym(e->stream, o.a, set.row_off, set.items, set.nitems, e->xt, kk, e->sym_slab, slabT, npair,
-                            e->xt_group_stride, dstride, tstride);
-      }
-      CHK(timed_end(e, kslot));
-      for (int g = 0; g < npair; ++g) {
-        const int kg = std::min(16, kk - 16 * g);
-        double* out = multi ? e->sym_wpart + (size_t)g * (size_t)total_rows * 16 : dst + (int64_t)(c + 16 * g) * e->ldp;
-        if (R > 1)
-          launch_sym9_reduce(e->stream, e->sym_slab + g * dstride, slabT + g * tstride, pl->row_begin, pl->zslot_begin, owned, pl->next_owned, R, e->sym_nb,
-                             e->nloc, kg, out, e->ldp, multi ? e->nslab : 0, total_rows, accumulate && !multi);
-        else
-          launch_sym_reduce(e->stream, e->sym_slab + g * dstride, slabT + g * tstride, set.row_begin, owned, e->sym_nb, e->nloc, kg,
-                            out, e->ldp, multi ? e->nslab : 0, total_rows, accumulate && !multi);
-      }
-      if (multi) {
-        CollGroup grp(e);
-        CHK(grp.begin(6, 8.0 * (double)e->nslab * kk * e->nranks));
-        for (int g = 0; g < npair; ++g) {
-          const int kg = std::min(16, kk - 16 * g);
-          CHK(coll_reduce_scatter(e, e->sym_wpart + (size_t)g * (size_t)total_rows * 16, e->sym_wrecv + (size_t)g * (size_t)e->nslab * 16,
-                                  (size_t)e->nslab * kg));
-        }
-        CHK(grp.end("reduce-scatter of the partial products", e->stream));
-        for (int g = 0; g < npair; ++g)
-          launch_chunk_to_panel(e->stream, e->sym_wrecv + (size_t)g * (size_t)e->nslab * 16, e->nslab, e->nloc, e->nloc_pad,
-                                std::min(16, kk - 16 * g), dst + (int64_t)(c + 16 * g) * e->ldp, e->ldp, accumulate);
-      }
-      CHK(timed_end(e, slot));
-      if (which == DAV_OP_A) {
-        e->st.applies += 1;
-        e->st.apply_cols += kk;
-      }
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
+int apply_sym_set(E* e, int which, OpDesc& o, const SymSet& set, bool partial, bool accumulate, const double* src, int k, double* dst, bool timed,
+                  bool inner) {
+  // symmetric-tiled sweep: every off-diagonal tile read (or generated) once, used twice.  16 columns per workgroup; 32
+  // columns per launch as paired workgroups that share their tile reads through the memory-side cache.
+  // Several ranks: each sweeps the block rows it stores against the all-gathered block and holds a partial of the
+  // WHOLE product; one reduce-scatter per 16 columns sums the partials and leaves every rank its row slab.
+  // pairing shares the READS of stored tiles: nothing to share when the entries are generated
+  // ... except where the generating variant of the wide kernel shares the GENERATED entries between two groups (hashed operator,
+  // two-block-row schedule)
+  const bool stored = o.kind == DAV_KIND_DENSE;
+  const SymLaunch wide = sym_launch(e, o, set, 32, false);      // what a launch of 32 columns of this operator runs
+  int step = (e->tune.sym_pair && !e->sym_no_pair && (stored || wide.family == SYM_WIDE_GENERATED)) ? 32 : 16;
+  // several ranks - or a communicator on a single rank (DAVIDSON_FORCE_RCCL=1: the GPU tests run the all-gather and the
+  // reduce-scatter of this path through RCCL on a one-GPU box)
+  const bool multi = e->nranks > 1 || has_comm(e);
+  const bool pair_ok = step == 32;
+  // Opt-in (Tune::sym_overlap, DAV_SYM_OVERLAP=1 at dav_create): the collectives of a block wider than 32 columns run on a second
+  // stream under the sweeps of its 32-column chunks.  All collectives of that pipeline are issued on the ONE communication stream in
+  // the same order on every rank, ordered against the engine's stream by events, so no two collectives of the communicator are
+  // ever in flight together.  Off by default: it has never run over more than one RCCL rank (round-4 advisor); the default below
+  // keeps every collective on the engine's stream in program order.
+  const bool wide_block = !partial && pair_ok && k > 32 && stored && wide.R == 2;
+  // Round 6: which way the collectives of a wide block go is decided by the engine itself, once, at the first such block over a
+  // real communicator of several ranks (coll_path_trial above) - unless the environment forced a path at dav_create
+  if (wide_block && e->comm && e->nranks > 1 && e->coll_path == COLL_PATH_UNDECIDED && !inner) return coll_path_trial(e, which, o, set, src, k, dst, timed);
+  if (e->tune.sym_overlap != 0 && wide_block && (e->comm || has_test_transport(e))) {
+    const int rc = apply_sym_overlapped(e, which, o, src, k, dst, timed, inner);
+    if (rc != 2) return rc;                          // 2: its streams / buffers / slabs could not be set up - serial path below
   }
+  // 64 columns (the widest expansion of the doubling policy below a basis of 128) as FOUR column groups in one launch on
+  // the super-row kernels: the four workgroups of a work item share every tile read through their XCD's L2.  Same box,
+  // N=200000, k=64: two paired launches 102.6 ms, one launch of four groups 93.6 ms (56.9 TFLOP/s).  Tune::sym_quad = 0: off.
+  // Several ranks (round 5): the same launch between ONE all-gather and ONE reduce-scatter of all four column groups - a block of
+  // 64 columns costs two collectives, not four.
+  if (e->tune.sym_quad && pair_ok && stored && k >= 64 && !inner && !e->sym_no_quad && wide.R == 2) step = 64;
+  if (multi) CHK(ensure_sym_wpart(e));
+  const int64_t* owned = (multi || partial) ? set.row_off : nullptr;
+  for (int c = 0; c < k; c += step) {
+    int kk = std::min(step, k - c);
+    // fp32 tiles (inner sweeps of the GJD correction, opt-in) where the sweep is bound by bytes: up to 16 columns.  Wider ones
+    // are bound by the fp64 matrix pipe either way, and the one-wave-per-SIMD kernel on the fp64 tiles is the faster of the two
+    const bool use32 = inner && kk <= 16 && inner_f32_tiles(e, o);
+    SymLaunch L = sym_launch(e, o, set, kk, use32);
+    while (sym_ensure_slabs(e, (size_t)L.ngroups * (size_t)(L.dstride + L.tstride) + 1) != 0) {
+      // not enough memory for this many column groups per launch: fewer from here on (4 -> 2 -> 1) - on ONE rank.  Several ranks
+      // must issue the same collectives: a rank that quietly fell back to narrower launches would leave its peers in theirs
+      if (L.ngroups < 2) return 1;
+      if (e->nranks > 1) return fail("symmetric sweep: no room for the partial-sum slabs of a " + std::to_string(16 * L.ngroups) +
+                                     "-column launch on rank " + std::to_string(e->rank) + " (DAV_SYM_QUAD=0 / DAV_SYM_PAIR=0 on every rank select narrower launches)");
+      if (L.ngroups > 2) { e->sym_no_quad = true; step = 32; kk = 32; }
+      else { e->sym_no_pair = true; step = 16; kk = 16; }
+      L = sym_launch(e, o, set, kk, use32, L.R);     // this launch keeps its schedule (the strides the slabs were asked for)
+    }
+    int slot = -1, kslot = -1;
+    // end to end: everything that turns the source columns into W - packing, (all-gather,) the sweep, the fixed-order sum(, reduce-scatter)
+    if (timed) CHK(timed_begin(e, which == DAV_OP_A ? 0 : 2, sym_stored_bytes(e, o, set, partial, use32) + 16.0 * (double)e->n * kk, &slot));
+    CHK(pack_operand(e, src + (int64_t)c * e->ldp, kk, multi));
+    if (timed && which == DAV_OP_A) CHK(timed_begin(e, 4, 2.0 * (double)e->n * (double)e->n * kk / e->nranks, &kslot));
+    if (timed && which == DAV_OP_B) {
+      // the second operator's sweep kernels by what they read (level 2): stored tiles -> bytes, generated block rows -> entries
+      // evaluated (once per 16 columns; once per 32 where the generating variant of the wide kernel runs)
+      const double tiles_entries = (double)set.ntiles * SYM_TB * SYM_TB;
+      if (stored) CHK(timed_begin(e, 8, (use32 ? 4.0 : 8.0) * tiles_entries + 16.0 * (double)e->n * kk, &kslot));
+      else CHK(timed_begin(e, 9, tiles_entries * L.gen_evals, &kslot));
+      if (kslot >= 0) e->ev_flops[kslot] = 4.0 * tiles_entries * kk;          // every stored / generated entry is used twice
+    }
+    sym_sweep(e, L, o, set, e->xt);
+    CHK(timed_end(e, kslot));
+    sym_reduce_groups(e, L, set, owned, multi ? e->sym_wpart : dst + (int64_t)c * e->ldp, multi ? e->nslab : 0, accumulate && !multi);
+    if (multi) CHK(sym_scatter_to_panel(e, kk, dst + (int64_t)c * e->ldp, accumulate, "reduce-scatter of the partial products"));
+    CHK(timed_end(e, slot));
+    count_apply(e, which, kk);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 // Byte and flop model of one product of a sparse operator with k columns (include/davidson_hip.h: dav_stats): values and columns of the
@@ -456,145 +437,125 @@ static void sparse_traffic(const E* e, const OpDesc& o, int k, double* bytes, do
   *flops = 2.0 * bb * nnz * k;
 }
 
-// inner = true: a sweep inside the GJD correction solve (may run on the fp32 copy, dav_set_inner_precision)
-int apply_ptr(E* e, int which, const double* src, int k, double* dst, bool timed, bool inner) {
-  OpDesc& o = e->op[which];
-  if (o.kind == DAV_KIND_NONE) return fail("dav_apply: operator not set");
-  if (o.kind == DAV_KIND_HOST) return fail("dav_apply: host operator - move blocks with dav_panel_get/put");
-  if (o.kind == DAV_KIND_IDENTITY) {
-    launch_copy_columns(e->stream, src, e->ldp, dst, e->ldp, e->nloc_pad, k);
-    return 0;
-  }
-  CHK(need_comm(e));
-  if (o.kind == DAV_KIND_DEVICE) {
-    // the caller's kernel(s): the block as ONE column-major matrix of all n rows (several ranks: gathered column by column in one
-    // grouped collective - slab r of a column is rows [r * nslab, (r + 1) * nslab)), the result straight into this rank's panel rows
-    const double* x = src;
-    int64_t ldx = e->ldp;
-    int slot = -1;
-    if (timed) CHK(timed_begin(e, which == DAV_OP_A ? 0 : 2, 16.0 * (double)e->n * k, &slot));
-    if (has_comm(e)) {
-      ldx = (int64_t)e->nranks * e->nslab;
-      const size_t need = (size_t)ldx * k;
-      if (need > e->cb_x_doubles) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (e->cb_x) HIPCHK(pool_free(e->cb_x));
-        e->cb_x = nullptr; e->cb_x_doubles = 0;
-        HIPCHK(pool_malloc(&e->cb_x, sizeof(double) * need));
-        e->cb_x_doubles = need;
-      }
-      CollGroup grp(e);
-      CHK(grp.begin(5, 8.0 * (double)e->nslab * k * e->nranks));
-      for (int c = 0; c < k; ++c) CHK(coll_allgather(e, src + (int64_t)c * e->ldp, e->cb_x + (int64_t)c * ldx, (size_t)e->nslab));
-      CHK(grp.end("all-gather of the new block", e->stream));
-      x = e->cb_x;
+static int apply_identity(E* e, const double* src, int k, double* dst) { launch_copy_columns(e->stream, src, e->ldp, dst, e->ldp, e->nloc_pad, k); return 0; }
+
+// the caller's kernel(s): the block as ONE column-major matrix of all n rows (several ranks: gathered column by column in one
+// grouped collective - slab r of a column is rows [r * nslab, (r + 1) * nslab)), the result straight into this rank's panel rows
+static int apply_device(E* e, int which, OpDesc& o, const double* src, int k, double* dst, bool timed) {
+  const double* x = src;
+  int64_t ldx = e->ldp;
+  int slot = -1;
+  if (timed) CHK(timed_begin(e, which == DAV_OP_A ? 0 : 2, 16.0 * (double)e->n * k, &slot));
+  if (has_comm(e)) {
+    ldx = (int64_t)e->nranks * e->nslab;
+    const size_t need = (size_t)ldx * k;
+    if (need > e->cb_x_doubles) {
+      HIPCHK(hipStreamSynchronize(e->stream));
+      if (e->cb_x) HIPCHK(pool_free(e->cb_x));
+      e->cb_x = nullptr; e->cb_x_doubles = 0;
+      HIPCHK(pool_malloc(&e->cb_x, sizeof(double) * need));
+      e->cb_x_doubles = need;
     }
-    const int rc = o.dev_fn(o.dev_ctx, (void*)e->stream, e->n, e->row0, e->nloc, k, x, ldx, dst, e->ldp);
-    if (rc != 0) return fail("dav_apply: the caller's device operator returned " + std::to_string(rc));
-    launch_zero_pad_rows(e->stream, dst, e->ldp, e->nloc, e->nloc_pad, k);     // the panels' padding rows stay zero whatever the callback left there
-    CHK(timed_end(e, slot));
-    if (which == DAV_OP_A) { e->st.applies += 1; e->st.apply_cols += k; }
-    HIPCHK(hipGetLastError());
-    return 0;
+    CollGroup grp(e);
+    CHK(grp.begin(5, 8.0 * (double)e->nslab * k * e->nranks));
+    for (int c = 0; c < k; ++c) CHK(coll_allgather(e, src + (int64_t)c * e->ldp, e->cb_x + (int64_t)c * ldx, (size_t)e->nslab));
+    CHK(grp.end("all-gather of the new block", e->stream));
+    x = e->cb_x;
   }
-  if (o.kind == DAV_KIND_CSR || o.kind == DAV_KIND_BSR) {
-    // The rows of this rank (CSR, k_spmm.hip) or the block rows touching its slab (BSR, k_bsrmm.hip): the operand packed - and gathered over
-    // the ranks - as for the row slabs, then one launch of the wave-per-item kernel per 64 columns (the matrix is read once per 64 columns)
-    // and the chunk sums of the long rows.  Always fp64 (inner sweeps too: there is no fp32 copy of a sparse operator).
-    const SparseStore& s = o.sp;
-    for (int c = 0; c < k; c += 64) {
-      const int kk = std::min(64, k - c), groups = (kk + 15) / 16, gp = groups == 3 ? 4 : groups;
-      int slot = -1, kslot = -1;
-      double bytes, flops;
-      sparse_traffic(e, o, kk, &bytes, &flops);
-      if (timed) CHK(timed_begin(e, which == DAV_OP_A ? 0 : 2, bytes, &slot));
-      launch_pack_xt(e->stream, src + (int64_t)c * e->ldp, e->ldp, e->nloc, e->nslab, kk, e->xt, e->xt_group_stride, e->row0);
-      if (has_comm(e)) {
-        CollGroup grp(e);
-        CHK(grp.begin(5, 8.0 * (double)e->nslab * 16 * groups * e->nranks));
-        for (int g = 0; g < groups; ++g) {
-          double* base = e->xt + g * e->xt_group_stride;
-          CHK(coll_allgather(e, base + e->row0 * 16, base, (size_t)e->nslab * 16));
-        }
-        CHK(grp.end("all-gather of the new block", e->stream));
-      }
-      double* out = dst + (int64_t)c * e->ldp;
-      if (timed && which == DAV_OP_A) CHK(timed_begin(e, 4, flops, &kslot));
-      if (o.kind == DAV_KIND_CSR) {
-        launch_spmm_csr(e->stream, s.items, s.nitems, s.rp, s.col, s.val, e->xt, e->xt_group_stride, gp, kk, s.part, out, e->ldp);
-        launch_spmm_csr_finish(e->stream, s.longs, s.nlong, s.part, kk, out, e->ldp);
-      } else {
-        launch_spmm_bsr(e->stream, s.items, s.nitems, s.b, s.rp, s.col, s.val, e->xt, e->xt_group_stride, gp, kk, s.part, out, e->ldp, s.grow0,
-                        e->nloc);
-        launch_spmm_bsr_finish(e->stream, s.longs, s.nlong, s.part, s.b, kk, out, e->ldp, s.grow0, e->nloc);
-      }
-      CHK(timed_end(e, kslot));
-      launch_zero_pad_rows(e->stream, out, e->ldp, e->nloc, e->nloc_pad, kk);
-      CHK(timed_end(e, slot));
-      if (which == DAV_OP_A) {
-        e->st.applies += 1;
-        e->st.apply_cols += kk;
-      }
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  if ((o.kind == DAV_KIND_DENSE || o.kind == DAV_KIND_HASHED || o.kind == DAV_KIND_HARNESS) && o.storage == 1) {
-    // A generated second operator whose tiles (partly) fit next to everything else is kept resident for its longest block rows
-    // (configs[3]: B = the unit-diagonal generator next to a stored A): those rows run the stored kernels - half the time per
-    // 16 columns of the generated sweep, a quarter in the 32- / 64-column launches - the others are generated as before; the
-    // two parts are summed in fixed order (the generated part adds to the resident part's result).
-    if (o.kind == DAV_KIND_HASHED && which == DAV_OP_B && !o.res_decided) CHK(sym_resident_split(e, which));
-    if (o.res) {
-      bool accumulate = false;
-      if (o.pass_res) {
-        OpDesc stored = OpDesc();
-        stored.kind = DAV_KIND_DENSE; stored.storage = 1; stored.a = o.res_a; stored.a32_refused = true;
-        CHK(apply_sym_set(e, which, stored, *o.res, true, false, src, k, dst, timed, inner));
-        accumulate = true;
-      }
-      if (o.pass_gen) CHK(apply_sym_set(e, which, o, *o.gen, true, accumulate, src, k, dst, timed, inner));
-      return 0;
-    }
-    return apply_sym_set(e, which, o, e->sym, false, false, src, k, dst, timed, inner);
-  }
+  const int rc = o.dev_fn(o.dev_ctx, (void*)e->stream, e->n, e->row0, e->nloc, k, x, ldx, dst, e->ldp);
+  if (rc != 0) return fail("dav_apply: the caller's device operator returned " + std::to_string(rc));
+  launch_zero_pad_rows(e->stream, dst, e->ldp, e->nloc, e->nloc_pad, k);     // the panels' padding rows stay zero whatever the callback left there
+  CHK(timed_end(e, slot));
+  count_apply(e, which, k);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// The rows of this rank (CSR, k_spmm.hip) or the block rows touching its slab (BSR, k_bsrmm.hip): the operand packed - and gathered over
+// the ranks - as for the row slabs, then one launch of the wave-per-item kernel per 64 columns (the matrix is read once per 64 columns)
+// and the chunk sums of the long rows.  Always fp64 (inner sweeps too: there is no fp32 copy of a sparse operator).
+static int apply_sparse(E* e, int which, OpDesc& o, const double* src, int k, double* dst, bool timed) {
+  const SparseStore& s = o.sp;
   for (int c = 0; c < k; c += 64) {
-    int kk = std::min(64, k - c);
-    int groups = (kk + 15) / 16;
-    int ngroups = groups == 3 ? 4 : groups;
+    const int kk = std::min(64, k - c), groups = (kk + 15) / 16, gp = groups == 3 ? 4 : groups;
+    int slot = -1, kslot = -1;
+    double bytes, flops;
+    sparse_traffic(e, o, kk, &bytes, &flops);
+    if (timed) CHK(timed_begin(e, which == DAV_OP_A ? 0 : 2, bytes, &slot));
+    CHK(pack_operand(e, src + (int64_t)c * e->ldp, kk, has_comm(e)));
+    double* out = dst + (int64_t)c * e->ldp;
+    if (timed && which == DAV_OP_A) CHK(timed_begin(e, 4, flops, &kslot));
+    if (o.kind == DAV_KIND_CSR) {
+      launch_spmm_csr(e->stream, s.items, s.nitems, s.rp, s.col, s.val, e->xt, e->xt_group_stride, gp, kk, s.part, out, e->ldp);
+      launch_spmm_csr_finish(e->stream, s.longs, s.nlong, s.part, kk, out, e->ldp);
+    } else {
+      launch_spmm_bsr(e->stream, s.items, s.nitems, s.b, s.rp, s.col, s.val, e->xt, e->xt_group_stride, gp, kk, s.part, out, e->ldp, s.grow0, e->nloc);
+      launch_spmm_bsr_finish(e->stream, s.longs, s.nlong, s.part, s.b, kk, out, e->ldp, s.grow0, e->nloc);
+    }
+    CHK(timed_end(e, kslot));
+    launch_zero_pad_rows(e->stream, out, e->ldp, e->nloc, e->nloc_pad, kk);
+    CHK(timed_end(e, slot));
+    count_apply(e, which, kk);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// Symmetric tiles, stored or generated.  A generated second operator whose tiles (partly) fit next to everything else is kept
+// resident for its longest block rows (configs[3]: B = the unit-diagonal generator next to a stored A): those rows run the stored
+// kernels - half the time per 16 columns of the generated sweep, a quarter in the 32- / 64-column launches - the others are generated
+// as before; the two parts are summed in fixed order (the generated part adds to the resident part's result).
+static int apply_symmetric(E* e, int which, OpDesc& o, const double* src, int k, double* dst, bool timed, bool inner) {
+  if (o.kind == DAV_KIND_HASHED && which == DAV_OP_B && !o.res_decided) CHK(sym_resident_split(e, which));
+  if (!o.res) return apply_sym_set(e, which, o, e->sym, false, false, src, k, dst, timed, inner);
+  bool accumulate = false;
+  if (o.pass_res) {
+    OpDesc stored = OpDesc();
+    stored.kind = DAV_KIND_DENSE; stored.storage = 1; stored.a = o.res_a; stored.a32_refused = true;
+    CHK(apply_sym_set(e, which, stored, *o.res, true, false, src, k, dst, timed, inner));
+    accumulate = true;
+  }
+  if (o.pass_gen) CHK(apply_sym_set(e, which, o, *o.gen, true, accumulate, src, k, dst, timed, inner));
+  return 0;
+}
+
+// full rows, stored or generated: this rank's row slab against the gathered block, 64 columns per launch
+static int apply_full_rows(E* e, int which, OpDesc& o, const double* src, int k, double* dst, bool timed) {
+  for (int c = 0; c < k; c += 64) {
+    const int kk = std::min(64, k - c), groups = (kk + 15) / 16, ngroups = groups == 3 ? 4 : groups;
     int slot = -1, kslot = -1;
     double bytes = 8.0 * (double)e->nloc * (double)e->n + 16.0 * (double)e->n * kk;
     if (timed) CHK(timed_begin(e, which == DAV_OP_A ? 0 : 2, bytes, &slot));
-    launch_pack_xt(e->stream, src + (int64_t)c * e->ldp, e->ldp, e->nloc, e->nslab, kk, e->xt, e->xt_group_stride, e->row0);
-    if (has_comm(e)) {
-      CollGroup grp(e);
-      CHK(grp.begin(5, 8.0 * (double)e->nslab * 16 * groups * e->nranks));
-      for (int g = 0; g < groups; ++g) {
-        double* base = e->xt + g * e->xt_group_stride;
-        CHK(coll_allgather(e, base + e->row0 * 16, base, (size_t)e->nslab * 16));
-      }
-      CHK(grp.end("all-gather of the new block", e->stream));
-    }
+    CHK(pack_operand(e, src + (int64_t)c * e->ldp, kk, has_comm(e)));
     int nsplit, jc;
     matvec_plan(e->nloc_pad, e->ncols_pad, ngroups, &nsplit, &jc, e->tune.mv_target, e->tune.mv_nsplit);
     if (matvec_slab_doubles(e->nloc_pad, ngroups, nsplit) > e->scratch_doubles) return fail("matvec scratch too small");
     if (timed && which == DAV_OP_A) CHK(timed_begin(e, 4, 2.0 * (double)e->nloc * (double)e->n * kk, &kslot));
     if (o.kind == DAV_KIND_DENSE)
-      launch_matvec_dense(e->stream, o.a, e->nloc_pad, e->nloc_pad, e->ncols_pad, e->xt, e->xt_group_stride, ngroups,
-                          e->scratch, nsplit, jc);
+      launch_matvec_dense(e->stream, o.a, e->nloc_pad, e->nloc_pad, e->ncols_pad, e->xt, e->xt_group_stride, ngroups, e->scratch, nsplit, jc);
     else
-      launch_matvec_free(e->stream, op_params(o), e->row0, e->nloc, e->n, e->nloc_pad, e->ncols_pad, e->xt,
-                         e->xt_group_stride, ngroups, e->scratch, nsplit, jc);
+      launch_matvec_free(e->stream, op_params(o), e->row0, e->nloc, e->n, e->nloc_pad, e->ncols_pad, e->xt, e->xt_group_stride, ngroups, e->scratch, nsplit, jc);
     CHK(timed_end(e, kslot));               // inner pair: the block-matvec kernel alone
     launch_slab_reduce(e->stream, e->scratch, nsplit, e->nloc_pad, ngroups, e->nloc, kk, dst + (int64_t)c * e->ldp, e->ldp);
     CHK(timed_end(e, slot));                // outer pair: pack + all-gather + kernel + reduction
-    if (which == DAV_OP_A) {
-      e->st.applies += 1;
-      e->st.apply_cols += kk;
-    }
+    count_apply(e, which, kk);
   }
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+// inner = true: a sweep inside the GJD correction solve (may run on the fp32 copy, dav_set_inner_precision)
+int apply_ptr(E* e, int which, const double* src, int k, double* dst, bool timed, bool inner) {
+  OpDesc& o = e->op[which];
+  if (o.kind == DAV_KIND_NONE) return fail("dav_apply: operator not set");
+  if (o.kind == DAV_KIND_HOST) return fail("dav_apply: host operator - move blocks with dav_panel_get/put");
+  if (o.kind == DAV_KIND_IDENTITY) return apply_identity(e, src, k, dst);
+  CHK(need_comm(e));
+  if (o.kind == DAV_KIND_DEVICE) return apply_device(e, which, o, src, k, dst, timed);
+  if (o.kind == DAV_KIND_CSR || o.kind == DAV_KIND_BSR) return apply_sparse(e, which, o, src, k, dst, timed);
+  if ((o.kind == DAV_KIND_DENSE || o.kind == DAV_KIND_HASHED || o.kind == DAV_KIND_HARNESS) && o.storage == 1)
+    return apply_symmetric(e, which, o, src, k, dst, timed, inner);
+  return apply_full_rows(e, which, o, src, k, dst, timed);
 }
 
 // W0 = Op * V0 for the unit columns V0 = e_idx of dav_init_basis over SEVERAL ranks of dealt-out symmetric tiles, without a sweep:
@@ -605,10 +566,7 @@ int apply_ptr(E* e, int which, const double* src, int k, double* dst, bool timed
 // N=200000 - a third of a configs[2] solve on several GPUs; this costs the reduce-scatter of 2 x N x 16 doubles.
 int gather_columns_sym_multi(E* e, OpDesc& o, int ncols, double* dst, double* h0) {
   CHK(need_comm(e));
-  if (!e->sym_wpart) {
-    HIPCHK(pool_malloc(&e->sym_wpart, sizeof(double) * (size_t)e->nranks * (size_t)e->nslab * 64));
-    HIPCHK(pool_malloc(&e->sym_wrecv, sizeof(double) * (size_t)e->nslab * 64));
-  }
+  CHK(ensure_sym_wpart(e));
   const int64_t total_rows = (int64_t)e->nranks * e->nslab;
   for (int c = 0; c < ncols; c += 32) {
     const int kk = std::min(32, ncols - c), npair = (kk + 15) / 16;
@@ -617,26 +575,19 @@ int gather_columns_sym_multi(E* e, OpDesc& o, int ncols, double* dst, double* h0
                                    e->sym_wpart + (size_t)g * (size_t)total_rows * 16);
     // h0 (dav_init_basis): the entries (idx_i, idx_j) this rank holds, summed over the ranks by an all-reduce that is a member of the
     // first reduce-scatter's group - V0^T W0 without a collective (and a Gram product) of its own
-    if (h0 && c == 0) launch_entries_sym(e->stream, o.a, e->sym.row_off, e->idx_dev, ncols, h0);
-    CollGroup grp(e);
-    CHK(grp.begin(6, 8.0 * (double)e->nslab * kk * e->nranks));
-    for (int g = 0; g < npair; ++g)
-      CHK(coll_reduce_scatter(e, e->sym_wpart + (size_t)g * (size_t)total_rows * 16, e->sym_wrecv + (size_t)g * (size_t)e->nslab * 16,
-                              (size_t)e->nslab * std::min(16, kk - 16 * g)));
-    if (h0 && c == 0) CHK(coll_allreduce(e, h0, (size_t)ncols * ncols));
-    CHK(grp.end("reduce-scatter of the gathered columns", e->stream));
-    for (int g = 0; g < npair; ++g)
-      launch_chunk_to_panel(e->stream, e->sym_wrecv + (size_t)g * (size_t)e->nslab * 16, e->nslab, e->nloc, e->nloc_pad, std::min(16, kk - 16 * g),
-                            dst + (int64_t)(c + 16 * g) * e->ldp, e->ldp, false);
+    const bool with_h0 = h0 && c == 0;
+    if (with_h0) launch_entries_sym(e->stream, o.a, e->sym.row_off, e->idx_dev, ncols, h0);
+    CHK(sym_scatter_to_panel(e, kk, dst + (int64_t)c * e->ldp, false, "reduce-scatter of the gathered columns", with_h0 ? h0 : nullptr,
+                             (size_t)ncols * ncols));
   }
   HIPCHK(hipGetLastError());
   return 0;
 }
 
-int apply_impl(E* e, int which, int src_panel, int c0, int k, int dst_panel, int d0, bool timed) {
+int apply_impl(E* e, int which, int src_panel, int c0, int k, int dst_panel, int d0, bool timed, bool inner) {
   CHK(check_panel(e, src_panel, c0, k));
   CHK(check_panel(e, dst_panel, d0, k));
-  return apply_ptr(e, which, panel_ptr(e, src_panel, c0), k, panel_ptr(e, dst_panel, d0), timed);
+  return apply_ptr(e, which, panel_ptr(e, src_panel, c0), k, panel_ptr(e, dst_panel, d0), timed, inner);
 }
 
 extern "C" int dav_apply(dav_handle_t e, int which, int src_panel, int c0, int k, int dst_panel, int d0) {
@@ -650,10 +601,8 @@ extern "C" int dav_apply(dav_handle_t e, int which, int src_panel, int c0, int k
 extern "C" int dav_apply_inner(dav_handle_t e, int which, int src_panel, int c0, int k, int dst_panel, int d0) {
   if (which < 0 || which > 1) return fail("dav_apply_inner: bad operator id");
   CHK(bind(e));
-  CHK(check_panel(e, src_panel, c0, k));
-  CHK(check_panel(e, dst_panel, d0, k));
   if (dst_panel == DAV_PANEL_X) guess_drop(e);
-  return apply_ptr(e, which, panel_ptr(e, src_panel, c0), k, panel_ptr(e, dst_panel, d0), false, true);
+  return apply_impl(e, which, src_panel, c0, k, dst_panel, d0, false, true);
 }
 
 // ---- measurement --------------------------------------------------------------------------------
@@ -696,8 +645,7 @@ extern "C" int dav_bench_apply2(dav_handle_t e, int which, int k, int reps, doub
   }
   const bool sym = e->op[which].storage == 1;
   // per rank: the stored bytes and the flops of the symmetric sweep are dealt out over the ranks like its tiles
-  *bytes = (sym ? (e->op[which].kind == DAV_KIND_DENSE ? 8.0 * 0.5 * (double)e->n * ((double)e->n + 1.0) / e->nranks : 0.0)
-                : 8.0 * (double)e->nloc * (double)e->n) + 16.0 * (double)e->n * k;
+  *bytes = (sym ? sym_stored_bytes(e, e->op[which], e->sym, false, false) : 8.0 * (double)e->nloc * (double)e->n) + 16.0 * (double)e->n * k;
   *flops = 2.0 * (sym ? (double)e->n / e->nranks : (double)e->nloc) * (double)e->n * k;
   e->st = saved;
   return 0;

@@ -116,6 +116,18 @@ struct SymSet {
   bool built = false;
 };
 void sym_set_release(SymSet& s);
+// One launch of the symmetric sweep over kk columns of a set, as sym_launch (engine_operators.hip) decides it
+enum SymFamily { SYM_ROW_STORED, SYM_ROW_GENERATED, SYM_SUPER, SYM_WIDE, SYM_WIDE_GENERATED, SYM_WIDE_F32 };
+struct SymLaunch {
+  SymFamily family = SYM_SUPER;     // one block row (k_matvec_sym.hip), matvec_sym9, matvec_symw on fp64 tiles / generating / on fp32 tiles
+  int kk = 0, ngroups = 0;          // columns, 16-column groups
+  int R = 0, nwg = 0, nbw = 1;      // block rows per workgroup, workgroups per work item, matvec_symw: 16-column groups per workgroup
+  bool use32 = false, tall = false; // reads the fp32 copy of the tiles; matvec_symw on the R = 4 work items
+  const SymPlan* plan = nullptr;    // the super-row schedule read (R = 1: none, the set's own runs)
+  int nitems = 0;                   // work items
+  int64_t dstride = 0, tstride = 0; // doubles per column group of the direct / transposed partial slabs
+  int gen_evals = 0;                // times the generated entries are evaluated per launch (stored tiles: 0)
+};
 
 // A sparse operator of either kind (engine_sparse.hip): this rank's rows (CSR) or the block rows touching its slab (BSR) in canonical form,
 // and the work list of the block product.  OpDesc::kind says which kernel reads it (k_spmm.hip / k_bsrmm.hip).
@@ -373,7 +385,6 @@ struct SmallMat {
 };
 
 // ---- engine.hip ------------------------------------------------------------------------------------------
-int fail(const std::string& msg);
 int bind(E* e);
 int collect_events(E* e);
 int timed_begin(E* e, int kind, double bytes, int* slot);
@@ -387,7 +398,6 @@ double* panel_ptr(E* e, int panel, int col);
 int check_panel(E* e, int panel, int c0, int k);
 int create_impl(E* e, int device, int64_t n, int max_cols, int gev, int rank, int nranks);
 // ---- engine_comm.hip -------------------------------------------------------------------------------------
-int rccl_load();
 double wall_seconds();
 void watchdog_loop(Watchdog* w);
 bool has_comm(E* e);
@@ -398,12 +408,6 @@ int test_allgather(E* e, const double* send, double* recv, size_t count);
 int test_allreduce(E* e, double* buf, size_t count);
 int test_reduce_scatter(E* e, const double* send, double* recv, size_t count);
 void shm_release(E* e);
-bool has_test_transport(const E*);
-size_t test_transport_max_message(const E*);
-int test_allgather(E*, const double*, double*, size_t);
-int test_allreduce(E*, double*, size_t);
-int test_reduce_scatter(E*, const double*, double*, size_t);
-void shm_release(E*);
 int watch_mark(E* e, const char* what, hipStream_t stream);
 int coll_group_begin(E* e);
 int coll_group_end(E* e, const char* what, hipStream_t stream);
@@ -437,7 +441,7 @@ int coll_allreduce(E* e, double* buf, size_t count);
 int coll_reduce_scatter(E* e, const double* send, double* recv, size_t count);
 // ---- engine_operators.hip --------------------------------------------------------------------------------
 int refresh_diag_host(E* e, int which);
-int sym_schedule(const E* e, int kk, bool stored_fp64);
+SymLaunch sym_launch(const E* e, const OpDesc& o, const SymSet& set, int kk, bool use32, int R = 0);
 std::vector<int> sym_group_owners(int nb, int nranks);
 int sym_setup(E* e);
 int sym_build_set(E* e, int first_block_row, int end_block_row, SymSet& out);
@@ -460,12 +464,10 @@ bool device_array(E* e, const void* p, const char* name, size_t bytes, std::stri
 static inline void guess_drop(E* e) { e->guess_cols = 0; e->guess_tag = GUESS_NONE; }    // X is about to be written
 // ---- engine_apply.hip ------------------------------------------------------------------------------------
 bool inner_f32_tiles(E* e, OpDesc& o);
-bool sym_wide_enabled(const E* e);
-void sym9_sweep(E* e, int R, const OpDesc& o, bool use32, const SymPlan* pl, const double* xt, int kk, double* slabD, double* slabT,
-                       int npair, int64_t dstride, int64_t tstride);
-int apply_sym_overlapped(E* e, int which, OpDesc& o, const double* src, int k, double* dst, bool timed, bool inner);
+int apply_sym_set(E* e, int which, OpDesc& o, const SymSet& set, bool partial, bool accumulate, const double* src, int k, double* dst, bool timed,
+                  bool inner);
 int apply_ptr(E* e, int which, const double* src, int k, double* dst, bool timed, bool inner = false);
-int apply_impl(E* e, int which, int src_panel, int c0, int k, int dst_panel, int d0, bool timed);
+int apply_impl(E* e, int which, int src_panel, int c0, int k, int dst_panel, int d0, bool timed, bool inner = false);
 int gather_columns_sym_multi(E* e, OpDesc& o, int ncols, double* dst, double* h0 = nullptr);
 // ---- engine_solver.hip -----------------------------------------------------------------------------------
 double* result_target(E* e);

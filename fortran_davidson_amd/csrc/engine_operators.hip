@@ -20,11 +20,15 @@ int refresh_diag_host(E* e, int which) {
   return 0;
 }
 
+// Tune::sym_wide (DAV_SYM_WIDE at dav_create) = 2 (default): the one-wave-per-SIMD kernel for more than 8 columns, 1: for more
+// than 16 only, 0: never (A/B runs)
+static bool sym_wide_enabled(const E* e) { return e->tune.sym_wide > 1; }   // ... for 9-16 columns too
+
 // Block rows per workgroup of the symmetric sweep for a launch of kk columns: 4 (k <= 8 - and 9-16 columns of stored fp64 tiles -
 // from 200 block rows on), 2 (more than 8 columns, from 64 block rows on: the one-wave-per-SIMD kernel of k_matvec_symw.hip), or 1 (the one-block-row kernel of
 // k_matvec_sym.hip: small matrices, where super rows leave too few work items and too much of the matrix in the masked
 // diagonal super blocks).  Tune::sym_r (DAV_SYM_R at dav_create) = 1 | 2 | 4 forces a schedule (4 only if k <= 16).
-int sym_schedule(const E* e, int kk, bool stored_fp64) {
+static int sym_schedule(const E* e, int kk, bool stored_fp64) {
   const int forced = e->tune.sym_r;                     // DAV_SYM_R at dav_create
   const int nb = (int)(e->ncols_pad / SYM_TB);          // block rows of the whole matrix
   // k <= 8, crossover measured end to end on one box (ms for R = 1 | 2 | 4): N=40000 (157 block rows) 1.33 | 1.38 | 1.39; N=60000
@@ -42,6 +46,49 @@ int sym_schedule(const E* e, int kk, bool stored_fp64) {
   if (forced == 1 || forced == 2 || forced == 4) R = forced;
   if (R == 4 && kk > 8 && !(stored_fp64 && kk <= 16 && sym_wide_enabled(e))) R = 2;
   return R;
+}
+
+// what the wide kernel's generating variant evaluates: the hashed operator, (round 6) the polynomial form of the reference's test operator
+static bool generated_polynomial(const OpDesc& o) { return o.kind == DAV_KIND_HASHED || (o.kind == DAV_KIND_HARNESS && !o.harness_libm); }
+
+// What one launch of kk columns of the symmetric sweep over `set` runs, decided HERE only: the launch, the slabs, the reductions, the
+// level-2 timing and the choice of columns per launch (engine_apply.hip) read it.  R = 0: sym_schedule picks the block rows per
+// workgroup; R > 0: the caller's (launches that share slabs laid out for that schedule).
+// Super rows: stored fp64 tiles, two block rows per workgroup and more than 8 columns run the one-wave-per-SIMD kernel
+// (k_matvec_symw.hip: 32 columns per workgroup, or 16 for a block of <= 16); generated operators, the fp32 copy and the k <= 8
+// schedule (R = 4, 4x4x4 MFMA) stay on matvec_sym9_kernel.
+SymLaunch sym_launch(const E* e, const OpDesc& o, const SymSet& set, int kk, bool use32, int R) {
+  const bool stored = o.kind == DAV_KIND_DENSE;
+  const int wide = e->tune.sym_wide;
+  if (R == 0) {
+    R = sym_schedule(e, kk, stored && !use32);      // (the harness operator runs the super-row kernels too since round 5)
+    if (use32 && R == 1) R = 2;                     // the fp32 tiles are read by the super-row kernels only
+  }
+  SymLaunch L;
+  L.kk = kk; L.ngroups = L.nwg = (kk + 15) / 16; L.use32 = use32; L.R = R;
+  if (R == 1) {
+    L.family = stored ? SYM_ROW_STORED : SYM_ROW_GENERATED;
+    L.nitems = set.nitems;
+    L.dstride = (int64_t)set.nitems * 16 * SYM_TB;
+    L.tstride = (int64_t)e->sym_nb * (e->sym_nb - 1) / 2 * 16 * SYM_TB;
+  } else {
+    L.plan = &set.plan[R == 4 ? 1 : 0];
+    L.nitems = L.plan->nitems;
+    L.dstride = (int64_t)L.nitems * R * 16 * SYM_TB;
+    L.tstride = L.plan->zslots * 16 * SYM_TB;
+    if (stored && !use32 && wide > 0 && ((R == 2 && (kk > 16 || wide > 1)) || (R == 4 && kk > 8 && kk <= 16))) {
+      L.family = SYM_WIDE; L.nbw = kk > 16 ? 2 : 1; L.tall = R == 4;
+    } else if (generated_polynomial(o) && R == 2 && kk > 16 && wide > 0 && e->tune.sym_gen_wide) {
+      // 17-32 columns per launch: one generated entry feeds the MFMAs of both 16-column groups (Tune::sym_gen_wide = 0: two groups
+      // of the 16-column kernel, every entry generated twice)
+      L.family = SYM_WIDE_GENERATED; L.nbw = 2;
+    } else if (stored && use32 && wide > 1 && e->tune.sym_wide32 && R == 2 && kk <= 16) {
+      L.family = SYM_WIDE_F32;     // mixed-precision inner sweeps, up to 16 columns; Tune::sym_wide32 = 0: the two-wave kernel
+    }
+    L.nwg = (L.ngroups + L.nbw - 1) / L.nbw;
+  }
+  L.gen_evals = stored ? 0 : L.nwg;      // each workgroup of a work item generates the item's entries
+  return L;
 }
 
 // Owners of the groups of 4 block rows (what every schedule's super rows nest in): longest group first, each to the rank
