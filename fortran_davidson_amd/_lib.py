@@ -5,6 +5,8 @@ import ctypes as C
 import os
 import subprocess
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, "lib")
 HIP_LIB = os.environ.get("DAVIDSON_HIP_LIB", os.path.join(LIB_DIR, "libdavidson_hip.so"))   # override: A/B builds
@@ -42,8 +44,9 @@ def hip_lib() -> C.CDLL:
             import torch  # noqa: F401
         except ImportError:    # harness without PyTorch: the system runtime is the only one
             pass
-        _hip = C.CDLL(HIP_LIB, mode=C.RTLD_LOCAL)
-        _hip.dav_last_error.restype = C.c_char_p
+        lib = C.CDLL(HIP_LIB, mode=C.RTLD_LOCAL)
+        _abi.apply(lib, _abi.DAV, optional=_abi.TEST_BUILD_ONLY)       # raises before the library can be used without prototypes
+        _hip = lib
         runtimes = hip_runtimes_mapped()
         if len(runtimes) > 1:
             raise RuntimeError("two HIP runtimes are mapped into this process (" + ", ".join(runtimes) + "): the "
@@ -74,7 +77,7 @@ def fortran_lib() -> C.CDLL:
         hip_lib()
         if not os.path.exists(FORTRAN_LIB):
             raise NativeLibraryMissing(f"{FORTRAN_LIB} not built: run `make -C fortran_davidson_amd`")
-        _fortran = C.CDLL(FORTRAN_LIB, mode=C.RTLD_GLOBAL)  # MKL dlopens its kernels and needs libmkl_core global
-        _fortran.fd_engine_create.restype = C.c_void_p
-        _fortran.fd_engine_handle.restype = C.c_void_p
+        lib = C.CDLL(FORTRAN_LIB, mode=C.RTLD_GLOBAL)  # MKL dlopens its kernels and needs libmkl_core global
+        _abi.apply(lib, _abi.FD)
+        _fortran = lib
     return _fortran

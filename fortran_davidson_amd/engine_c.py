@@ -321,6 +321,11 @@ def _f(a):
     return np.asfortranarray(a, dtype=np.float64)
 
 
+def _optional(x):
+    """(use_x, x) as the C side takes an optional double: `int use_x, double x`"""
+    return (0, 0.0) if x is None else (1, x)
+
+
 class CEngine:
     """RAII wrapper over dav_create/dav_destroy.  `handle` may be borrowed from the Fortran side."""
 
@@ -331,8 +336,7 @@ class CEngine:
         self.owned = handle is None
         if handle is None:
             h = C.c_void_p()
-            self._chk(self.lib.dav_create(C.byref(h), C.c_int(device), C.c_int64(n), C.c_int(max_cols),
-                                          C.c_int(1 if gev else 0), C.c_int(rank), C.c_int(nranks)))
+            self._chk(self.lib.dav_create(C.byref(h), device, n, max_cols, int(gev), rank, nranks))
             self.h = h
         else:
             self.h = C.c_void_p(handle)
@@ -358,7 +362,7 @@ class CEngine:
     # -- bookkeeping
     def stats(self) -> Stats:
         st = Stats()
-        self._chk(self.lib.dav_get_stats_n(self.h, C.byref(st), C.c_size_t(C.sizeof(st))))
+        self._chk(self.lib.dav_get_stats_n(self.h, C.byref(st), C.sizeof(st)))
         return st
 
     def reset_stats(self):
@@ -366,7 +370,7 @@ class CEngine:
 
     def set_timing(self, level):
         """0 = no events, 1 = block matvec only (default), 2 = every phase (gram_ms, panel_ms, comm_ms)."""
-        self._chk(self.lib.dav_set_timing(self.h, C.c_int(level)))
+        self._chk(self.lib.dav_set_timing(self.h, level))
 
     def synchronize(self):
         self._chk(self.lib.dav_synchronize(self.h))
@@ -412,54 +416,49 @@ class CEngine:
 
     def set_storage(self, mode):
         """0 = full storage, 1 = symmetric-tiled (lower block triangle only)."""
-        self._chk(self.lib.dav_set_storage(self.h, C.c_int(mode)))
+        self._chk(self.lib.dav_set_storage(self.h, mode))
 
     def set_dense_host(self, which, a):
         a = _f(a)
-        self._chk(self.lib.dav_set_dense_host(self.h, C.c_int(which), _dp(a), C.c_int64(a.shape[0])))
+        self._chk(self.lib.dav_set_dense_host(self.h, which, _dp(a), a.shape[0]))
 
     def set_dense_dev(self, which, dev_ptr, lda):
         """a(lda, n) column-major in device memory (e.g. a torch tensor's data_ptr())."""
-        self._chk(self.lib.dav_set_dense_dev(self.h, C.c_int(which), C.c_void_p(dev_ptr), C.c_int64(lda)))
+        self._chk(self.lib.dav_set_dense_dev(self.h, which, dev_ptr, lda))
 
     def set_dense_generated(self, which, seed, sparsity, diag_val=None):
-        self._chk(self.lib.dav_set_dense_generated(self.h, C.c_int(which), C.c_uint64(seed), C.c_double(sparsity),
-                                                   C.c_int(0 if diag_val is None else 1),
-                                                   C.c_double(0.0 if diag_val is None else diag_val)))
+        self._chk(self.lib.dav_set_dense_generated(self.h, which, seed, sparsity, *_optional(diag_val)))
 
     # -- streaming ingest (rows in the reference's on-disk order, row-major)
     def dense_begin(self, which):
-        self._chk(self.lib.dav_dense_begin(self.h, C.c_int(which)))
+        self._chk(self.lib.dav_dense_begin(self.h, which))
 
     def dense_put_rows(self, which, row0, rows):
         """rows: (nrows, n) C-ordered block of complete rows, global rows row0..row0+nrows-1."""
         r = np.ascontiguousarray(rows, dtype=np.float64)
-        self._chk(self.lib.dav_dense_put_rows(self.h, C.c_int(which), C.c_int64(row0), C.c_int64(r.shape[0]), _dp(r),
-                                              C.c_int64(r.shape[1])))
+        self._chk(self.lib.dav_dense_put_rows(self.h, which, row0, r.shape[0], _dp(r), r.shape[1]))
 
     def dense_end(self, which):
-        self._chk(self.lib.dav_dense_end(self.h, C.c_int(which)))
+        self._chk(self.lib.dav_dense_end(self.h, which))
 
     def set_dense_file(self, which, path, fmt="text"):
         """fmt: "text" = the reference's write_matrix/read_matrix format, "f64" = raw row-major float64."""
         code = {"text": 0, "f64": 1}[fmt]
-        self._chk(self.lib.dav_set_dense_file(self.h, C.c_int(which), str(path).encode(), C.c_int(code)))
+        self._chk(self.lib.dav_set_dense_file(self.h, which, str(path).encode(), code))
 
     def set_operator_hashed(self, which, seed, sparsity, diag_val=None):
-        self._chk(self.lib.dav_set_operator_hashed(self.h, C.c_int(which), C.c_uint64(seed), C.c_double(sparsity),
-                                                   C.c_int(0 if diag_val is None else 1),
-                                                   C.c_double(0.0 if diag_val is None else diag_val)))
+        self._chk(self.lib.dav_set_operator_hashed(self.h, which, seed, sparsity, *_optional(diag_val)))
 
     def set_operator_harness(self, which, e_table):
         e = np.ascontiguousarray(e_table, dtype=np.float64)
-        self._chk(self.lib.dav_set_operator_harness(self.h, C.c_int(which), _dp(e)))
+        self._chk(self.lib.dav_set_operator_harness(self.h, which, _dp(e)))
 
     def set_operator_identity(self, which):
-        self._chk(self.lib.dav_set_operator_identity(self.h, C.c_int(which)))
+        self._chk(self.lib.dav_set_operator_identity(self.h, which))
 
     def set_operator_host(self, which, diag):
         d = np.ascontiguousarray(diag, dtype=np.float64)
-        self._chk(self.lib.dav_set_operator_host(self.h, C.c_int(which), _dp(d)))
+        self._chk(self.lib.dav_set_operator_host(self.h, which, _dp(d)))
 
     def set_operator_device(self, which, fn, ctx, diag):
         """The caller's own block apply on device memory (dav_device_apply_fn): `fn` a ctypes function pointer (DEVICE_APPLY_FN or a
@@ -467,7 +466,7 @@ class CEngine:
         d = np.ascontiguousarray(diag, dtype=np.float64)
         self._device_ops = getattr(self, "_device_ops", {})
         self._device_ops[which] = (fn, ctx)                # keep the callback alive as long as the engine
-        self._chk(self.lib.dav_set_operator_device(self.h, C.c_int(which), C.cast(fn, C.c_void_p), C.c_void_p(ctx if isinstance(ctx, int) else C.cast(ctx, C.c_void_p).value), _dp(d)))
+        self._chk(self.lib.dav_set_operator_device(self.h, which, fn, ctx, _dp(d)))
 
     def set_operator_csr(self, which, indptr, indices=None, data=None, base=0, lower=False):
         """dav_set_operator_csr: a symmetric matrix in CSR form (the global arrays; indptr / indices numbered from `base`), every nonzero
@@ -483,8 +482,8 @@ class CEngine:
         ci_p = ci.ctypes.data_as(C.POINTER(C.c_int32)) if ci.size else (C.c_int32 * 1)()
         vv_p = _dp(vv) if vv.size else (C.c_double * 1)()
         self._saw_values(which, None)
-        self._chk(self.lib.dav_set_operator_csr(self.h, C.c_int(which), rp.ctypes.data_as(C.POINTER(C.c_int64)), ci_p, vv_p, C.c_int(base),
-                                                C.c_int(CSR_LOWER if lower else CSR_FULL)))
+        self._chk(self.lib.dav_set_operator_csr(self.h, which, rp.ctypes.data_as(C.POINTER(C.c_int64)), ci_p, vv_p, base,
+                                                CSR_LOWER if lower else CSR_FULL))
         self._saw_values(which, int(rp[-1] - rp[0]))
 
     def set_operator_csr_dev(self, which, row_ptr, col_idx, vals, base=0, lower=False):
@@ -496,10 +495,8 @@ class CEngine:
         import torch
         torch.cuda.current_stream(row_ptr.device).synchronize()
         self._saw_values(which, None)
-        self._chk(self.lib.dav_set_operator_csr_dev(self.h, C.c_int(which), C.c_void_p(row_ptr.data_ptr()), C.c_int(rpb),
-                                                    C.c_void_p(col_idx.data_ptr() or None), C.c_int(cib),
-                                                    C.c_void_p(vals.data_ptr() or None), C.c_int(base),
-                                                    C.c_int(CSR_LOWER if lower else CSR_FULL)))
+        self._chk(self.lib.dav_set_operator_csr_dev(self.h, which, row_ptr.data_ptr(), rpb, col_idx.data_ptr() or None, cib,
+                                                    vals.data_ptr() or None, base, CSR_LOWER if lower else CSR_FULL))
         self._saw_values(which, nnz)
 
     def set_operator_bsr(self, which, indptr, indices=None, data=None, base=0, lower=False, layout=BSR_ROW_MAJOR):
@@ -517,8 +514,8 @@ class CEngine:
         ci_p = ci.ctypes.data_as(C.POINTER(C.c_int32)) if ci.size else (C.c_int32 * 1)()
         vv_p = _dp(vv) if vv.size else (C.c_double * 1)()
         self._saw_values(which, None)
-        self._chk(self.lib.dav_set_operator_bsr(self.h, C.c_int(which), C.c_int(b), rp.ctypes.data_as(C.POINTER(C.c_int64)), ci_p, vv_p,
-                                                C.c_int(base), C.c_int(CSR_LOWER if lower else CSR_FULL), C.c_int(layout)))
+        self._chk(self.lib.dav_set_operator_bsr(self.h, which, b, rp.ctypes.data_as(C.POINTER(C.c_int64)), ci_p, vv_p, base,
+                                                CSR_LOWER if lower else CSR_FULL, layout))
         self._saw_values(which, int(rp[-1] - rp[0]) * b * b)
 
     def set_operator_bsr_dev(self, which, row_ptr, col_idx, vals, base=0, lower=False, layout=BSR_ROW_MAJOR):
@@ -530,10 +527,8 @@ class CEngine:
         import torch
         torch.cuda.current_stream(row_ptr.device).synchronize()
         self._saw_values(which, None)
-        self._chk(self.lib.dav_set_operator_bsr_dev(self.h, C.c_int(which), C.c_int(b), C.c_void_p(row_ptr.data_ptr()), C.c_int(rpb),
-                                                    C.c_void_p(col_idx.data_ptr() or None), C.c_int(cib),
-                                                    C.c_void_p(vals.data_ptr() or None), C.c_int(base),
-                                                    C.c_int(CSR_LOWER if lower else CSR_FULL), C.c_int(layout)))
+        self._chk(self.lib.dav_set_operator_bsr_dev(self.h, which, b, row_ptr.data_ptr(), rpb, col_idx.data_ptr() or None, cib,
+                                                    vals.data_ptr() or None, base, CSR_LOWER if lower else CSR_FULL, layout))
         self._saw_values(which, nnzb * b * b)
 
     def _saw_values(self, which, count):
@@ -545,7 +540,7 @@ class CEngine:
         """dav_keep_value_map: a sticky switch per operator; the NEXT sparse set call of `which` also keeps where every stored value came
         from (8 bytes per entry or block of this rank, 16 per row or block row), which update_operator_values needs.  No effect on an
         operator that is already set."""
-        self._chk(self.lib.dav_keep_value_map(self.h, C.c_int(which), C.c_int(1 if on else 0)))
+        self._chk(self.lib.dav_keep_value_map(self.h, which, int(on)))
 
     def update_operator_values(self, which, vals):
         """dav_update_operator_values / dav_update_operator_values_dev: new values on the kept pattern of a CSR or BSR operator set after
@@ -558,19 +553,19 @@ class CEngine:
         if dev is not None:
             import torch
             torch.cuda.current_stream(dev.device).synchronize()
-            self._chk(self.lib.dav_update_operator_values_dev(self.h, C.c_int(which), C.c_void_p(dev.data_ptr() or None)))
+            self._chk(self.lib.dav_update_operator_values_dev(self.h, which, dev.data_ptr() or None))
         else:
-            self._chk(self.lib.dav_update_operator_values(self.h, C.c_int(which), _dp(host) if host.size else (C.c_double * 1)()))
+            self._chk(self.lib.dav_update_operator_values(self.h, which, _dp(host) if host.size else (C.c_double * 1)()))
 
     def get_diagonal(self, which):
         d = np.zeros(self.n)
-        self._chk(self.lib.dav_get_diagonal(self.h, C.c_int(which), _dp(d)))
+        self._chk(self.lib.dav_get_diagonal(self.h, which, _dp(d)))
         return d
 
     # -- hot path
     def init_basis(self, ncols):
         idx = np.zeros(ncols, dtype=np.int64)
-        self._chk(self.lib.dav_init_basis(self.h, C.c_int(ncols), idx.ctypes.data_as(C.POINTER(C.c_int64))))
+        self._chk(self.lib.dav_init_basis(self.h, ncols, idx.ctypes.data_as(C.POINTER(C.c_int64))))
         return idx
 
     # -- warm start
@@ -585,22 +580,22 @@ class CEngine:
             import torch
             t, ld, ncols = dev
             torch.cuda.current_stream(t.device).synchronize()
-            self._chk(self.lib.dav_set_guess_dev(self.h, C.c_void_p(t.data_ptr() or None), C.c_int64(ld), C.c_int(ncols)))
+            self._chk(self.lib.dav_set_guess_dev(self.h, t.data_ptr() or None, ld, ncols))
         else:
-            self._chk(self.lib.dav_set_guess(self.h, _dp(host), C.c_int64(host.shape[0]), C.c_int(host.shape[1])))
+            self._chk(self.lib.dav_set_guess(self.h, _dp(host), host.shape[0], host.shape[1]))
 
     def set_guess_raw(self, x, ldx, ncols):
         """dav_set_guess with an explicit leading dimension: x a one-dimensional float64 array holding x(ldx, ncols) column-major"""
         a = np.ascontiguousarray(x, dtype=np.float64)
-        self._chk(self.lib.dav_set_guess(self.h, _dp(a), C.c_int64(ldx), C.c_int(ncols)))
+        self._chk(self.lib.dav_set_guess(self.h, _dp(a), ldx, ncols))
 
     def set_guess_dev_raw(self, dev_ptr, ldx, ncols):
         """dav_set_guess_dev with a raw device pointer (e.g. a torch tensor's data_ptr() plus an offset) and leading dimension"""
-        self._chk(self.lib.dav_set_guess_dev(self.h, C.c_void_p(dev_ptr), C.c_int64(ldx), C.c_int(ncols)))
+        self._chk(self.lib.dav_set_guess_dev(self.h, dev_ptr, ldx, ncols))
 
     def keep_result_as_guess(self, on=True):
         """dav_keep_result_as_guess: sticky; while on, the Ritz vectors a solve leaves in X are the staged guess of the next solve"""
-        self._chk(self.lib.dav_keep_result_as_guess(self.h, C.c_int(1 if on else 0)))
+        self._chk(self.lib.dav_keep_result_as_guess(self.h, int(on)))
 
     def guess_columns(self):
         """dav_guess_columns: staged guess columns, 0 = none"""
@@ -613,47 +608,42 @@ class CEngine:
         1-based position for a unit column); no images: orthonormalise, then expand(0, ncols) and project(0, ncols)"""
         idx = np.zeros(ncols, dtype=np.int64)
         g = C.c_int(0)
-        self._chk(self.lib.dav_init_basis_guess(self.h, C.c_int(ncols), idx.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(g)))
+        self._chk(self.lib.dav_init_basis_guess(self.h, ncols, idx.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(g)))
         return idx, g.value
 
     def apply(self, which, src_panel, c0, k, dst_panel, d0):
-        self._chk(self.lib.dav_apply(self.h, C.c_int(which), C.c_int(src_panel), C.c_int(c0), C.c_int(k),
-                                     C.c_int(dst_panel), C.c_int(d0)))
+        self._chk(self.lib.dav_apply(self.h, which, src_panel, c0, k, dst_panel, d0))
 
     def apply_inner(self, which, src_panel, c0, k, dst_panel, d0):
         """dav_apply as the GJD correction solve issues it (may read the fp32 copy of the tiles; csrc/davidson_hip_private.h)"""
-        self._chk(self.lib.dav_apply_inner(self.h, C.c_int(which), C.c_int(src_panel), C.c_int(c0), C.c_int(k),
-                                           C.c_int(dst_panel), C.c_int(d0)))
+        self._chk(self.lib.dav_apply_inner(self.h, which, src_panel, c0, k, dst_panel, d0))
 
     def resident_fraction(self, which):
         f = C.c_double()
-        self._chk(self.lib.dav_resident_fraction(self.h, C.c_int(which), C.byref(f)))
+        self._chk(self.lib.dav_resident_fraction(self.h, which, C.byref(f)))
         return f.value
 
     def gram(self, panel_p, p0, p, panel_q, q0, q):
         out = np.zeros((p, q), order="F")
-        self._chk(self.lib.dav_gram(self.h, C.c_int(panel_p), C.c_int(p0), C.c_int(p), C.c_int(panel_q), C.c_int(q0),
-                                    C.c_int(q), _dp(out), C.c_int64(p)))
+        self._chk(self.lib.dav_gram(self.h, panel_p, p0, p, panel_q, q0, q, _dp(out), p))
         return out
 
     def project(self, c0, k, H, S=None):
         ld = H.shape[0]
         sp = _dp(S) if S is not None else C.POINTER(C.c_double)()
-        self._chk(self.lib.dav_project(self.h, C.c_int(c0), C.c_int(k), _dp(H), C.c_int64(ld), sp, C.c_int64(ld)))
+        self._chk(self.lib.dav_project(self.h, c0, k, _dp(H), ld, sp, ld))
 
     def ritz_residual_correction(self, m, lowest, Y, theta, method=METHOD_DPR):
         Y = _f(Y)
         theta = np.ascontiguousarray(theta, dtype=np.float64)
         res = np.zeros(lowest)
-        self._chk(self.lib.dav_ritz_residual_correction(self.h, C.c_int(m), C.c_int(lowest), _dp(Y),
-                                                        C.c_int64(Y.shape[0]), _dp(theta), C.c_int(method), _dp(res)))
+        self._chk(self.lib.dav_ritz_residual_correction(self.h, m, lowest, _dp(Y), Y.shape[0], _dp(theta), method, _dp(res)))
         return res
 
     def gjd_correction(self, m, theta, max_inner=500, inner_tol=1e-12):
         theta = np.ascontiguousarray(theta, dtype=np.float64)
         it = C.c_int(0)
-        self._chk(self.lib.dav_gjd_correction(self.h, C.c_int(m), _dp(theta), C.c_int(max_inner),
-                                              C.c_double(inner_tol), C.byref(it)))
+        self._chk(self.lib.dav_gjd_correction(self.h, m, _dp(theta), max_inner, inner_tol, C.byref(it)))
         return it.value
 
     def gjd_correction_n(self, m, ncols, theta, tol_per_col, max_inner=500, inner_tol=1e-12):
@@ -663,29 +653,25 @@ class CEngine:
         tols = np.ascontiguousarray(tol_per_col, dtype=np.float64)
         assert theta.size >= ncols and tols.size >= ncols
         it = C.c_int(0)
-        self._chk(self.lib.dav_gjd_correction_n(self.h, C.c_int(m), C.c_int(ncols), _dp(theta), C.c_int(max_inner),
-                                                C.c_double(inner_tol), _dp(tols), C.byref(it)))
+        self._chk(self.lib.dav_gjd_correction_n(self.h, m, ncols, _dp(theta), max_inner, inner_tol, _dp(tols), C.byref(it)))
         return it.value
 
     def ortho_gram(self, m, kt):
         Cm = np.zeros((max(m, 1), kt), order="F")
         G = np.zeros((kt, kt), order="F")
-        self._chk(self.lib.dav_ortho_gram(self.h, C.c_int(m), C.c_int(kt), _dp(Cm), C.c_int64(max(m, 1)), _dp(G),
-                                          C.c_int64(kt)))
+        self._chk(self.lib.dav_ortho_gram(self.h, m, kt, _dp(Cm), max(m, 1), _dp(G), kt))
         return Cm[:m], G
 
     def ortho_apply(self, m, kt, Cm, M):
         Cm = _f(Cm) if m > 0 else np.zeros((1, kt), order="F")
         M = _f(M)
-        self._chk(self.lib.dav_ortho_apply(self.h, C.c_int(m), C.c_int(kt), _dp(Cm), C.c_int64(Cm.shape[0]), _dp(M),
-                                           C.c_int64(M.shape[0])))
+        self._chk(self.lib.dav_ortho_apply(self.h, m, kt, _dp(Cm), Cm.shape[0], _dp(M), M.shape[0]))
 
     def ortho_apply_all(self, m, kt, Cm, M):
         """dav_ortho_apply on T and on its images in the W (and BV) panels"""
         Cm = _f(Cm) if m > 0 else np.zeros((1, kt), order="F")
         M = _f(M)
-        self._chk(self.lib.dav_ortho_apply_all(self.h, C.c_int(m), C.c_int(kt), _dp(Cm), C.c_int64(Cm.shape[0]), _dp(M),
-                                               C.c_int64(M.shape[0])))
+        self._chk(self.lib.dav_ortho_apply_all(self.h, m, kt, _dp(Cm), Cm.shape[0], _dp(M), M.shape[0]))
 
     def project_ortho(self, m, k, gev=False):
         """dav_project_ortho: ([V T]^T (A T), [V T]^T (B T) | None, V^T T, T^T T) in one fetch"""
@@ -695,109 +681,102 @@ class CEngine:
         Cm = np.zeros((max(m, 1), k), order="F")
         G = np.zeros((k, k), order="F")
         sp = _dp(S) if gev else C.POINTER(C.c_double)()
-        self._chk(self.lib.dav_project_ortho(self.h, C.c_int(m), C.c_int(k), _dp(H), C.c_int64(p), sp, C.c_int64(p), _dp(Cm),
-                                             C.c_int64(max(m, 1)), _dp(G), C.c_int64(k)))
+        self._chk(self.lib.dav_project_ortho(self.h, m, k, _dp(H), p, sp, p, _dp(Cm), max(m, 1), _dp(G), k))
         return H, S, Cm[:m], G
 
     def expand(self, m, kt):
-        self._chk(self.lib.dav_expand(self.h, C.c_int(m), C.c_int(kt)))
+        self._chk(self.lib.dav_expand(self.h, m, kt))
 
     def restart(self, m, keep, Yk):
         Yk = _f(Yk)
-        self._chk(self.lib.dav_restart(self.h, C.c_int(m), C.c_int(keep), _dp(Yk), C.c_int64(Yk.shape[0])))
+        self._chk(self.lib.dav_restart(self.h, m, keep, _dp(Yk), Yk.shape[0]))
 
     def panel_transform(self, src_panel, s0, p, M, dst_panel, d0):
         M = _f(M)
-        self._chk(self.lib.dav_panel_transform(self.h, C.c_int(src_panel), C.c_int(s0), C.c_int(p), _dp(M),
-                                               C.c_int64(M.shape[0]), C.c_int(M.shape[1]), C.c_int(dst_panel),
-                                               C.c_int(d0)))
+        self._chk(self.lib.dav_panel_transform(self.h, src_panel, s0, p, _dp(M), M.shape[0], M.shape[1], dst_panel, d0))
 
     def panel_get(self, panel, c0, k):
         out = np.zeros((self.n, k), order="F")
-        self._chk(self.lib.dav_panel_get(self.h, C.c_int(panel), C.c_int(c0), C.c_int(k), _dp(out), C.c_int64(self.n)))
+        self._chk(self.lib.dav_panel_get(self.h, panel, c0, k, _dp(out), self.n))
         return out
 
     def panel_put(self, panel, c0, data):
         data = _f(data)
-        self._chk(self.lib.dav_panel_put(self.h, C.c_int(panel), C.c_int(c0), C.c_int(data.shape[1]), _dp(data),
-                                         C.c_int64(data.shape[0])))
+        self._chk(self.lib.dav_panel_put(self.h, panel, c0, data.shape[1], _dp(data), data.shape[0]))
 
     def set_width(self, m):
-        self._chk(self.lib.dav_set_width(self.h, C.c_int(m)))
+        self._chk(self.lib.dav_set_width(self.h, m))
 
     def ranks_agree(self, words):
         w = np.ascontiguousarray(words, dtype=np.float64)
-        self._chk(self.lib.dav_ranks_agree(self.h, _dp(w), C.c_int(w.size)))
+        self._chk(self.lib.dav_ranks_agree(self.h, _dp(w), w.size))
 
     def agree_inputs(self, words):
         """the inputs of a solve, verified across the ranks in a fixed-size collective whenever they differ from the last verified ones"""
         w = np.ascontiguousarray(words, dtype=np.float64)
-        self._chk(self.lib.dav_agree_inputs(self.h, _dp(w), C.c_int(w.size)))
+        self._chk(self.lib.dav_agree_inputs(self.h, _dp(w), w.size))
 
     def agree_next(self, words):
         w = np.ascontiguousarray(words, dtype=np.float64)
-        self._chk(self.lib.dav_agree_next(self.h, _dp(w), C.c_int(w.size)))
+        self._chk(self.lib.dav_agree_next(self.h, _dp(w), w.size))
 
     def set_inner_precision(self, bits):
-        self._chk(self.lib.dav_set_inner_precision(self.h, C.c_int(bits)))
+        self._chk(self.lib.dav_set_inner_precision(self.h, bits))
 
     def rr_enable(self, on=True):
-        self._chk(self.lib.dav_rr_enable(self.h, C.c_int(1 if on else 0)))
+        self._chk(self.lib.dav_rr_enable(self.h, int(on)))
 
     def project_dev(self, c0, k):
-        self._chk(self.lib.dav_project_dev(self.h, C.c_int(c0), C.c_int(k)))
+        self._chk(self.lib.dav_project_dev(self.h, c0, k))
 
     def rr_ritz(self, m, ncorr, lowest, method=METHOD_DPR, want_gram=False):
         """(theta[m], resnorm[lowest], sweeps[, C, G]) from the device-resident projected matrices"""
         theta, res, sweeps = np.zeros(m), np.zeros(lowest), C.c_int(0)
         if want_gram:
             Cm, G = np.zeros((m, ncorr), order="F"), np.zeros((ncorr, ncorr), order="F")
-            self._chk(self.lib.dav_rr_ritz(self.h, C.c_int(m), C.c_int(ncorr), C.c_int(lowest), C.c_int(method), _dp(theta), _dp(res),
-                                           _dp(Cm), C.c_int64(m), _dp(G), C.c_int64(ncorr), C.byref(sweeps)))
+            self._chk(self.lib.dav_rr_ritz(self.h, m, ncorr, lowest, method, _dp(theta), _dp(res), _dp(Cm), m, _dp(G), ncorr,
+                                           C.byref(sweeps)))
             return theta, res, sweeps.value, Cm, G
-        self._chk(self.lib.dav_rr_ritz(self.h, C.c_int(m), C.c_int(ncorr), C.c_int(lowest), C.c_int(method), _dp(theta), _dp(res),
-                                       None, C.c_int64(0), None, C.c_int64(0), C.byref(sweeps)))
+        self._chk(self.lib.dav_rr_ritz(self.h, m, ncorr, lowest, method, _dp(theta), _dp(res), None, 0, None, 0, C.byref(sweeps)))
         return theta, res, sweeps.value
 
     def rr_restart(self, m, keep):
         """collapse restart with the device-resident eigenvectors: V, W (and B V) <- their first `keep` Ritz combinations"""
-        self._chk(self.lib.dav_rr_restart(self.h, C.c_int(m), C.c_int(keep)))
+        self._chk(self.lib.dav_rr_restart(self.h, m, keep))
 
     def rr_get(self, m, ncols):
         theta, Y = np.zeros(m), np.zeros((m, ncols), order="F")
-        self._chk(self.lib.dav_rr_get(self.h, C.c_int(m), C.c_int(ncols), _dp(theta), _dp(Y), C.c_int64(m)))
+        self._chk(self.lib.dav_rr_get(self.h, m, ncols, _dp(theta), _dp(Y), m))
         return theta, Y
 
     def bench_apply(self, k, reps, which=OP_A):
         """(ms per apply END TO END: pack + kernel + reduction, algorithmic bytes per apply)"""
         ms, nbytes = C.c_double(), C.c_double()
-        self._chk(self.lib.dav_bench_apply(self.h, C.c_int(which), C.c_int(k), C.c_int(reps), C.byref(ms),
-                                           C.byref(nbytes)))
+        self._chk(self.lib.dav_bench_apply(self.h, which, k, reps, C.byref(ms), C.byref(nbytes)))
         return ms.value, nbytes.value
 
     def bench_stream(self, doubles=0, reps=5):
         """(copy GB/s, triad GB/s) of plain streaming kernels on this box (read + written bytes)"""
         cp, tr = C.c_double(), C.c_double()
-        self._chk(self.lib.dav_bench_stream(self.h, C.c_int64(doubles), C.c_int(reps), C.byref(cp), C.byref(tr)))
+        self._chk(self.lib.dav_bench_stream(self.h, doubles, reps, C.byref(cp), C.byref(tr)))
         return cp.value, tr.value
 
     def bench_stream3(self, doubles=0, reps=5):
         """(copy, triad, read-only GB/s): bench_stream plus a kernel that only reads (two arrays, one partial sum per workgroup written)"""
         cp, tr, rd = C.c_double(), C.c_double(), C.c_double()
-        self._chk(self.lib.dav_bench_stream3(self.h, C.c_int64(doubles), C.c_int(reps), C.byref(cp), C.byref(tr), C.byref(rd)))
+        self._chk(self.lib.dav_bench_stream3(self.h, doubles, reps, C.byref(cp), C.byref(tr), C.byref(rd)))
         return cp.value, tr.value, rd.value
 
     def bench_harness_rate(self, iters=2000):
         """entries per second of the matrix-free test operator's arithmetic (atan2 + sqrt + log + cos, fp64) on registers"""
         r = C.c_double(0.0)
-        self._chk(self.lib.dav_bench_harness_rate(self.h, C.c_int(iters), C.byref(r)))
+        self._chk(self.lib.dav_bench_harness_rate(self.h, iters, C.byref(r)))
         return r.value
 
     def bench_apply2(self, k, reps, which=OP_A):
         """(ms per apply end to end, ms of the block-matvec kernel alone, algorithmic bytes, flops) per apply"""
         ms, kms, nbytes, flops = C.c_double(), C.c_double(), C.c_double(), C.c_double()
-        self._chk(self.lib.dav_bench_apply2(self.h, C.c_int(which), C.c_int(k), C.c_int(reps), C.byref(ms), C.byref(kms),
-                                            C.byref(nbytes), C.byref(flops)))
+        self._chk(self.lib.dav_bench_apply2(self.h, which, k, reps, C.byref(ms), C.byref(kms), C.byref(nbytes), C.byref(flops)))
         return ms.value, kms.value, nbytes.value, flops.value
 
 
@@ -805,10 +784,10 @@ def parse_text_f64(data: bytes) -> np.ndarray:
     """The engine's parser of the reference's text dumps (host only): all numbers in `data`."""
     lib = hip_lib()
     n = C.c_size_t(0)
-    if lib.dav_parse_text_f64(data, C.c_size_t(len(data)), None, C.c_size_t(0), C.byref(n)) != 0:
+    if lib.dav_parse_text_f64(data, len(data), None, 0, C.byref(n)) != 0:
         raise DavidsonHipError(lib.dav_last_error().decode())
     out = np.empty(n.value)
-    if lib.dav_parse_text_f64(data, C.c_size_t(len(data)), _dp(out), C.c_size_t(out.size), C.byref(n)) != 0:
+    if lib.dav_parse_text_f64(data, len(data), _dp(out), out.size, C.byref(n)) != 0:
         raise DavidsonHipError(lib.dav_last_error().decode())
     return out
 

@@ -16,19 +16,12 @@ import ctypes as C
 import numpy as np
 
 from ._lib import fortran_lib, hip_lib
-from .engine_c import (CEngine, DavidsonHipError, _device_bsr_tensors, _device_csr_tensors, check_bsr, check_csr, device_bsr_tensors,
-                       device_csr_tensors, guess_array, is_torch_bsr, is_torch_csr, torch_bsr_parts, torch_csr_parts, update_values_array)
+from .engine_c import (CEngine, DavidsonHipError, _device_bsr_tensors, _device_csr_tensors, _dp, _f, _optional, check_bsr, check_csr,
+                       device_bsr_tensors, device_csr_tensors, guess_array, is_torch_bsr, is_torch_csr, torch_bsr_parts, torch_csr_parts,
+                       update_values_array)
 
 _METHOD = {"DPR": 0, "GJD": 1}
 _CB = C.CFUNCTYPE(None, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
-
-
-def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _f(a):
-    return np.asfortranarray(a, dtype=np.float64)
 
 
 def _initial_vectors(x, n, lowest):
@@ -63,14 +56,12 @@ def generalized_eigensolver(matrix, lowest, method, max_iterations, tolerance, m
     b = _f(second_matrix) if second_matrix is not None else np.zeros((1, 1), order="F")
     if initial_vectors is not None:
         x0 = _initial_vectors(initial_vectors, n, lowest)
-        lib.fd_dense_solve_guess(C.c_int(n), _dp(a), C.c_int(0 if second_matrix is None else 1), _dp(b), C.c_int(lowest),
-                                 C.c_int(_METHOD.get(method, 2)), C.c_int(max_iterations), C.c_double(tolerance),
-                                 C.c_int(-1 if max_dim_sub is None else max_dim_sub), C.c_int(x0.shape[1]), _dp(x0), _dp(evals),
-                                 _dp(evecs), C.byref(iters))
+        lib.fd_dense_solve_guess(n, _dp(a), int(second_matrix is not None), _dp(b), lowest, _METHOD.get(method, 2), max_iterations,
+                                 tolerance, -1 if max_dim_sub is None else max_dim_sub, x0.shape[1], _dp(x0), _dp(evals), _dp(evecs),
+                                 C.byref(iters))
         return evals, evecs, iters.value
-    lib.fd_dense_solve(C.c_int(n), _dp(a), C.c_int(0 if second_matrix is None else 1), _dp(b), C.c_int(lowest),
-                       C.c_int(_METHOD.get(method, 2)), C.c_int(max_iterations), C.c_double(tolerance),
-                       C.c_int(-1 if max_dim_sub is None else max_dim_sub), _dp(evals), _dp(evecs), C.byref(iters))
+    lib.fd_dense_solve(n, _dp(a), int(second_matrix is not None), _dp(b), lowest, _METHOD.get(method, 2), max_iterations, tolerance,
+                       -1 if max_dim_sub is None else max_dim_sub, _dp(evals), _dp(evecs), C.byref(iters))
     return evals, evecs, iters.value
 
 
@@ -128,15 +119,13 @@ def generalized_eigensolver_sparse(indptr, indices, data, lowest, method, max_it
     iters = C.c_int(-1)
     if initial_vectors is not None:
         x0 = _initial_vectors(initial_vectors, n, lowest)
-        fortran_lib().fd_sparse_solve_guess(C.c_int(n), _i64(rp), _i32(ci), _dp(vv), C.c_int(0 if second is None else 1), _i64(rpb),
-                                            _i32(cib), _dp(vvb), C.c_int(0), C.c_int(1 if lower else 0), C.c_int(lowest),
-                                            C.c_int(_METHOD.get(method, 2)), C.c_int(max_iterations), C.c_double(tolerance),
-                                            C.c_int(-1 if max_dim_sub is None else max_dim_sub), C.c_int(x0.shape[1]), _dp(x0),
-                                            _dp(evals), _dp(evecs), C.byref(iters))
+        fortran_lib().fd_sparse_solve_guess(n, _i64(rp), _i32(ci), _dp(vv), int(second is not None), _i64(rpb), _i32(cib), _dp(vvb), 0,
+                                            int(lower), lowest, _METHOD.get(method, 2), max_iterations, tolerance,
+                                            -1 if max_dim_sub is None else max_dim_sub, x0.shape[1], _dp(x0), _dp(evals), _dp(evecs),
+                                            C.byref(iters))
         return evals, evecs, iters.value
-    fortran_lib().fd_sparse_solve(C.c_int(n), _i64(rp), _i32(ci), _dp(vv), C.c_int(0 if second is None else 1), _i64(rpb), _i32(cib),
-                                  _dp(vvb), C.c_int(0), C.c_int(1 if lower else 0), C.c_int(lowest), C.c_int(_METHOD.get(method, 2)),
-                                  C.c_int(max_iterations), C.c_double(tolerance), C.c_int(-1 if max_dim_sub is None else max_dim_sub),
+    fortran_lib().fd_sparse_solve(n, _i64(rp), _i32(ci), _dp(vv), int(second is not None), _i64(rpb), _i32(cib), _dp(vvb), 0, int(lower),
+                                  lowest, _METHOD.get(method, 2), max_iterations, tolerance, -1 if max_dim_sub is None else max_dim_sub,
                                   _dp(evals), _dp(evecs), C.byref(iters))
     return evals, evecs, iters.value
 
@@ -198,15 +187,13 @@ def generalized_eigensolver_bsr(indptr, indices, data, lowest, method, max_itera
     iters = C.c_int(-1)
     if initial_vectors is not None:
         x0 = _initial_vectors(initial_vectors, n, lowest)
-        fortran_lib().fd_bsr_solve_guess(C.c_int(n), C.c_int(b), _i64(rp), _i32(ci), _dp(vv), C.c_int(0 if second is None else 1),
-                                         _i64(rpb), _i32(cib), _dp(vvb), C.c_int(0), C.c_int(1 if lower else 0), C.c_int(lowest),
-                                         C.c_int(_METHOD.get(method, 2)), C.c_int(max_iterations), C.c_double(tolerance),
-                                         C.c_int(-1 if max_dim_sub is None else max_dim_sub), C.c_int(x0.shape[1]), _dp(x0),
-                                         _dp(evals), _dp(evecs), C.byref(iters))
+        fortran_lib().fd_bsr_solve_guess(n, b, _i64(rp), _i32(ci), _dp(vv), int(second is not None), _i64(rpb), _i32(cib), _dp(vvb), 0,
+                                         int(lower), lowest, _METHOD.get(method, 2), max_iterations, tolerance,
+                                         -1 if max_dim_sub is None else max_dim_sub, x0.shape[1], _dp(x0), _dp(evals), _dp(evecs),
+                                         C.byref(iters))
         return evals, evecs, iters.value
-    fortran_lib().fd_bsr_solve(C.c_int(n), C.c_int(b), _i64(rp), _i32(ci), _dp(vv), C.c_int(0 if second is None else 1), _i64(rpb),
-                               _i32(cib), _dp(vvb), C.c_int(0), C.c_int(1 if lower else 0), C.c_int(lowest), C.c_int(_METHOD.get(method, 2)),
-                               C.c_int(max_iterations), C.c_double(tolerance), C.c_int(-1 if max_dim_sub is None else max_dim_sub),
+    fortran_lib().fd_bsr_solve(n, b, _i64(rp), _i32(ci), _dp(vv), int(second is not None), _i64(rpb), _i32(cib), _dp(vvb), 0, int(lower),
+                               lowest, _METHOD.get(method, 2), max_iterations, tolerance, -1 if max_dim_sub is None else max_dim_sub,
                                _dp(evals), _dp(evecs), C.byref(iters))
     return evals, evecs, iters.value
 
@@ -230,13 +217,11 @@ def generalized_eigensolver_free(fun_matrix_gemv, n, lowest, method, max_iterati
     iters = C.c_int(-1)
     if initial_vectors is not None:
         x0 = _initial_vectors(initial_vectors, n, lowest)
-        lib.fd_free_solve_guess(C.c_int(n), fa, fb, C.c_int(lowest), C.c_int(max_iterations), C.c_double(tolerance),
-                                C.c_int(10 * lowest if max_dim_sub is None else max_dim_sub), C.c_int(x0.shape[1]), _dp(x0), _dp(evals),
-                                _dp(evecs), C.byref(iters))
+        lib.fd_free_solve_guess(n, fa, fb, lowest, max_iterations, tolerance, 10 * lowest if max_dim_sub is None else max_dim_sub,
+                                x0.shape[1], _dp(x0), _dp(evals), _dp(evecs), C.byref(iters))
         return evals, evecs, iters.value
-    lib.fd_free_solve(C.c_int(n), fa, fb, C.c_int(lowest), C.c_int(max_iterations), C.c_double(tolerance),
-                      C.c_int(10 * lowest if max_dim_sub is None else max_dim_sub), _dp(evals), _dp(evecs),
-                      C.byref(iters))
+    lib.fd_free_solve(n, fa, fb, lowest, max_iterations, tolerance, 10 * lowest if max_dim_sub is None else max_dim_sub, _dp(evals),
+                      _dp(evecs), C.byref(iters))
     return evals, evecs, iters.value
 
 
@@ -252,13 +237,11 @@ class DavidsonEngine:
         self.n, self.lowest = n, lowest
         self.max_dim = 10 * lowest if max_dim_sub is None else max_dim_sub
         self.gev = gev
-        self.p = C.c_void_p(self.lib.fd_engine_create(C.c_int(n), C.c_int(lowest), C.c_int(self.max_dim),
-                                                      C.c_int(1 if gev else 0), C.c_int(device), C.c_int(rank),
-                                                      C.c_int(nranks)))
+        self.p = C.c_void_p(self.lib.fd_engine_create(n, lowest, self.max_dim, int(gev), device, rank, nranks))
         self.device = device
         self.c = CEngine(handle=self.lib.fd_engine_handle(self.p), device=device)
         if storage != "full":
-            self.lib.fd_engine_set_storage(self.p, C.c_int({"full": 0, "symmetric": 1}[storage]))
+            self.lib.fd_engine_set_storage(self.p, {"full": 0, "symmetric": 1}[storage])
 
     def close(self):
         if self.p:
@@ -277,13 +260,13 @@ class DavidsonEngine:
     def set_dense(self, which, matrix):
         a = _f(matrix)
         assert a.shape == (self.n, self.n)
-        self.lib.fd_engine_set_dense(self.p, C.c_int(which), _dp(a))
+        self.lib.fd_engine_set_dense(self.p, which, _dp(a))
 
     def _keep_map(self, which, keep_map):
         """the switch of the set call that follows (Fortran: engine_keep_value_map); what update_values knew of the operator goes"""
         self._kept = getattr(self, "_kept", {})
         self._kept.pop(which, None)
-        self.lib.fd_engine_keep_value_map(self.p, C.c_int(which), C.c_int(1 if keep_map else 0))
+        self.lib.fd_engine_keep_value_map(self.p, which, int(keep_map))
 
     def set_sparse(self, which, indptr, indices=None, data=None, lower=False, keep_map=False):
         """Operator A (which=1) or B (which=2) as a symmetric matrix in CSR form, 0-based (Fortran: engine_set_sparse): three arrays,
@@ -296,8 +279,7 @@ class DavidsonEngine:
             return self._set_sparse_device(which, *torch_csr_parts(a), lower=lower, keep_map=keep_map)
         _, rp, ci, vv = _sparse_input(a, self.n, lower)
         self._keep_map(which, keep_map)
-        self.lib.fd_engine_set_sparse(self.p, C.c_int(which), C.c_int(self.n), _i64(rp), _i32(ci), _dp(vv), C.c_int(0),
-                                      C.c_int(1 if lower else 0))
+        self.lib.fd_engine_set_sparse(self.p, which, self.n, _i64(rp), _i32(ci), _dp(vv), 0, int(lower))
         if keep_map:
             self._kept[which] = {"count": int(rp[-1] - rp[0]), "b": 1, "fortran_blocks": False}
 
@@ -306,9 +288,8 @@ class DavidsonEngine:
         self._keep_map(which, keep_map)
         import torch
         torch.cuda.current_stream(row_ptr.device).synchronize()
-        st = self.lib.fd_engine_set_sparse_device(self.p, C.c_int(which), C.c_int(self.n), C.c_void_p(row_ptr.data_ptr()), C.c_int(rpb),
-                                                  C.c_void_p(col_idx.data_ptr() or None), C.c_int(cib),
-                                                  C.c_void_p(vals.data_ptr() or None), C.c_int(0), C.c_int(1 if lower else 0))
+        st = self.lib.fd_engine_set_sparse_device(self.p, which, self.n, row_ptr.data_ptr(), rpb, col_idx.data_ptr() or None, cib,
+                                                  vals.data_ptr() or None, 0, int(lower))
         if st != 0:
             raise DavidsonHipError(hip_lib().dav_last_error().decode())
         if keep_map:
@@ -325,8 +306,7 @@ class DavidsonEngine:
             return self._set_block_sparse_device(which, *torch_bsr_parts(a), lower=lower, keep_map=keep_map)
         b, rp, ci, vv = _bsr_input(a, self.n, lower)
         self._keep_map(which, keep_map)
-        self.lib.fd_engine_set_block_sparse(self.p, C.c_int(which), C.c_int(self.n), C.c_int(b), _i64(rp), _i32(ci), _dp(vv), C.c_int(0),
-                                            C.c_int(1 if lower else 0))
+        self.lib.fd_engine_set_block_sparse(self.p, which, self.n, b, _i64(rp), _i32(ci), _dp(vv), 0, int(lower))
         if keep_map:       # the Fortran door took the blocks in Fortran order: an update transposes them the same way
             self._kept[which] = {"count": int(rp[-1] - rp[0]) * b * b, "b": b, "fortran_blocks": True}
 
@@ -335,10 +315,8 @@ class DavidsonEngine:
         self._keep_map(which, keep_map)
         import torch
         torch.cuda.current_stream(row_ptr.device).synchronize()
-        st = self.lib.fd_engine_set_block_sparse_device(self.p, C.c_int(which), C.c_int(self.n), C.c_int(b), C.c_void_p(row_ptr.data_ptr()),
-                                                        C.c_int(rpb), C.c_void_p(col_idx.data_ptr() or None), C.c_int(cib),
-                                                        C.c_void_p(vals.data_ptr() or None), C.c_int(0), C.c_int(1 if lower else 0),
-                                                        C.c_int(1))
+        st = self.lib.fd_engine_set_block_sparse_device(self.p, which, self.n, b, row_ptr.data_ptr(), rpb, col_idx.data_ptr() or None, cib,
+                                                        vals.data_ptr() or None, 0, int(lower), 1)
         if st != 0:
             raise DavidsonHipError(hip_lib().dav_last_error().decode())
         if keep_map:
@@ -363,28 +341,28 @@ class DavidsonEngine:
             if kept["fortran_blocks"] and b > 1:
                 dev = dev.reshape(-1, b, b).transpose(1, 2).contiguous()
             torch.cuda.current_stream(dev.device).synchronize()
-            st = self.lib.fd_engine_update_values_device(self.p, C.c_int(which), C.c_void_p(dev.data_ptr() or None))
+            st = self.lib.fd_engine_update_values_device(self.p, which, dev.data_ptr() or None)
             if st != 0:
                 raise DavidsonHipError(hip_lib().dav_last_error().decode())
             return
         if kept["fortran_blocks"] and b > 1:
             host = np.ascontiguousarray(host.reshape(-1, b, b).transpose(0, 2, 1)).reshape(-1)
-        self.lib.fd_engine_update_values(self.p, C.c_int(which), _dp(host) if host.size else (C.c_double * 1)(), C.c_int64(host.size))
+        self.lib.fd_engine_update_values(self.p, which, _dp(host) if host.size else (C.c_double * 1)(), host.size)
 
     def set_correction_policy(self, policy):
         """"all" = the reference's policy (default); "unconverged" = opt-in: correct only the wanted pairs
         that have not converged; "locking" = opt-in (standard problems): converged wanted pairs are locked and the
         search space is kept orthogonal to them (Fortran: engine_set_correction_policy)."""
-        self.lib.fd_engine_set_policy(self.p, C.c_int({"all": 0, "unconverged": 1, "locking": 2}[policy]))
+        self.lib.fd_engine_set_policy(self.p, {"all": 0, "unconverged": 1, "locking": 2}[policy])
 
     def set_inner_precision(self, bits):
         """32: the sweeps inside the GJD correction read an fp32 copy of the stored symmetric tiles (Fortran:
         engine_set_inner_precision); 64 (default): the reference's precision throughout."""
-        self.lib.fd_engine_set_inner_precision(self.p, C.c_int(bits))
+        self.lib.fd_engine_set_inner_precision(self.p, bits)
 
     def set_device_rr(self, on=True):
         """Rayleigh-Ritz on the device (Fortran: engine_set_device_rr); default off = host LAPACK as the reference."""
-        self.lib.fd_engine_set_device_rr(self.p, C.c_int(1 if on else 0))
+        self.lib.fd_engine_set_device_rr(self.p, int(on))
 
     def read_matrix(self, which, path, fmt="text"):
         """Operator from a file, streamed to HBM (Fortran: engine_read_matrix): "text" = the reference's
@@ -392,9 +370,7 @@ class DavidsonEngine:
         self.c.set_dense_file(which - 1, path, fmt)
 
     def _set_op(self, which, kind, seed, sparsity, diag_val):
-        self.lib.fd_engine_set_operator(self.p, C.c_int(which), C.c_int(kind), C.c_int(seed), C.c_double(sparsity),
-                                        C.c_int(0 if diag_val is None else 1),
-                                        C.c_double(0.0 if diag_val is None else diag_val))
+        self.lib.fd_engine_set_operator(self.p, which, kind, seed, sparsity, *_optional(diag_val))
 
     def generate_diagonal_dominant(self, which, sparsity, diag_val=None, seed=1):
         """generate_diagonal_dominant(n, sparsity[, diag_val]) built directly in HBM."""
@@ -425,18 +401,17 @@ class DavidsonEngine:
             import torch
             t, ld, ncols = dev
             torch.cuda.current_stream(t.device).synchronize()
-            st = self.lib.fd_engine_set_initial_vectors_device(self.p, C.c_void_p(t.data_ptr() or None), C.c_int(ld),
-                                                               C.c_int(min(ncols, width)))
+            st = self.lib.fd_engine_set_initial_vectors_device(self.p, t.data_ptr() or None, ld, min(ncols, width))
         else:
             host = np.asfortranarray(host[:, :width])
-            st = self.lib.fd_engine_set_initial_vectors(self.p, _dp(host), C.c_int(host.shape[1]))
+            st = self.lib.fd_engine_set_initial_vectors(self.p, _dp(host), host.shape[1])
         if st != 0:
             raise DavidsonHipError(hip_lib().dav_last_error().decode())
 
     def keep_result_as_guess(self, on=True):
         """Sticky (Fortran: engine_keep_result_as_guess): while on, every solve starts from the Ritz vectors the previous solve on this
         engine left in HBM - nothing is copied; update_values and the set calls keep them."""
-        self.lib.fd_engine_keep_result_as_guess(self.p, C.c_int(1 if on else 0))
+        self.lib.fd_engine_keep_result_as_guess(self.p, int(on))
 
     def solve(self, method="DPR", max_iterations=1000, tolerance=1e-8, want_vectors=True, initial_vectors=None, reuse_vectors=None):
         """initial_vectors: see set_initial_vectors (a one-shot guess for this solve).  reuse_vectors: True / False turns
@@ -449,17 +424,15 @@ class DavidsonEngine:
         evals = np.zeros(self.lowest)
         evecs = np.zeros((self.n, self.lowest) if want_vectors else (1, 1), order="F")
         iters = C.c_int(-1)
-        self.lib.fd_engine_solve(self.p, C.c_int(self.lowest), C.c_int(_METHOD.get(method, 2)), C.c_int(max_iterations),
-                                 C.c_double(tolerance), C.c_int(self.max_dim), _dp(evals),
-                                 C.c_int(1 if want_vectors else 0), _dp(evecs), C.byref(iters))
+        self.lib.fd_engine_solve(self.p, self.lowest, _METHOD.get(method, 2), max_iterations, tolerance, self.max_dim, _dp(evals),
+                                 int(want_vectors), _dp(evecs), C.byref(iters))
         return evals, (evecs if want_vectors else None), iters.value
 
 
 # ---- helper modules (array_utils / lapack_wrapper) --------------------------------------------------
 def generate_diagonal_dominant(m, sparsity, diag_val=None, seed=1):
     out = np.zeros((m, m), order="F")
-    fortran_lib().fd_generate_diagonal_dominant(C.c_int(m), C.c_double(sparsity), C.c_int(0 if diag_val is None else 1),
-                                                C.c_double(0.0 if diag_val is None else diag_val), C.c_int(seed), _dp(out))
+    fortran_lib().fd_generate_diagonal_dominant(m, sparsity, *_optional(diag_val), seed, _dp(out))
     return out
 
 
@@ -469,7 +442,7 @@ def lapack_generalized_eigensolver(mtx, stx=None):
     s = _f(stx) if stx is not None else np.zeros((1, 1), order="F")
     w = np.zeros(n)
     v = np.zeros((n, n), order="F")
-    fortran_lib().fd_lapack_eigensolver(C.c_int(n), _dp(mtx), C.c_int(0 if stx is None else 1), _dp(s), _dp(w), _dp(v))
+    fortran_lib().fd_lapack_eigensolver(n, _dp(mtx), int(stx is not None), _dp(s), _dp(w), _dp(v))
     return w, v
 
 
@@ -480,21 +453,20 @@ def lapack_rayleigh_ritz(mtx, nvec, stx=None):
     s = _f(stx) if stx is not None else np.zeros((1, 1), order="F")
     w = np.zeros(n)
     v = np.zeros((n, n), order="F")
-    fortran_lib().fd_lapack_rayleigh_ritz(C.c_int(n), _dp(mtx), C.c_int(0 if stx is None else 1), _dp(s), C.c_int(nvec),
-                                          _dp(w), _dp(v))
+    fortran_lib().fd_lapack_rayleigh_ritz(n, _dp(mtx), int(stx is not None), _dp(s), nvec, _dp(w), _dp(v))
     return w[:nvec], v[:, :nvec]
 
 
 def lapack_qr(basis):
     q = _f(basis).copy(order="F")
-    fortran_lib().fd_lapack_qr(C.c_int(q.shape[0]), C.c_int(q.shape[1]), _dp(q))
+    fortran_lib().fd_lapack_qr(q.shape[0], q.shape[1], _dp(q))
     return q
 
 
 def lapack_solver(arr, brr):
     a = _f(arr).copy(order="F")
     b = np.array(brr, dtype=np.float64).reshape(-1, 1).copy(order="F")
-    fortran_lib().fd_lapack_solver(C.c_int(a.shape[0]), _dp(a), _dp(b))
+    fortran_lib().fd_lapack_solver(a.shape[0], _dp(a), _dp(b))
     return b[:, 0]
 
 
@@ -504,27 +476,26 @@ def lapack_matmul(transA, transB, arr, brr):
     k = a.shape[0] if transA == "T" else a.shape[1]
     n = b.shape[0] if transB == "T" else b.shape[1]
     c = np.zeros((m, n), order="F")
-    fortran_lib().fd_lapack_matmul(C.c_int(transA == "T"), C.c_int(transB == "T"), C.c_int(m), C.c_int(k), C.c_int(n),
-                                   _dp(a), _dp(b), _dp(c))
+    fortran_lib().fd_lapack_matmul(int(transA == "T"), int(transB == "T"), m, k, n, _dp(a), _dp(b), _dp(c))
     return c
 
 
 def lapack_sort(id_, vector):
     v = np.array(vector, dtype=np.float64)
     keys = np.zeros(v.size, dtype=np.int32)
-    fortran_lib().fd_lapack_sort(C.c_int(v.size), C.c_int(id_ == "D"), _dp(v), keys.ctypes.data_as(C.POINTER(C.c_int)))
+    fortran_lib().fd_lapack_sort(v.size, int(id_ == "D"), _dp(v), keys.ctypes.data_as(C.POINTER(C.c_int)))
     return keys, v
 
 
 def generate_preconditioner(diag, dim_sub):
     d = np.array(diag, dtype=np.float64)
     out = np.zeros((d.size, dim_sub), order="F")
-    fortran_lib().fd_generate_preconditioner(C.c_int(d.size), _dp(d), C.c_int(dim_sub), _dp(out))
+    fortran_lib().fd_generate_preconditioner(d.size, _dp(d), dim_sub, _dp(out))
     return out
 
 
 def norm(v):
     v = np.ascontiguousarray(v, dtype=np.float64)
     res = C.c_double()
-    fortran_lib().fd_norm(C.c_int(v.size), _dp(v), C.byref(res))
+    fortran_lib().fd_norm(v.size, _dp(v), C.byref(res))
     return res.value

@@ -118,11 +118,11 @@ def test_host_data_reaches_the_host_entry_column_major_and_wide_guesses_are_cut(
 
     class Lib(_NoCalls):
         def dav_set_guess(self, h, x, ldx, ncols):
-            seen["c"] = (ldx.value, ncols.value, np.ctypeslib.as_array(x, shape=(ncols.value, ldx.value)).T.copy())
+            seen["c"] = (ldx, ncols, np.ctypeslib.as_array(x, shape=(ncols, ldx)).T.copy())
             return 0
 
         def fd_engine_set_initial_vectors(self, p, x, ncols):
-            seen["f"] = (ncols.value, np.ctypeslib.as_array(x, shape=(ncols.value, 6)).T.copy())
+            seen["f"] = (ncols, np.ctypeslib.as_array(x, shape=(ncols, 6)).T.copy())
             return 0
 
     x = np.arange(30.0).reshape(6, 5)                        # C order: the front ends make it column-major

@@ -88,7 +88,7 @@ def test_blocks_are_taken_flat_or_as_nnzb_b_b_and_reach_the_host_entry():
 
     class Lib(_NoCalls):
         def dav_update_operator_values(self, h, which, vals):
-            seen.append(which.value)
+            seen.append(which)
             return 0
 
     e = _engine(4, 8)
@@ -121,7 +121,7 @@ def test_update_values_hands_the_fortran_door_blocks_in_fortran_order():
 
     class Lib(_NoCalls):
         def fd_engine_update_values(self, p, which, vals, count):
-            got["which"], got["vals"] = which.value, np.ctypeslib.as_array(vals, shape=(count.value,)).copy()
+            got["which"], got["vals"] = which, np.ctypeslib.as_array(vals, shape=(count,)).copy()
 
     eng = fd.DavidsonEngine.__new__(fd.DavidsonEngine)
     eng.n, eng.lib, eng.p, eng.device = 4, Lib(), None, 0
