@@ -149,6 +149,10 @@ struct SparseStore {
   int64_t* dpos = nullptr;          // device: positions of the diagonal entries (blocks) in the caller's vals, row by row in input order
   int64_t gcount = 0;               // entries (blocks) of the caller's vals
   int triangle = 0, rowmaj = 0;     // of the set call: DAV_CSR_FULL / DAV_CSR_LOWER; BSR: the caller's blocks are row-major
+  // BSR, built at the first DAV_METHOD_BDPR correction (engine_bdpr.hip): the diagonal blocks of the local block rows, b x b column-major
+  // each, duplicates summed in stored order; new values (dav_update_operator_values) make them stale, a set call releases them
+  double* bdiag = nullptr;
+  bool bdiag_valid = false;
 };
 
 struct OpDesc {
@@ -480,4 +484,7 @@ int ritz_impl(E* e, int m, int ncorr, int lowest, const double* Y, int64_t ldy, 
                      double* info_out);
 int restart_contract(E* e, int m, int keep, const double* Mdev, int64_t ldm);
 void basis_order_ensure(E* e, int ncols);
+// ---- engine_bdpr.hip -------------------------------------------------------------------------------------
+int bdpr_prepare(E* e);
+void bdpr_correct(E* e, int m, int ncorr, const double* theta_dev);
 #pragma GCC visibility pop

@@ -285,8 +285,10 @@ int ritz_impl(E* e, int m, int ncorr, int lowest, const double* Y, int64_t ldy, 
   CHK(bind(e));
   const bool dev = Y == nullptr;
   if (m <= 0 || lowest <= 0 || lowest > ncorr || ncorr > m || (!dev && ldy < m)) return fail("dav_ritz_residual_correction: bad shape");
-  if (method == DAV_METHOD_DPR && m + ncorr > e->cols_alloc) return fail("basis panel too narrow for the correction block");
+  const bool bdpr = method == DAV_METHOD_BDPR;
+  if ((method == DAV_METHOD_DPR || bdpr) && m + ncorr > e->cols_alloc) return fail("basis panel too narrow for the correction block");
   CHK(check_panel(e, DAV_PANEL_V, 0, m));
+  if (bdpr) CHK(bdpr_prepare(e));            // the method's contract, before any panel is written
   const double *dY, *dY2, *dTheta;
   int64_t ldm_y, ldm_y2;
   std::vector<double> y2;
@@ -318,7 +320,7 @@ int ritz_impl(E* e, int m, int ncorr, int lowest, const double* Y, int64_t ldy, 
     a.pin = e->tune.pg_pin;
     launch_panel_gemm(e->stream, a);
   }
-  // R = W*Y + Z*(-Y*diag(theta)), norms, (DPR) T
+  // R = W*Y + Z*(-Y*diag(theta)), norms, (DPR) T; BDPR: R and norms as for GJD, then T from R by the block solves
   PanelGemmArgs r{};
   r.P1 = panel_ptr(e, DAV_PANEL_W, 0); r.ld1 = e->ldp; r.p1 = m; r.M1 = dY; r.tp1 = ldm_y;
   r.P2 = panel_ptr(e, e->gev ? DAV_PANEL_BV : DAV_PANEL_V, 0); r.ld2 = e->ldp; r.p2 = m; r.M2 = dY2; r.tp2 = ldm_y2;
@@ -334,6 +336,7 @@ int ritz_impl(E* e, int m, int ncorr, int lowest, const double* Y, int64_t ldy, 
   }
   r.pin = e->tune.pg_pin;
   launch_panel_gemm(e->stream, r);
+  if (bdpr) bdpr_correct(e, m, ncorr, dTheta);       // T = blocksolve(R) into V[:, m:m+ncorr]
   if (!fuse_norms) launch_norm_finish(e->stream, e->norm_partial, (int)(e->nloc_pad / PG_ROWS), lowest, result_target(e));
   // optionally the Gram block the first orthonormalisation pass needs, [V T]^T T with T = V[:, m:m+ncorr] just
   // written: it rides on the same reduction and the same fetch as the norms (one synchronisation less)

@@ -302,3 +302,14 @@ int guess_flag_words(int ncols);
 bool guess_ingest_wide(const double* src, int64_t ldx, const double* dst, int64_t ldd);
 void launch_guess_ingest(hipStream_t st, const double* src, int64_t ldx, int64_t nrows, int ncols, int64_t npad, double* dst, int64_t ldd,
                          unsigned long long* flags);
+
+// ---- k_bdpr.hip: block-diagonal preconditioned correction of a BSR operator (DAV_METHOD_BDPR) --------------------------------------------
+// out[I b^2 + k b + m] = entry (m, k) of the diagonal block of local block row I < nbl (global block row ib0 + I) of the canonical store
+// rp / col / val: the row's blocks with that block column added in stored order from +0.0; no such block: zeros
+void launch_bdpr_diag_blocks(hipStream_t st, int bs, const int64_t* rp, const int32_t* col, const double* val, int64_t nbl, int64_t ib0, double* out);
+// T[I b .. (I + 1) b, j] = (theta[j] B_II - A_II)^-1 R[I b .. (I + 1) b, j] for I < nbl, j < ncols (nbl * bs = nloc): Gaussian elimination with
+// partial pivoting (largest magnitude, ties to the lowest row), an exactly zero pivot gives +0.0 for that block and column.  dA / dB: the
+// diagonal blocks as launch_bdpr_diag_blocks leaves them, dB == nullptr: B_II = I.  Rows [nloc, nrows_pad) of the ncols columns of T are
+// written as +0.0.  1 <= bs <= 16
+void launch_bdpr_solve(hipStream_t st, int bs, const double* dA, const double* dB, const double* theta, const double* R, int64_t ldr, double* T,
+                       int64_t ldt, int ncols, int64_t nbl, int64_t nloc, int64_t nrows_pad);

@@ -11,6 +11,7 @@ from ._lib import hip_lib
 OP_A, OP_B = 0, 1
 PANEL_V, PANEL_W, PANEL_BV, PANEL_X, PANEL_R, PANEL_S = range(6)
 METHOD_DPR, METHOD_GJD = 0, 1
+METHOD_BDPR = 3          # block-diagonal DPR of a BSR operator (DAV_METHOD_BDPR)
 
 
 # int fn(ctx, hip_stream, n, row0, nloc, k, x_dev, ldx, y_dev, ldy) - include/davidson_hip.h: dav_device_apply_fn

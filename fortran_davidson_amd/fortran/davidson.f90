@@ -186,9 +186,13 @@ contains
           meth = DAV_METHOD_DPR
        case ("GJD")
           meth = DAV_METHOD_GJD
+       case ("BDPR")
+          ! block-diagonal DPR for BSR operators (opt-in, not in the reference): the correction block comes out of the Ritz phase like
+          ! DPR's, so everything below that asks for GJD takes the DPR side; the engine refuses operators the method does not serve
+          meth = DAV_METHOD_BDPR
        case default
           ! the reference leaves the correction undefined here (src/davidson.f90:656-669)
-          print *, "generalized_eigensolver: unknown correction method '", trim(method), "' (DPR or GJD)"
+          print *, "generalized_eigensolver: unknown correction method '", trim(method), "' (DPR, GJD or BDPR)"
           error stop
        end select
     end if
@@ -340,7 +344,7 @@ contains
        if (drr) then
           ! 3 + 4 on the device: eigenpairs of the device-resident projected matrices, then the same fused phase from
           ! where they lie; one synchronisation brings back the Ritz values, the residual norms and the Gram blocks
-          if (phase == DAV_METHOD_DPR) then
+          if (phase == DAV_METHOD_DPR .or. phase == DAV_METHOD_BDPR) then
              if (allocated(c_pre)) deallocate(c_pre, g_pre)
              allocate(c_pre(m, ncorr), g_pre(ncorr, ncorr))
              call check_dav(dav_rr_ritz(h, int(m, c_int), int(ncorr, c_int), int(lowest, c_int), int(phase, c_int), theta, &
@@ -359,6 +363,7 @@ contains
                "dav_ritz_residual_correction")
           have_pre = .true.
        else
+          ! (BDPR too: the entry above has no method argument; the first Gram pass is then made by the orthonormalisation, as for GJD)
           call check_dav(dav_ritz_residual_correction_n(h, int(m, c_int), int(ncorr, c_int), int(lowest, c_int), y, &
                int(m, c_int64_t), theta, int(phase, c_int), errors), "dav_ritz_residual_correction")
        end if

@@ -27,10 +27,11 @@ contains
 
   function method_name(code) result(name)
     integer(c_int), intent(in) :: code
-    character(len=3) :: name
+    character(len=4) :: name
     name = "DPR"
     if (code == 1) name = "GJD"
     if (code > 1) name = "XXX"
+    if (code == 3) name = "BDPR"
   end function method_name
 
   !> generalized_eigensolver(matrix, ...) - dense specific.  max_dim < 0: argument absent.

@@ -8,7 +8,7 @@ module davidson_hip_c
   integer(c_int), parameter :: DAV_OP_A = 0, DAV_OP_B = 1
   integer(c_int), parameter :: DAV_PANEL_V = 0, DAV_PANEL_W = 1, DAV_PANEL_BV = 2, DAV_PANEL_X = 3, &
        DAV_PANEL_R = 4, DAV_PANEL_S = 5
-  integer(c_int), parameter :: DAV_METHOD_DPR = 0, DAV_METHOD_GJD = 1, DAV_METHOD_NONE = 2
+  integer(c_int), parameter :: DAV_METHOD_DPR = 0, DAV_METHOD_GJD = 1, DAV_METHOD_NONE = 2, DAV_METHOD_BDPR = 3
   !> dav_panel_unit_column: "the engine keeps no such entry of the start order" (not an error)
   integer(c_int), parameter :: DAV_NO_SUCH_ENTRY = 2
   !> dav_set_operator_csr: every nonzero given / only j <= i given (the engine mirrors the strict lower part)

@@ -20,7 +20,30 @@ from .engine_c import (CEngine, DavidsonHipError, _device_bsr_tensors, _device_c
                        device_bsr_tensors, device_csr_tensors, guess_array, is_torch_bsr, is_torch_csr, torch_bsr_parts, torch_csr_parts,
                        update_values_array)
 
-_METHOD = {"DPR": 0, "GJD": 1}
+_METHOD = {"DPR": 0, "GJD": 1, "BDPR": 3}
+
+
+def _check_bdpr(method, blocks, gev=False, n=0, nranks=1, where="generalized_eigensolver"):
+    """method "BDPR" (block-diagonal DPR) serves BSR operators only - A of any block size 1..16, B (generalized problems) of the same
+    one, and with several ranks a block size that divides the rows of a rank's slab.  The engine refuses anything else at the first
+    correction and the Fortran doors stop the process on an engine error, so the front ends refuse here (ValueError), before any
+    engine call.  blocks: the block sizes of A and B as the caller set them, None = not a BSR operator."""
+    if method != "BDPR":
+        return
+    ba, bb = blocks
+    if ba is None:
+        raise ValueError(f"{where}: method 'BDPR' needs operator A in BSR form (generalized_eigensolver_bsr, "
+                         "DavidsonEngine.set_block_sparse)")
+    if gev and bb != ba:
+        raise ValueError(f"{where}: method 'BDPR' needs operator B in BSR form with the block size of A ({ba}), not "
+                         + ("another kind of operator" if bb is None else f"block size {bb}"))
+    if nranks > 1:
+        nslab = -(-(-(-n // nranks)) // 16) * 16
+        if nslab % ba != 0:
+            raise ValueError(f"{where}: method 'BDPR' on {nranks} ranks needs a block size that divides the {nslab} rows of a rank's "
+                             f"slab, not {ba}")
+
+
 _CB = C.CFUNCTYPE(None, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
 
 
@@ -43,6 +66,7 @@ def _initial_vectors(x, n, lowest):
 def generalized_eigensolver(matrix, lowest, method, max_iterations, tolerance, max_dim_sub=None,
                             second_matrix=None, initial_vectors=None):
     """initial_vectors (n, g): the solve starts from these columns instead of unit vectors (Fortran: initial_vectors=)."""
+    _check_bdpr(method, (None, None))
     lib = fortran_lib()
     iters = C.c_int(-1)
     evals = np.zeros(lowest)
@@ -99,6 +123,7 @@ def generalized_eigensolver_sparse(indptr, indices, data, lowest, method, max_it
     may also be a torch.sparse_csr_tensor; one on the GPU is built there (DavidsonEngine.set_sparse on the tensor's device).
     lower=True: only the entries with column <= row are given, for A and B.  initial_vectors (n, g): the solve starts from these
     columns instead of unit vectors.  Returns (eigenvalues, eigenvectors, iters)."""
+    _check_bdpr(method, (None, None), where="generalized_eigensolver_sparse")
     a = indptr if indices is None and data is None else (indptr, indices, data)
     if _is_device_csr(a) or _is_device_csr(second):
         # a matrix in device memory: an engine of its own, built on the GPU (DavidsonEngine.set_sparse)
@@ -239,6 +264,7 @@ class DavidsonEngine:
         self.gev = gev
         self.p = C.c_void_p(self.lib.fd_engine_create(n, lowest, self.max_dim, int(gev), device, rank, nranks))
         self.device = device
+        self.nranks = nranks
         self.c = CEngine(handle=self.lib.fd_engine_handle(self.p), device=device)
         if storage != "full":
             self.lib.fd_engine_set_storage(self.p, {"full": 0, "symmetric": 1}[storage])
@@ -260,10 +286,18 @@ class DavidsonEngine:
     def set_dense(self, which, matrix):
         a = _f(matrix)
         assert a.shape == (self.n, self.n)
+        self._note_blocks(which, None)
         self.lib.fd_engine_set_dense(self.p, which, _dp(a))
+
+    def _note_blocks(self, which, b):
+        """the block size of operator `which` while it is a BSR operator, None otherwise: what solve("BDPR") checks before the engine is
+        called"""
+        self._blocks = getattr(self, "_blocks", [None, None])
+        self._blocks[which - 1] = b
 
     def _keep_map(self, which, keep_map):
         """the switch of the set call that follows (Fortran: engine_keep_value_map); what update_values knew of the operator goes"""
+        self._note_blocks(which, None)
         self._kept = getattr(self, "_kept", {})
         self._kept.pop(which, None)
         self.lib.fd_engine_keep_value_map(self.p, which, int(keep_map))
@@ -307,6 +341,7 @@ class DavidsonEngine:
         b, rp, ci, vv = _bsr_input(a, self.n, lower)
         self._keep_map(which, keep_map)
         self.lib.fd_engine_set_block_sparse(self.p, which, self.n, b, _i64(rp), _i32(ci), _dp(vv), 0, int(lower))
+        self._note_blocks(which, b)
         if keep_map:       # the Fortran door took the blocks in Fortran order: an update transposes them the same way
             self._kept[which] = {"count": int(rp[-1] - rp[0]) * b * b, "b": b, "fortran_blocks": True}
 
@@ -319,6 +354,7 @@ class DavidsonEngine:
                                                         vals.data_ptr() or None, 0, int(lower), 1)
         if st != 0:
             raise DavidsonHipError(hip_lib().dav_last_error().decode())
+        self._note_blocks(which, b)
         if keep_map:
             self._kept[which] = {"count": nnzb * b * b, "b": b, "fortran_blocks": False}
 
@@ -367,9 +403,11 @@ class DavidsonEngine:
     def read_matrix(self, which, path, fmt="text"):
         """Operator from a file, streamed to HBM (Fortran: engine_read_matrix): "text" = the reference's
         write_matrix/read_matrix dump format, "f64" = raw row-major float64."""
+        self._note_blocks(which, None)
         self.c.set_dense_file(which - 1, path, fmt)
 
     def _set_op(self, which, kind, seed, sparsity, diag_val):
+        self._note_blocks(which, None)
         self.lib.fd_engine_set_operator(self.p, which, kind, seed, sparsity, *_optional(diag_val))
 
     def generate_diagonal_dominant(self, which, sparsity, diag_val=None, seed=1):
@@ -387,6 +425,7 @@ class DavidsonEngine:
 
     def set_device_operator(self, which, fn, ctx, diag):
         """The caller's own operator as a block apply on device memory (engine_set_device_operator; which = 1 / 2)."""
+        self._note_blocks(which, None)
         self.c.set_operator_device(which - 1, fn, ctx, diag)
 
     def set_initial_vectors(self, x):
@@ -416,7 +455,10 @@ class DavidsonEngine:
     def solve(self, method="DPR", max_iterations=1000, tolerance=1e-8, want_vectors=True, initial_vectors=None, reuse_vectors=None):
         """initial_vectors: see set_initial_vectors (a one-shot guess for this solve).  reuse_vectors: True / False turns
         keep_result_as_guess on / off before the solve (sticky), None leaves it as it is; with it on and no initial_vectors the solve
-        starts from the previous solve's Ritz vectors when they are still in place."""
+        starts from the previous solve's Ritz vectors when they are still in place.  method "BDPR": the block-diagonal form of DPR,
+        for operators set with set_block_sparse (ValueError otherwise, before the engine is called)."""
+        if method == "BDPR":
+            _check_bdpr(method, getattr(self, "_blocks", [None, None]), self.gev, self.n, self.nranks, "DavidsonEngine.solve")
         if reuse_vectors is not None:
             self.keep_result_as_guess(bool(reuse_vectors))
         if initial_vectors is not None:

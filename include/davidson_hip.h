@@ -42,7 +42,18 @@ enum { DAV_PANEL_V = 0,   /* search-space basis V (and, in its tail columns, the
        DAV_PANEL_S = 5 }; /* scratch for out-of-place block transforms                             */
 /* correction method (src/davidson.f90:656-669) */
 enum { DAV_METHOD_DPR = 0, DAV_METHOD_GJD = 1,
-       DAV_METHOD_NONE = 2 /* residues and norms only: the iteration will restart, no correction */ };
+       DAV_METHOD_NONE = 2 /* residues and norms only: the iteration will restart, no correction */,
+       /* Block-diagonal preconditioned correction (opt-in, not in the reference; purely additive within ABI 109): the block-Jacobi form of
+        * DPR for BSR operators.  The Ritz phase writes the residues R and their norms as for GJD and then, for every b x b diagonal block
+        * I and column j, solves (theta_j * B_II - A_II) t_I = r_I (B_II = I for a standard problem) by Gaussian elimination with partial
+        * pivoting into V[:, m:m+ncorr]; an exactly zero pivot gives t_I = 0 for that block and column, as DPR's zero denominator does.
+        * For b = 1 the block is bit for bit DPR's.  CONTRACT, refused (non-zero, dav_last_error names the slot and the reason, V[:, 0:m]
+        * untouched) at the first such correction: operator A is a BSR operator (any 1 <= b <= 16); for a generalized problem operator B
+        * is a BSR operator of the same b; with several ranks b divides the rows of a rank's slab, so that no diagonal block straddles two
+        * ranks and the solves need no communication.  The diagonal blocks (duplicates summed in input order) are gathered once per
+        * operator at the first correction - 8 b bytes per local row - gathered again after dav_update_operator_values(_dev), released
+        * with the operator.  dav_ritz_residual_correction_g has no method argument and stays DPR; dav_rr_ritz takes the method with C / G. */
+       DAV_METHOD_BDPR = 3 };
 
 typedef struct dav_stats {
   int64_t n;               /* global order                                                          */
