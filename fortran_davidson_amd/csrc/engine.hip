@@ -219,6 +219,7 @@ Tune tune_from_env() {
   t.gjd_trace = getenv("DAV_GJD_TRACE") != nullptr;
   t.harness_libm = geti("DAV_HARNESS_LIBM", 0);
   t.no_h0 = geti("DAV_NO_H0", 0);
+  t.cheb_fuse = geti("DAV_CHEB_FUSE", t.cheb_fuse);
   t.coll_select = geti("DAV_COLL_SELECT", 1);
   t.coll_trial_corrupt = geti("DAV_COLL_TRIAL_CORRUPT", 0);
   t.coll_forced = getenv("DAV_SYM_OVERLAP") != nullptr || getenv("DAV_COLL_DIRECT") != nullptr;
@@ -528,6 +529,7 @@ extern "C" int dav_destroy(dav_handle_t e) {
   if (e->arena_host) pool_host_free(e->arena_host);
   lt.lap("arenas");
   pool_free(e->gjd_ws);
+  pool_free(e->cheb_ws);
   ingest_release(e);
   shm_release(e);
   pool_free(e->sym_slab);

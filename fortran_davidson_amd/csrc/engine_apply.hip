@@ -474,18 +474,26 @@ static int apply_device(E* e, int which, OpDesc& o, const double* src, int k, do
 // The rows of this rank (CSR, k_spmm.hip) or the block rows touching its slab (BSR, k_bsrmm.hip): the operand packed - and gathered over
 // the ranks - as for the row slabs, then one launch of the wave-per-item kernel per 64 columns (the matrix is read once per 64 columns)
 // and the chunk sums of the long rows.  Always fp64 (inner sweeps too: there is no fp32 copy of a sparse operator).
-static int apply_sparse(E* e, int which, OpDesc& o, const double* src, int k, double* dst, bool timed) {
+// epi (CSR): the step of the Chebyshev correction in the product's epilogue (k_spmm.hip), its columns those of src / dst.
+static int apply_sparse(E* e, int which, OpDesc& o, const double* src, int k, double* dst, bool timed, const ChebEpi* epi = nullptr) {
   const SparseStore& s = o.sp;
   for (int c = 0; c < k; c += 64) {
     const int kk = std::min(64, k - c), groups = (kk + 15) / 16, gp = groups == 3 ? 4 : groups;
     int slot = -1, kslot = -1;
     double bytes, flops;
     sparse_traffic(e, o, kk, &bytes, &flops);
+    if (epi) bytes += 8.0 * (double)e->nloc * kk * (epi->zprev ? 3 : 2);      // the epilogue reads z, r (and z_{k-1}) at the rows it writes
     if (timed) CHK(timed_begin(e, which == DAV_OP_A ? 0 : 2, bytes, &slot));
     CHK(pack_operand(e, src + (int64_t)c * e->ldp, kk, has_comm(e)));
     double* out = dst + (int64_t)c * e->ldp;
     if (timed && which == DAV_OP_A) CHK(timed_begin(e, 4, flops, &kslot));
-    if (o.kind == DAV_KIND_CSR) {
+    if (o.kind == DAV_KIND_CSR && epi) {
+      ChebEpi ep = *epi;
+      ep.z += (int64_t)c * ep.ld; ep.r += (int64_t)c * ep.ld; ep.pi += c;
+      if (ep.zprev) ep.zprev += (int64_t)c * ep.ld;
+      launch_spmm_csr_cheb(e->stream, s.items, s.nitems, s.rp, s.col, s.val, e->xt, e->xt_group_stride, gp, kk, s.part, out, e->ldp, ep);
+      launch_spmm_csr_finish_cheb(e->stream, s.longs, s.nlong, s.part, kk, out, e->ldp, ep);
+    } else if (o.kind == DAV_KIND_CSR) {
       launch_spmm_csr(e->stream, s.items, s.nitems, s.rp, s.col, s.val, e->xt, e->xt_group_stride, gp, kk, s.part, out, e->ldp);
       launch_spmm_csr_finish(e->stream, s.longs, s.nlong, s.part, kk, out, e->ldp);
     } else {
@@ -556,6 +564,13 @@ int apply_ptr(E* e, int which, const double* src, int k, double* dst, bool timed
   if ((o.kind == DAV_KIND_DENSE || o.kind == DAV_KIND_HASHED || o.kind == DAV_KIND_HARNESS) && o.storage == 1)
     return apply_symmetric(e, which, o, src, k, dst, timed, inner);
   return apply_full_rows(e, which, o, src, k, dst, timed);
+}
+
+int apply_csr_cheb(E* e, const double* src, int k, double* dst, const ChebEpi& epi) {
+  OpDesc& o = e->op[DAV_OP_A];
+  if (o.kind != DAV_KIND_CSR) return fail("apply_csr_cheb: operator A is not a CSR operator");
+  CHK(need_comm(e));
+  return apply_sparse(e, DAV_OP_A, o, src, k, dst, true, &epi);
 }
 
 // W0 = Op * V0 for the unit columns V0 = e_idx of dav_init_basis over SEVERAL ranks of dealt-out symmetric tiles, without a sweep:

@@ -153,6 +153,10 @@ struct SparseStore {
   // each, duplicates summed in stored order; new values (dav_update_operator_values) make them stale, a set call releases them
   double* bdiag = nullptr;
   bool bdiag_valid = false;
+  // CSR / BSR, built at the first DAV_METHOD_CHEB correction (engine_cheb.hip): the largest row sum of |a_ij| of the whole matrix, one slot
+  // per rank (the maximum of the slots is the bound) followed by the partials of the row-sum kernel; stale and released as bdiag is
+  double* rbound = nullptr;
+  bool rbound_valid = false;
 };
 
 struct OpDesc {
@@ -222,6 +226,7 @@ struct Tune {
   bool coll_forced = false;     // DAV_SYM_OVERLAP or DAV_COLL_DIRECT present in the environment
   int no_h0 = 0;          // DAV_NO_H0=1: the first projection by a Gram product instead of the operator's entries at the start indices (A/B)
   int harness_libm = 0;   // DAV_HARNESS_LIBM=1: the harness operator's entries by four library calls each (A/B; default: the one-variable polynomial)
+  int cheb_fuse = 1;      // DAV_CHEB_FUSE=0: the step of the Chebyshev correction as a launch of its own behind the CSR product instead of inside it (A/B, equality test)
 };
 Tune tune_from_env();
 
@@ -267,6 +272,7 @@ struct dav_engine {
   double* norm_partial = nullptr;
   unsigned* counters = nullptr;   // zeroed words of the last-workgroup finishes: [0, GRAM_MAX_COUNTERS) Gram tiles, [GRAM_MAX_COUNTERS] the panel norms
   double* gjd_ws = nullptr;       // GJD inner-solver workspace (lazy)
+  double* cheb_ws = nullptr;      // Chebyshev correction (engine_cheb.hip, lazy): three column blocks of the GJD workspace's width, then the coefficients
   int storage = 0;                // storage mode for dense operators set after dav_set_storage
   int sym_nb = 0;                 // symmetric-tiled sweep: block rows of the whole matrix
   SymSet sym;                     // work lists over the block rows this rank stores (or generates)
@@ -378,6 +384,9 @@ struct Watchdog {
   int device = 0, rank = 0, nranks = 1;
 };
 
+// the method of a method code: the Chebyshev correction keeps its degree above the low byte (bits 8..15, 0 = the default), every other
+// code is its own method.  Every comparison of a method code goes through this.
+static inline int method_kind(int code) { return code > 0 && (code & 0xff) == DAV_METHOD_CHEB ? DAV_METHOD_CHEB : code; }
 static inline int64_t roundup(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // several small matrices in ONE staging buffer and ONE host-to-device copy (each H2D command costs
@@ -471,6 +480,7 @@ bool inner_f32_tiles(E* e, OpDesc& o);
 int apply_sym_set(E* e, int which, OpDesc& o, const SymSet& set, bool partial, bool accumulate, const double* src, int k, double* dst, bool timed,
                   bool inner);
 int apply_ptr(E* e, int which, const double* src, int k, double* dst, bool timed, bool inner = false);
+int apply_csr_cheb(E* e, const double* src, int k, double* dst, const ChebEpi& epi);   // operator A (CSR): the product with the step in its epilogue
 int apply_impl(E* e, int which, int src_panel, int c0, int k, int dst_panel, int d0, bool timed, bool inner = false);
 int gather_columns_sym_multi(E* e, OpDesc& o, int ncols, double* dst, double* h0 = nullptr);
 // ---- engine_solver.hip -----------------------------------------------------------------------------------
@@ -487,4 +497,7 @@ void basis_order_ensure(E* e, int ncols);
 // ---- engine_bdpr.hip -------------------------------------------------------------------------------------
 int bdpr_prepare(E* e);
 void bdpr_correct(E* e, int m, int ncorr, const double* theta_dev);
+// ---- engine_cheb.hip -------------------------------------------------------------------------------------
+int cheb_prepare(E* e, int degree);
+int cheb_correct(E* e, int m, int ncorr, int lowest, int degree, const double* theta_dev);
 #pragma GCC visibility pop

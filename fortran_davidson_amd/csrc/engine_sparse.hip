@@ -10,12 +10,13 @@
 
 void sparse_release(E* e, OpDesc& o) {
   SparseStore& s = o.sp;
-  if (!s.rp && !s.col && !s.val && !s.items && !s.longs && !s.part && !s.src && !s.doff && !s.dpos && !s.bdiag) return;
+  if (!s.rp && !s.col && !s.val && !s.items && !s.longs && !s.part && !s.src && !s.doff && !s.dpos && !s.bdiag && !s.rbound) return;
   (void)hipStreamSynchronize(e->stream);         // applies in flight may still read the arrays
   pool_free(s.rp); pool_free(s.col); pool_free(s.val);
   pool_free(s.items); pool_free(s.longs); pool_free(s.part);
   pool_free(s.src); pool_free(s.doff); pool_free(s.dpos);
   pool_free(s.bdiag);
+  pool_free(s.rbound);
   s = SparseStore();
 }
 
@@ -674,6 +675,7 @@ int update_from_device(E* e, int which, const char* name, BuildScratch& sc, cons
   if (o.kind == DAV_KIND_CSR) launch_sparse_refresh_csr(st, s.src, s.nnz, vals, s.val);
   else launch_bsr_build_gather(st, s.b, s.src, s.nnz, vals, s.rowmaj, s.val);
   o.sp.bdiag_valid = false;          // the diagonal blocks of a BDPR correction follow the values: rebuilt at the next one
+  o.sp.rbound_valid = false;         // ... and the row-sum bound of a CHEB correction
   launch_sparse_refresh_diag(st, s.b, s.doff, s.dpos, vals, e->n, diag);
   if (e->nloc > 0) HIPCHK(hipMemcpyAsync(o.diag, diag + e->row0, sizeof(double) * e->nloc, hipMemcpyDeviceToDevice, st));
   // what depends on the numbers: the diagonal on the host and the start-vector order of A

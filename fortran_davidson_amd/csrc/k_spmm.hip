@@ -11,17 +11,30 @@
 // Results of whole rows are staged in LDS ([row][column], one region of 16 GP columns per wave: 2 / 4 / 8 KiB) and stored column by
 // column: 16 consecutive rows of a panel column (128 bytes) per quarter-wave.  Partial rows of chunks go to part[slot][0:64] (one
 // 512-byte row per chunk).
+//
+// EPI = ChebEpi (launch_spmm_csr_cheb / launch_spmm_csr_finish_cheb): the two places that store a finished row value - the
+// column-by-column store from LDS and the finishing pass of the long rows - store cheb_combine (kernels.h) of it instead, the step of the
+// Chebyshev correction, so that the product is never written and read back.  The epilogue is a trailing argument pack: empty for the plain
+// product, whose kernels keep their signature, their instructions and their order of summation.
 #include "kernels.h"
 
 namespace {
 constexpr int SPMM_UNROLL = 8;          // steps of a stream whose loads are issued before their FMAs
 }
 
-template <int GP>
+namespace {
+__device__ __forceinline__ double spmm_epilogue(double y, int64_t row, int col, const ChebEpi& epi) {
+  const int64_t at = (int64_t)col * epi.ld + row;
+  return cheb_combine(y, epi.z[at], epi.r[at], epi.zprev ? epi.zprev[at] : 0.0, epi.zprev != nullptr, epi.hdr[CHEB_C], epi.pi[col], epi.ab[0],
+                      epi.ab[1], epi.hdr[CHEB_VALID] != 0.0);
+}
+}  // namespace
+
+template <int GP, class... EPI>
 __global__ __launch_bounds__(256) void spmm_csr_kernel(const CsrItem* __restrict__ items, int nitems, const int64_t* __restrict__ rp,
                                                        const int32_t* __restrict__ col, const double* __restrict__ val,
                                                        const double* __restrict__ xt, int64_t gstride, int kk, double* __restrict__ part,
-                                                       double* __restrict__ dst, int64_t ldd) {
+                                                       double* __restrict__ dst, int64_t ldd, EPI... epi) {
   constexpr int S = 4 / GP;
   constexpr int LD = 16 * GP + 1;       // staging row of the launch's columns, padded: a column read by 16 rows hits 16 different banks
   __shared__ double stage[4][CSR_ROWS][LD];
@@ -68,14 +81,20 @@ __global__ __launch_bounds__(256) void spmm_csr_kernel(const CsrItem* __restrict
   if (slot >= 0) return;
   // column-major store of the staged rows: lane = (column offset cc, row rr), 16 consecutive rows of 4 columns per instruction
   const int rr = lane & 15, cc = lane >> 4;
-  if (rr < nrows)
-    for (int cl = cc; cl < kk; cl += 4) dst[(int64_t)cl * ldd + row + rr] = stage[wave][rr][cl];
+  if (rr < nrows) {
+    if constexpr (sizeof...(EPI) > 0) {
+      for (int cl = cc; cl < kk; cl += 4) dst[(int64_t)cl * ldd + row + rr] = spmm_epilogue(stage[wave][rr][cl], row + rr, cl, epi...);
+    } else {
+      for (int cl = cc; cl < kk; cl += 4) dst[(int64_t)cl * ldd + row + rr] = stage[wave][rr][cl];
+    }
+  }
 }
 
 // one wave per long row: lane = column, the row's chunk partials added in chunk order (loads issued SPMM_UNROLL chunks ahead of the
 // adds: the arrowhead row of N = 10^6 has 977 chunks, and one dependent load per chunk made this wave the tail of the apply)
+template <class... EPI>
 __global__ __launch_bounds__(64) void spmm_csr_finish_kernel(const CsrLong* __restrict__ longs, const double* __restrict__ part, int kk,
-                                                             double* __restrict__ dst, int64_t ldd) {
+                                                             double* __restrict__ dst, int64_t ldd, EPI... epi) {
   const CsrLong L = longs[blockIdx.x];
   const int lane = threadIdx.x;
   const double* __restrict__ pp = part + (int64_t)L.first * 64 + lane;
@@ -89,22 +108,44 @@ __global__ __launch_bounds__(64) void spmm_csr_finish_kernel(const CsrLong* __re
     for (int u = 0; u < SPMM_UNROLL; ++u) sum += v[u];
   }
   for (; q < L.count; ++q) sum += pp[(int64_t)q * 64];
-  if (lane < kk) dst[(int64_t)lane * ldd + L.row] = sum;
+  if (lane < kk) {
+    if constexpr (sizeof...(EPI) > 0) sum = spmm_epilogue(sum, L.row, lane, epi...);
+    dst[(int64_t)lane * ldd + L.row] = sum;
+  }
 }
 
-void launch_spmm_csr(hipStream_t st, const CsrItem* items, int nitems, const int64_t* rp, const int32_t* col, const double* val,
-                     const double* xt, int64_t xt_gstride, int groups, int kk, double* part, double* dst, int64_t ldd) {
+namespace {
+template <class... EPI>
+void spmm_csr_launch(hipStream_t st, const CsrItem* items, int nitems, const int64_t* rp, const int32_t* col, const double* val, const double* xt,
+                     int64_t xt_gstride, int groups, int kk, double* part, double* dst, int64_t ldd, EPI... epi) {
   if (nitems <= 0 || kk <= 0) return;
   const dim3 grid((unsigned)((nitems + 3) / 4)), block(256);
   if (groups == 1)
-    hipLaunchKernelGGL(spmm_csr_kernel<1>, grid, block, 0, st, items, nitems, rp, col, val, xt, xt_gstride, kk, part, dst, ldd);
+    hipLaunchKernelGGL((spmm_csr_kernel<1, EPI...>), grid, block, 0, st, items, nitems, rp, col, val, xt, xt_gstride, kk, part, dst, ldd, epi...);
   else if (groups == 2)
-    hipLaunchKernelGGL(spmm_csr_kernel<2>, grid, block, 0, st, items, nitems, rp, col, val, xt, xt_gstride, kk, part, dst, ldd);
+    hipLaunchKernelGGL((spmm_csr_kernel<2, EPI...>), grid, block, 0, st, items, nitems, rp, col, val, xt, xt_gstride, kk, part, dst, ldd, epi...);
   else
-    hipLaunchKernelGGL(spmm_csr_kernel<4>, grid, block, 0, st, items, nitems, rp, col, val, xt, xt_gstride, kk, part, dst, ldd);
+    hipLaunchKernelGGL((spmm_csr_kernel<4, EPI...>), grid, block, 0, st, items, nitems, rp, col, val, xt, xt_gstride, kk, part, dst, ldd, epi...);
+}
+}  // namespace
+
+void launch_spmm_csr(hipStream_t st, const CsrItem* items, int nitems, const int64_t* rp, const int32_t* col, const double* val,
+                     const double* xt, int64_t xt_gstride, int groups, int kk, double* part, double* dst, int64_t ldd) {
+  spmm_csr_launch(st, items, nitems, rp, col, val, xt, xt_gstride, groups, kk, part, dst, ldd);
+}
+
+void launch_spmm_csr_cheb(hipStream_t st, const CsrItem* items, int nitems, const int64_t* rp, const int32_t* col, const double* val,
+                          const double* xt, int64_t xt_gstride, int groups, int kk, double* part, double* dst, int64_t ldd, const ChebEpi& epi) {
+  spmm_csr_launch<ChebEpi>(st, items, nitems, rp, col, val, xt, xt_gstride, groups, kk, part, dst, ldd, epi);
 }
 
 void launch_spmm_csr_finish(hipStream_t st, const CsrLong* longs, int nlong, const double* part, int kk, double* dst, int64_t ldd) {
   if (nlong <= 0 || kk <= 0) return;
-  hipLaunchKernelGGL(spmm_csr_finish_kernel, dim3((unsigned)nlong), dim3(64), 0, st, longs, part, kk, dst, ldd);
+  hipLaunchKernelGGL(spmm_csr_finish_kernel<>, dim3((unsigned)nlong), dim3(64), 0, st, longs, part, kk, dst, ldd);
+}
+
+void launch_spmm_csr_finish_cheb(hipStream_t st, const CsrLong* longs, int nlong, const double* part, int kk, double* dst, int64_t ldd,
+                                 const ChebEpi& epi) {
+  if (nlong <= 0 || kk <= 0) return;
+  hipLaunchKernelGGL(spmm_csr_finish_kernel<ChebEpi>, dim3((unsigned)nlong), dim3(64), 0, st, longs, part, kk, dst, ldd, epi);
 }

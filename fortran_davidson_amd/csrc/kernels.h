@@ -189,6 +189,15 @@ struct CsrLong { int32_t row, first, count, pad; };   // a row longer than CSR_C
 void launch_spmm_csr(hipStream_t st, const CsrItem* items, int nitems, const int64_t* rp, const int32_t* col, const double* val,
                      const double* xt, int64_t xt_gstride, int groups, int kk, double* part, double* dst, int64_t ldd);
 void launch_spmm_csr_finish(hipStream_t st, const CsrLong* longs, int nlong, const double* part, int kk, double* dst, int64_t ldd);
+// The step of the Chebyshev correction (k_cheb.hip) applied to every finished row value of the product INSTEAD of storing it: with
+// y = (A z)[i, j] the element written is cheb_combine(y, z[i, j], r[i, j], zprev[i, j], ...) - the product is never stored and read back.
+// z / r / zprev: panel columns of leading dimension ld, column 0 = column 0 of the launch (zprev == nullptr: z_0 = 0, not read);
+// hdr / ab / pi: the coefficients cheb_coef left on the device (CHEB_* below), pi[j] of the launch's column j.  Must not alias dst.
+struct ChebEpi { const double *z, *r, *zprev, *hdr, *ab, *pi; int64_t ld; };
+void launch_spmm_csr_cheb(hipStream_t st, const CsrItem* items, int nitems, const int64_t* rp, const int32_t* col, const double* val,
+                          const double* xt, int64_t xt_gstride, int groups, int kk, double* part, double* dst, int64_t ldd, const ChebEpi& epi);
+void launch_spmm_csr_finish_cheb(hipStream_t st, const CsrLong* longs, int nlong, const double* part, int kk, double* dst, int64_t ldd,
+                                 const ChebEpi& epi);
 
 // ---- K1c': device build of a CSR operator (k_csr_build.hip; dav_set_operator_csr_dev) -----------------------------------------------
 // The caller's global arrays: row_ptr and col_idx of 32 (rp64 / ci64 = 0) or 64 bits, numbered from `base`.  info[4] (set to ~0 first):
@@ -313,3 +322,35 @@ void launch_bdpr_diag_blocks(hipStream_t st, int bs, const int64_t* rp, const in
 // written as +0.0.  1 <= bs <= 16
 void launch_bdpr_solve(hipStream_t st, int bs, const double* dA, const double* dB, const double* theta, const double* R, int64_t ldr, double* T,
                        int64_t ldt, int ncols, int64_t nbl, int64_t nloc, int64_t nrows_pad);
+
+// ---- k_cheb.hip: Chebyshev-filtered correction of a sparse operator (DAV_METHOD_CHEB; engine_cheb.hip) ---------------------------------
+constexpr int CHEB_MAX_DEGREE = 64;
+constexpr int CHEB_DEFAULT_DEGREE = 10;
+constexpr int CHEB_BOUND_PARTIALS = 1024;      // workgroups of the row-sum kernel at the most: one partial maximum each
+// Coefficients of one correction, on the device: coef[CHEB_VALID] = 1.0 when the interval is usable (0.0: the block is +0.0),
+// coef[CHEB_C] = c, coef[CHEB_AB + 2 k] / [.. + 1] = alpha_k / beta_k of the step that makes z_{k+1} from z_k (k = 0: alpha_0 = s_1 / e of
+// z_1 = alpha_0 r, beta_0 = 0), then pi_k of column j at coef[CHEB_PI + k * pstride + j].
+constexpr int CHEB_VALID = 0, CHEB_C = 1, CHEB_AB = 2, CHEB_PI = CHEB_AB + 2 * CHEB_MAX_DEGREE + 6;   // 136: the rows of pi start 16-byte aligned
+inline size_t cheb_coef_doubles(int ncols) { return (size_t)CHEB_PI + (size_t)CHEB_MAX_DEGREE * (size_t)((ncols + 63) / 64 * 64); }
+// The one statement of a step's arithmetic, shared by cheb_step and the epilogue of the CSR product (their bits must agree):
+//   t = fma(-c, z, y);  t = fma(pi, r, t);  u = alpha * t;  result = fma(-beta, zprev, u)   (no zprev: u);  not valid: +0.0
+__device__ __forceinline__ double cheb_combine(double y, double z, double r, double zprev, bool has_prev, double c, double pi, double alpha,
+                                               double beta, bool valid) {
+#pragma clang fp contract(off)
+  double t = __builtin_fma(-c, z, y);
+  t = __builtin_fma(pi, r, t);
+  const double u = alpha * t;
+  const double o = has_prev ? __builtin_fma(-beta, zprev, u) : u;
+  return valid ? o : 0.0;
+}
+// slots[rank] = max over the stored rows of sum_j |a_ij| (rows of the nbl local block rows of block size bs, bs = 1: CSR rows; a row's
+// entries added in stored order from +0.0; NaN propagates), slots[p] = +0.0 for the other p < nranks; partial: CHEB_BOUND_PARTIALS doubles
+void launch_cheb_row_bound(hipStream_t st, int bs, const int64_t* rp, const double* val, int64_t nbl, double* partial, double* slots, int rank,
+                           int nranks);
+// the interval and the coefficients of a correction of `degree` from theta[0 .. ncorr) and max(slots[0 .. nranks)): one lane per column
+void launch_cheb_coef(hipStream_t st, const double* theta, int ncorr, int lowest, int degree, const double* slots, int nranks, double* coef,
+                      int pstride);
+// out[:, j] = cheb_combine(az[:, j], z[:, j], r[:, j], zprev[:, j]) with step k's coefficients for j < ncols, rows [0, nloc); rows [nloc,
+// nrows_pad) are written as +0.0.  k = 0: out = alpha_0 r (az, z, zprev not read).  zprev == nullptr: not read.  out may be zprev.
+void launch_cheb_step(hipStream_t st, int k, const double* coef, int pstride, const double* az, const double* z, const double* r, const double* zprev,
+                      double* out, int64_t ld, int ncols, int64_t nloc, int64_t nrows_pad);

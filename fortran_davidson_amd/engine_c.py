@@ -12,6 +12,13 @@ OP_A, OP_B = 0, 1
 PANEL_V, PANEL_W, PANEL_BV, PANEL_X, PANEL_R, PANEL_S = range(6)
 METHOD_DPR, METHOD_GJD = 0, 1
 METHOD_BDPR = 3          # block-diagonal DPR of a BSR operator (DAV_METHOD_BDPR)
+METHOD_CHEB = 4          # Chebyshev-filtered correction of a CSR / BSR operator (DAV_METHOD_CHEB), default degree
+
+
+def method_cheb(degree=0):
+    """the method code of the Chebyshev correction of `degree` (the header's DAV_METHOD_CHEB_DEGREE): the degree rides in bits 8..15,
+    0 = the engine's default of 10.  The engine itself refuses a degree outside 1..64."""
+    return METHOD_CHEB | (int(degree) << 8)
 
 
 # int fn(ctx, hip_stream, n, row0, nloc, k, x_dev, ldx, y_dev, ldy) - include/davidson_hip.h: dav_device_apply_fn

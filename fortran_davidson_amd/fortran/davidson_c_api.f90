@@ -32,7 +32,17 @@ contains
     if (code == 1) name = "GJD"
     if (code > 1) name = "XXX"
     if (code == 3) name = "BDPR"
+    if (code > 3 .and. iand(code, 255) == 4) name = "CHEB"      ! the Chebyshev correction: its degree rides above the low byte
   end function method_name
+
+  !> what the doors hand to generalized_eigensolver: method_name, and behind "CHEB" the degree of bits 8.. of the code ("CHEB16"; none =
+  !> the default degree).  A degree the driver does not take (outside 1..64) makes a name it does not know.
+  function method_label(code) result(label)
+    integer(c_int), intent(in) :: code
+    character(len=12) :: label
+    label = method_name(code)
+    if (label == "CHEB" .and. ishft(code, -8) /= 0) write (label(5:12), "(i0)") ishft(code, -8)
+  end function method_label
 
   !> generalized_eigensolver(matrix, ...) - dense specific.  max_dim < 0: argument absent.
   subroutine fd_dense_solve(n, a, has_b, b, lowest, method, max_it, tol, max_dim, evals, evecs, iters) &
@@ -45,16 +55,16 @@ contains
     integer :: it
     if (has_b /= 0) then
        if (max_dim >= 0) then
-          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, max_dim, b(:, 1:n))
+          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, max_dim, b(:, 1:n))
        else
-          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, &
+          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, &
                second_matrix=b(:, 1:n))
        end if
     else
        if (max_dim >= 0) then
-          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, max_dim)
+          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, max_dim)
        else
-          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it)
+          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it)
        end if
     end if
     iters = it
@@ -92,15 +102,15 @@ contains
     if (has_b /= 0) then
        b = csr_from_c(n, rpb, colb, valsb, base, lower)
        if (max_dim >= 0) then
-          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, max_dim, b)
+          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, max_dim, b)
        else
-          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, second_matrix=b)
+          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, second_matrix=b)
        end if
     else
        if (max_dim >= 0) then
-          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, max_dim)
+          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, max_dim)
        else
-          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it)
+          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it)
        end if
     end if
     iters = it
@@ -141,15 +151,15 @@ contains
     if (has_b /= 0) then
        bm = bsr_from_c(n, b, rpb, colb, valsb, base, lower)
        if (max_dim >= 0) then
-          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, max_dim, bm)
+          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, max_dim, bm)
        else
-          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, second_matrix=bm)
+          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, second_matrix=bm)
        end if
     else
        if (max_dim >= 0) then
-          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, max_dim)
+          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, max_dim)
        else
-          call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it)
+          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it)
        end if
     end if
     iters = it
@@ -422,9 +432,9 @@ contains
     md = max_dim
     if (md < 0) md = 10 * lowest
     if (has_b /= 0) then
-       call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, md, b(:, 1:n), initial_vectors=x0)
+       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, b(:, 1:n), initial_vectors=x0)
     else
-       call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, md, initial_vectors=x0)
+       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, initial_vectors=x0)
     end if
     iters = it
   end subroutine fd_dense_solve_guess
@@ -445,9 +455,9 @@ contains
     a = csr_from_c(n, rp, col, vals, base, lower)
     if (has_b /= 0) then
        b = csr_from_c(n, rpb, colb, valsb, base, lower)
-       call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, md, b, initial_vectors=x0)
+       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, b, initial_vectors=x0)
     else
-       call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, md, initial_vectors=x0)
+       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, initial_vectors=x0)
     end if
     iters = it
   end subroutine fd_sparse_solve_guess
@@ -468,9 +478,9 @@ contains
     a = bsr_from_c(n, b, rp, col, vals, base, lower)
     if (has_b /= 0) then
        bm = bsr_from_c(n, b, rpb, colb, valsb, base, lower)
-       call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, md, bm, initial_vectors=x0)
+       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, bm, initial_vectors=x0)
     else
-       call generalized_eigensolver(a, evals, evecs, lowest, method_name(method), max_it, tol, it, md, initial_vectors=x0)
+       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, initial_vectors=x0)
     end if
     iters = it
   end subroutine fd_bsr_solve_guess
@@ -534,9 +544,9 @@ contains
     if (md < 0) md = 10 * lowest
     if (want_vectors /= 0) then
        call c_f_pointer(c_loc(evecs), vec, [eng%n, int(lowest)])
-       call generalized_eigensolver(eng, evals, vec, lowest, method_name(method), max_it, tol, it, md)
+       call generalized_eigensolver(eng, evals, vec, lowest, method_label(method), max_it, tol, it, md)
     else
-       call generalized_eigensolver(eng, eigenvalues=evals, lowest=lowest, method=method_name(method), &
+       call generalized_eigensolver(eng, eigenvalues=evals, lowest=lowest, method=method_label(method), &
             max_iterations=max_it, tolerance=tol, iters=it, max_dim_sub=md)
     end if
     iters = it

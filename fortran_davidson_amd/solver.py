@@ -44,6 +44,40 @@ def _check_bdpr(method, blocks, gev=False, n=0, nranks=1, where="generalized_eig
                              f"slab, not {ba}")
 
 
+def _cheb_degree(method):
+    """the degree of method "CHEB" / "CHEB<d>" (0 = the default), None when `method` is not such a string.  ValueError: a degree outside
+    1..64 - the Fortran doors stop the process on a name they do not know."""
+    if not isinstance(method, str) or not method.startswith("CHEB"):
+        return None
+    tail = method[4:]
+    if tail == "":
+        return 0
+    if not (tail.isascii() and tail.isdigit()) or not 1 <= int(tail) <= 64:
+        raise ValueError(f"method {method!r}: the degree of the Chebyshev correction is 'CHEB' (default) or 'CHEB<d>' with 1 <= d <= 64")
+    return int(tail)
+
+
+def _method_code(method):
+    """the integer the doors take: _METHOD's, or 4 | degree << 8 for "CHEB" / "CHEB<d>" (engine_c.method_cheb); unknown names: 2"""
+    d = _cheb_degree(method)
+    return _METHOD.get(method, 2) if d is None else 4 | (d << 8)
+
+
+def _check_cheb(method, sparse_a, gev=False, where="generalized_eigensolver"):
+    """method "CHEB" / "CHEB<d>" (Chebyshev-filtered correction) serves standard problems whose operator A is a CSR or BSR operator: its
+    spectral bound comes from the stored entries.  The engine refuses anything else at the first correction and the Fortran doors stop
+    the process on an engine error, so the front ends refuse here (ValueError), before any engine call.  sparse_a: A was set in CSR or
+    BSR form."""
+    if _cheb_degree(method) is None:
+        return
+    if not sparse_a:
+        raise ValueError(f"{where}: method {method!r} needs operator A in CSR or BSR form (generalized_eigensolver_sparse, "
+                         "generalized_eigensolver_bsr, DavidsonEngine.set_sparse / set_block_sparse)")
+    if gev:
+        raise ValueError(f"{where}: method {method!r} serves standard problems only (the filter of a generalized problem would need "
+                         "the inverse of B)")
+
+
 _CB = C.CFUNCTYPE(None, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
 
 
@@ -67,6 +101,7 @@ def generalized_eigensolver(matrix, lowest, method, max_iterations, tolerance, m
                             second_matrix=None, initial_vectors=None):
     """initial_vectors (n, g): the solve starts from these columns instead of unit vectors (Fortran: initial_vectors=)."""
     _check_bdpr(method, (None, None))
+    _check_cheb(method, False)
     lib = fortran_lib()
     iters = C.c_int(-1)
     evals = np.zeros(lowest)
@@ -80,11 +115,11 @@ def generalized_eigensolver(matrix, lowest, method, max_iterations, tolerance, m
     b = _f(second_matrix) if second_matrix is not None else np.zeros((1, 1), order="F")
     if initial_vectors is not None:
         x0 = _initial_vectors(initial_vectors, n, lowest)
-        lib.fd_dense_solve_guess(n, _dp(a), int(second_matrix is not None), _dp(b), lowest, _METHOD.get(method, 2), max_iterations,
+        lib.fd_dense_solve_guess(n, _dp(a), int(second_matrix is not None), _dp(b), lowest, _method_code(method), max_iterations,
                                  tolerance, -1 if max_dim_sub is None else max_dim_sub, x0.shape[1], _dp(x0), _dp(evals), _dp(evecs),
                                  C.byref(iters))
         return evals, evecs, iters.value
-    lib.fd_dense_solve(n, _dp(a), int(second_matrix is not None), _dp(b), lowest, _METHOD.get(method, 2), max_iterations, tolerance,
+    lib.fd_dense_solve(n, _dp(a), int(second_matrix is not None), _dp(b), lowest, _method_code(method), max_iterations, tolerance,
                        -1 if max_dim_sub is None else max_dim_sub, _dp(evals), _dp(evecs), C.byref(iters))
     return evals, evecs, iters.value
 
@@ -124,6 +159,7 @@ def generalized_eigensolver_sparse(indptr, indices, data, lowest, method, max_it
     lower=True: only the entries with column <= row are given, for A and B.  initial_vectors (n, g): the solve starts from these
     columns instead of unit vectors.  Returns (eigenvalues, eigenvectors, iters)."""
     _check_bdpr(method, (None, None), where="generalized_eigensolver_sparse")
+    _check_cheb(method, True, second is not None, "generalized_eigensolver_sparse")
     a = indptr if indices is None and data is None else (indptr, indices, data)
     if _is_device_csr(a) or _is_device_csr(second):
         # a matrix in device memory: an engine of its own, built on the GPU (DavidsonEngine.set_sparse)
@@ -145,12 +181,12 @@ def generalized_eigensolver_sparse(indptr, indices, data, lowest, method, max_it
     if initial_vectors is not None:
         x0 = _initial_vectors(initial_vectors, n, lowest)
         fortran_lib().fd_sparse_solve_guess(n, _i64(rp), _i32(ci), _dp(vv), int(second is not None), _i64(rpb), _i32(cib), _dp(vvb), 0,
-                                            int(lower), lowest, _METHOD.get(method, 2), max_iterations, tolerance,
+                                            int(lower), lowest, _method_code(method), max_iterations, tolerance,
                                             -1 if max_dim_sub is None else max_dim_sub, x0.shape[1], _dp(x0), _dp(evals), _dp(evecs),
                                             C.byref(iters))
         return evals, evecs, iters.value
     fortran_lib().fd_sparse_solve(n, _i64(rp), _i32(ci), _dp(vv), int(second is not None), _i64(rpb), _i32(cib), _dp(vvb), 0, int(lower),
-                                  lowest, _METHOD.get(method, 2), max_iterations, tolerance, -1 if max_dim_sub is None else max_dim_sub,
+                                  lowest, _method_code(method), max_iterations, tolerance, -1 if max_dim_sub is None else max_dim_sub,
                                   _dp(evals), _dp(evecs), C.byref(iters))
     return evals, evecs, iters.value
 
@@ -185,6 +221,7 @@ def generalized_eigensolver_bsr(indptr, indices, data, lowest, method, max_itera
     (DavidsonEngine.set_block_sparse on the tensor's device).  lower=True: only the blocks with block column <= block row are given,
     for A and B.  n: the order (default: block rows x b).  initial_vectors (n, g): the solve starts from these columns instead of unit
     vectors.  Returns (eigenvalues, eigenvectors, iters)."""
+    _check_cheb(method, True, second is not None, "generalized_eigensolver_bsr")
     a = indptr if indices is None and data is None else (indptr, indices, data)
     if _is_device_bsr(a) or _is_device_bsr(second):
         # a matrix in device memory: an engine of its own, built on the GPU (DavidsonEngine.set_block_sparse)
@@ -213,12 +250,12 @@ def generalized_eigensolver_bsr(indptr, indices, data, lowest, method, max_itera
     if initial_vectors is not None:
         x0 = _initial_vectors(initial_vectors, n, lowest)
         fortran_lib().fd_bsr_solve_guess(n, b, _i64(rp), _i32(ci), _dp(vv), int(second is not None), _i64(rpb), _i32(cib), _dp(vvb), 0,
-                                         int(lower), lowest, _METHOD.get(method, 2), max_iterations, tolerance,
+                                         int(lower), lowest, _method_code(method), max_iterations, tolerance,
                                          -1 if max_dim_sub is None else max_dim_sub, x0.shape[1], _dp(x0), _dp(evals), _dp(evecs),
                                          C.byref(iters))
         return evals, evecs, iters.value
     fortran_lib().fd_bsr_solve(n, b, _i64(rp), _i32(ci), _dp(vv), int(second is not None), _i64(rpb), _i32(cib), _dp(vvb), 0, int(lower),
-                               lowest, _METHOD.get(method, 2), max_iterations, tolerance, -1 if max_dim_sub is None else max_dim_sub,
+                               lowest, _method_code(method), max_iterations, tolerance, -1 if max_dim_sub is None else max_dim_sub,
                                _dp(evals), _dp(evecs), C.byref(iters))
     return evals, evecs, iters.value
 
@@ -227,6 +264,7 @@ def generalized_eigensolver_free(fun_matrix_gemv, n, lowest, method, max_iterati
                                  fun_second_matrix_gemv, initial_vectors=None):
     """Matrix-free specific with numpy callbacks X(n,k) -> Y(n,k) (reference: src/davidson.f90:277-337).  initial_vectors (n, g): the
     solve starts from these columns instead of unit vectors."""
+    _check_cheb(method, False, where="generalized_eigensolver_free")
     lib = fortran_lib()
 
     def wrap(fn):
@@ -289,11 +327,13 @@ class DavidsonEngine:
         self._note_blocks(which, None)
         self.lib.fd_engine_set_dense(self.p, which, _dp(a))
 
-    def _note_blocks(self, which, b):
+    def _note_blocks(self, which, b, sparse=False):
         """the block size of operator `which` while it is a BSR operator, None otherwise: what solve("BDPR") checks before the engine is
-        called"""
+        called; sparse: it is a CSR or BSR operator, what solve("CHEB") checks"""
         self._blocks = getattr(self, "_blocks", [None, None])
         self._blocks[which - 1] = b
+        self._sparse = getattr(self, "_sparse", [False, False])
+        self._sparse[which - 1] = bool(sparse) or b is not None
 
     def _keep_map(self, which, keep_map):
         """the switch of the set call that follows (Fortran: engine_keep_value_map); what update_values knew of the operator goes"""
@@ -314,6 +354,7 @@ class DavidsonEngine:
         _, rp, ci, vv = _sparse_input(a, self.n, lower)
         self._keep_map(which, keep_map)
         self.lib.fd_engine_set_sparse(self.p, which, self.n, _i64(rp), _i32(ci), _dp(vv), 0, int(lower))
+        self._note_blocks(which, None, sparse=True)
         if keep_map:
             self._kept[which] = {"count": int(rp[-1] - rp[0]), "b": 1, "fortran_blocks": False}
 
@@ -326,6 +367,7 @@ class DavidsonEngine:
                                                   vals.data_ptr() or None, 0, int(lower))
         if st != 0:
             raise DavidsonHipError(hip_lib().dav_last_error().decode())
+        self._note_blocks(which, None, sparse=True)
         if keep_map:
             self._kept[which] = {"count": nnz, "b": 1, "fortran_blocks": False}
 
@@ -456,7 +498,11 @@ class DavidsonEngine:
         """initial_vectors: see set_initial_vectors (a one-shot guess for this solve).  reuse_vectors: True / False turns
         keep_result_as_guess on / off before the solve (sticky), None leaves it as it is; with it on and no initial_vectors the solve
         starts from the previous solve's Ritz vectors when they are still in place.  method "BDPR": the block-diagonal form of DPR,
-        for operators set with set_block_sparse (ValueError otherwise, before the engine is called)."""
+        for operators set with set_block_sparse (ValueError otherwise, before the engine is called).  method "CHEB" / "CHEB<d>": the
+        Chebyshev-filtered correction of degree d (1..64, default 10) for a standard problem whose A was set with set_sparse or
+        set_block_sparse (ValueError otherwise, before the engine is called)."""
+        if _cheb_degree(method) is not None:
+            _check_cheb(method, getattr(self, "_sparse", [False, False])[0], self.gev, "DavidsonEngine.solve")
         if method == "BDPR":
             _check_bdpr(method, getattr(self, "_blocks", [None, None]), self.gev, self.n, self.nranks, "DavidsonEngine.solve")
         if reuse_vectors is not None:
@@ -466,7 +512,7 @@ class DavidsonEngine:
         evals = np.zeros(self.lowest)
         evecs = np.zeros((self.n, self.lowest) if want_vectors else (1, 1), order="F")
         iters = C.c_int(-1)
-        self.lib.fd_engine_solve(self.p, self.lowest, _METHOD.get(method, 2), max_iterations, tolerance, self.max_dim, _dp(evals),
+        self.lib.fd_engine_solve(self.p, self.lowest, _method_code(method), max_iterations, tolerance, self.max_dim, _dp(evals),
                                  int(want_vectors), _dp(evecs), C.byref(iters))
         return evals, (evecs if want_vectors else None), iters.value
 

@@ -54,6 +54,23 @@ enum { DAV_METHOD_DPR = 0, DAV_METHOD_GJD = 1,
         * operator at the first correction - 8 b bytes per local row - gathered again after dav_update_operator_values(_dev), released
         * with the operator.  dav_ritz_residual_correction_g has no method argument and stays DPR; dav_rr_ritz takes the method with C / G. */
        DAV_METHOD_BDPR = 3 };
+/* Chebyshev-filtered correction (opt-in, not in the reference; purely additive within ABI 109) for standard problems whose operator A is
+ * a CSR or BSR operator: Chebyshev-Davidson (Zhou & Saad 2007).  The method code carries the degree: DAV_METHOD_CHEB in the low byte, the
+ * degree d in bits 8..15, 1 <= d <= 64, 0 = the default of 10; every comparison of a method code looks at the low byte.  The Ritz phase
+ * writes the residues R and their norms as for GJD and then, for column j < ncorr with Ritz value theta_j and residue r_j,
+ *   z_1 = (s_1 / e) r_j,   z_{k+1} = (2 s_{k+1} / e) (A z_k - c z_k + pi_k r_j) - s_k s_{k+1} z_{k-1},   V[:, m + j] = z_d
+ * with c = (a + b) / 2, e = (b - a) / 2, s_1 = e / (a0 - c), s_{k+1} = 1 / (2 / s_1 - s_k), pi_0 = 1, pi_1 = (s_1 / e)(theta_j - c),
+ * pi_{k+1} = (2 s_{k+1} / e)(theta_j - c) pi_k - s_k s_{k+1} pi_{k-1}: z_d = p_d(A) x_j - p_d(theta_j) x_j for the Chebyshev polynomial p_d
+ * that is small on [a, b] and 1 at a0.  It costs d - 1 block products of ncorr columns, enqueued back to back: no dot product, nothing
+ * fetched in between.  The interval: b = the largest row sum of |a_ij| of the stored operator (kept with the operator, built at the first
+ * such correction, built again after dav_update_operator_values(_dev), released by a set call), a0 = theta_0, delta = (b - a0) / 64,
+ * a = min(max(theta_{min(ncorr, 2 lowest) - 1}, theta_{lowest - 1} + delta), b - delta).  When b or a Ritz value is not finite, or
+ * a0 < a < b does not hold, the block is +0.0 (DPR's zero-denominator rule).  CONTRACT, refused (non-zero, dav_last_error says why, every
+ * panel as it was): a generalized problem; an operator A that is not CSR / BSR; a degree outside 1..64; no memory for the workspace (three
+ * column blocks).  DAV_CHEB_FUSE=0 (read at dav_create) runs the step as a launch of its own instead of inside the CSR product: same bits.
+ * dav_ritz_residual_correction_g has no method argument and stays DPR; dav_rr_ritz takes the method with C / G. */
+enum { DAV_METHOD_CHEB = 4 };
+#define DAV_METHOD_CHEB_DEGREE(d) (4 | ((d) << 8))
 
 typedef struct dav_stats {
   int64_t n;               /* global order                                                          */
