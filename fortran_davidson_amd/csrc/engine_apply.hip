@@ -433,6 +433,11 @@ int apply_sym_set(E* e, int which, OpDesc& o, const SymSet& set, bool partial, b
 // entries (blocks of b x b; CSR: b = 1), the offsets, the gathered operand read and this rank's rows written.
 static void sparse_traffic(const E* e, const OpDesc& o, int k, double* bytes, double* flops) {
   const double bb = (double)o.sp.b * o.sp.b, nnz = (double)o.sp.nnz;
+  if (o.kind == DAV_KIND_DIA) {          // k_dia.hip: the slots, the offsets, the operand, the rows written; flops = the useful work
+    *bytes = 8.0 * (double)o.sp.dia_nd * (double)e->nloc + 4.0 * (double)o.sp.dia_nd + 8.0 * (double)e->n * k + 8.0 * (double)e->nloc * k;
+    *flops = 2.0 * nnz * k;
+    return;
+  }
   *bytes = 8.0 * bb * nnz + 4.0 * nnz + 8.0 * (double)(o.sp.nrows + 1) + 8.0 * (double)e->n * k + 8.0 * (double)e->nloc * k;
   *flops = 2.0 * bb * nnz * k;
 }
@@ -474,7 +479,8 @@ static int apply_device(E* e, int which, OpDesc& o, const double* src, int k, do
 // The rows of this rank (CSR, k_spmm.hip) or the block rows touching its slab (BSR, k_bsrmm.hip): the operand packed - and gathered over
 // the ranks - as for the row slabs, then one launch of the wave-per-item kernel per 64 columns (the matrix is read once per 64 columns)
 // and the chunk sums of the long rows.  Always fp64 (inner sweeps too: there is no fp32 copy of a sparse operator).
-// epi (CSR): the step of the Chebyshev correction in the product's epilogue (k_spmm.hip), its columns those of src / dst.
+// A CSR matrix stored by diagonals (DAV_KIND_DIA, k_dia.hip) takes the same steps with one launch and no work list.
+// epi (CSR, DIA): the step of the Chebyshev correction in the product's epilogue (k_spmm.hip, k_dia.hip), its columns those of src / dst.
 static int apply_sparse(E* e, int which, OpDesc& o, const double* src, int k, double* dst, bool timed, const ChebEpi* epi = nullptr) {
   const SparseStore& s = o.sp;
   for (int c = 0; c < k; c += 64) {
@@ -487,7 +493,16 @@ static int apply_sparse(E* e, int which, OpDesc& o, const double* src, int k, do
     CHK(pack_operand(e, src + (int64_t)c * e->ldp, kk, has_comm(e)));
     double* out = dst + (int64_t)c * e->ldp;
     if (timed && which == DAV_OP_A) CHK(timed_begin(e, 4, flops, &kslot));
-    if (o.kind == DAV_KIND_CSR && epi) {
+    if (o.kind == DAV_KIND_DIA) {
+      if (epi) {
+        ChebEpi ep = *epi;
+        ep.z += (int64_t)c * ep.ld; ep.r += (int64_t)c * ep.ld; ep.pi += c;
+        if (ep.zprev) ep.zprev += (int64_t)c * ep.ld;
+        launch_spmm_dia_cheb(e->stream, s.dia_off, s.dia_nd, s.dia_val, s.dia_ld, e->nloc, e->row0, e->n, e->xt, e->xt_group_stride, gp, kk, out, e->ldp, ep);
+      } else {
+        launch_spmm_dia(e->stream, s.dia_off, s.dia_nd, s.dia_val, s.dia_ld, e->nloc, e->row0, e->n, e->xt, e->xt_group_stride, gp, kk, out, e->ldp);
+      }
+    } else if (o.kind == DAV_KIND_CSR && epi) {
       ChebEpi ep = *epi;
       ep.z += (int64_t)c * ep.ld; ep.r += (int64_t)c * ep.ld; ep.pi += c;
       if (ep.zprev) ep.zprev += (int64_t)c * ep.ld;
@@ -560,7 +575,7 @@ int apply_ptr(E* e, int which, const double* src, int k, double* dst, bool timed
   if (o.kind == DAV_KIND_IDENTITY) return apply_identity(e, src, k, dst);
   CHK(need_comm(e));
   if (o.kind == DAV_KIND_DEVICE) return apply_device(e, which, o, src, k, dst, timed);
-  if (o.kind == DAV_KIND_CSR || o.kind == DAV_KIND_BSR) return apply_sparse(e, which, o, src, k, dst, timed);
+  if (o.kind == DAV_KIND_CSR || o.kind == DAV_KIND_BSR || o.kind == DAV_KIND_DIA) return apply_sparse(e, which, o, src, k, dst, timed);
   if ((o.kind == DAV_KIND_DENSE || o.kind == DAV_KIND_HASHED || o.kind == DAV_KIND_HARNESS) && o.storage == 1)
     return apply_symmetric(e, which, o, src, k, dst, timed, inner);
   return apply_full_rows(e, which, o, src, k, dst, timed);
@@ -568,7 +583,7 @@ int apply_ptr(E* e, int which, const double* src, int k, double* dst, bool timed
 
 int apply_csr_cheb(E* e, const double* src, int k, double* dst, const ChebEpi& epi) {
   OpDesc& o = e->op[DAV_OP_A];
-  if (o.kind != DAV_KIND_CSR) return fail("apply_csr_cheb: operator A is not a CSR operator");
+  if (o.kind != DAV_KIND_CSR && o.kind != DAV_KIND_DIA) return fail("apply_csr_cheb: operator A is not a CSR operator");
   CHK(need_comm(e));
   return apply_sparse(e, DAV_OP_A, o, src, k, dst, true, &epi);
 }
@@ -653,7 +668,7 @@ extern "C" int dav_bench_apply2(dav_handle_t e, int which, int k, int reps, doub
   e->timing_level = saved_level;
   *avg_ms = total / reps;
   *kernel_ms = ktotal / reps;
-  if (e->op[which].kind == DAV_KIND_CSR || e->op[which].kind == DAV_KIND_BSR) {
+  if (e->op[which].kind == DAV_KIND_CSR || e->op[which].kind == DAV_KIND_BSR || e->op[which].kind == DAV_KIND_DIA) {
     sparse_traffic(e, e->op[which], k, bytes, flops);
     e->st = saved;
     return 0;

@@ -9,6 +9,7 @@ const char* kind_name(int kind) {
     case DAV_KIND_NONE: return "not set";
     case DAV_KIND_DENSE: return "a dense matrix";
     case DAV_KIND_CSR: return "a CSR matrix";
+    case DAV_KIND_DIA: return "a CSR matrix stored by diagonals";
     default: return "not a BSR matrix";
   }
 }

@@ -25,7 +25,7 @@ size_t ws_block(const E* e) { return (size_t)e->ldp * ws_cols(e); }
 int cheb_prepare(E* e, int degree) {
   if (e->gev) return refuse("a generalized problem is not served (the filter would need the inverse of operator B)");
   OpDesc& A = e->op[DAV_OP_A];
-  if (A.kind != DAV_KIND_CSR && A.kind != DAV_KIND_BSR)
+  if (A.kind != DAV_KIND_CSR && A.kind != DAV_KIND_BSR && A.kind != DAV_KIND_DIA)
     return refuse(std::string("operator A is ") + kind_name(A.kind) +
                   ": the spectral bound is taken from the stored entries of a CSR or BSR operator (dav_set_operator_csr / dav_set_operator_bsr)");
   if (degree < 1 || degree > CHEB_MAX_DEGREE) return refuse("degree " + std::to_string(degree) + " is outside 1.." + std::to_string(CHEB_MAX_DEGREE));
@@ -46,7 +46,8 @@ int cheb_prepare(E* e, int degree) {
       s.rbound = nullptr;
       return refuse("device memory for the spectral bound could not be allocated");
     }
-    launch_cheb_row_bound(e->stream, s.b, s.rp, s.val, s.nrows, s.rbound + e->nranks, s.rbound, e->rank, e->nranks);
+    if (A.kind == DAV_KIND_DIA) launch_dia_row_bound(e->stream, s.dia_val, s.dia_ld, s.dia_nd, e->nloc, s.rbound + e->nranks, s.rbound, e->rank, e->nranks);
+    else launch_cheb_row_bound(e->stream, s.b, s.rp, s.val, s.nrows, s.rbound + e->nranks, s.rbound, e->rank, e->nranks);
     HIPCHK(hipGetLastError());
     if (has_comm(e)) CHK(coll_allreduce(e, s.rbound, (size_t)e->nranks));     // a sum: every slot has one non-zero term
     s.rbound_valid = true;
@@ -56,7 +57,7 @@ int cheb_prepare(E* e, int degree) {
 
 // V[:, m:m+ncorr] = z_d from R[:, 0:ncorr] on the engine's stream, behind the residual product that wrote R (cheb_prepare has passed).
 // z_k alternate between workspace blocks; the last step writes into V.  Separate step: blocks 0 / 1 hold z, block 2 the product, the step
-// overwrites z_{k-1} in place.  Fused (CSR, DAV_CHEB_FUSE): the product's epilogue writes z_{k+1} into the third block, the three rotate.
+// overwrites z_{k-1} in place.  Fused (CSR, also stored by diagonals; DAV_CHEB_FUSE): the product's epilogue writes z_{k+1} into the third block, the three rotate.
 int cheb_correct(E* e, int m, int ncorr, int lowest, int degree, const double* theta_dev) {
   if (ncorr > ws_cols(e)) return refuse("the correction block is wider than the workspace");
   const SparseStore& s = e->op[DAV_OP_A].sp;
@@ -65,7 +66,8 @@ int cheb_correct(E* e, int m, int ncorr, int lowest, int degree, const double* t
   const int pstride = (int)roundup(ws_cols(e), 64);
   const double* R = panel_ptr(e, DAV_PANEL_R, 0);
   double* T = panel_ptr(e, DAV_PANEL_V, m);
-  const bool fuse = e->tune.cheb_fuse != 0 && e->op[DAV_OP_A].kind == DAV_KIND_CSR;
+  const int kind = e->op[DAV_OP_A].kind;
+  const bool fuse = e->tune.cheb_fuse != 0 && (kind == DAV_KIND_CSR || kind == DAV_KIND_DIA);
   launch_cheb_coef(e->stream, theta_dev, ncorr, lowest, degree, s.rbound, e->nranks, coef, pstride);
   launch_cheb_step(e->stream, 0, coef, pstride, nullptr, nullptr, R, nullptr, degree == 1 ? T : ws[0], e->ldp, ncorr, e->nloc, e->nloc_pad);
   int cur = 0, prev = -1;          // blocks of z_k and z_{k-1}

@@ -157,6 +157,12 @@ struct SparseStore {
   // per rank (the maximum of the slots is the bound) followed by the partials of the row-sum kernel; stale and released as bdiag is
   double* rbound = nullptr;
   bool rbound_valid = false;
+  // DAV_KIND_DIA (a CSR set call with DAV_CSR_DIAGONALS; k_dia.hip): the storage by diagonals.  col / val and the work list are released
+  // once it is filled (rp too) - unless the set call kept its value map, which keeps rp / col / val / src / doff / dpos for the refresh
+  int32_t* dia_off = nullptr;       // device: the dia_nd sorted offsets column - row of the whole matrix
+  double* dia_val = nullptr;        // device: dia_val[d * dia_ld + i] = entry (row0 + i, row0 + i + dia_off[d]) of local row i, or +0.0
+  int dia_nd = 0;
+  int64_t dia_ld = 0;               // nloc rounded up to 16: every diagonal starts 128-byte aligned
 };
 
 struct OpDesc {
@@ -187,7 +193,7 @@ struct OpDesc {
   // DAV_KIND_DEVICE: the caller's own block apply on device memory (dav_set_operator_device)
   dav_device_apply_fn dev_fn = nullptr;
   void* dev_ctx = nullptr;
-  SparseStore sp;            // DAV_KIND_CSR / DAV_KIND_BSR
+  SparseStore sp;            // DAV_KIND_CSR / DAV_KIND_BSR / DAV_KIND_DIA
 };
 
 struct SmallBuf {            // device small matrix + pinned staging

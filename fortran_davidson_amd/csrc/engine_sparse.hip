@@ -6,17 +6,24 @@
 // work list and sets the operator.  Host and device entries produce the same arrays bit for bit.  With dav_keep_value_map on, CSR travels
 // with sources too and every entry keeps them (the value map) with the sources of the diagonal; dav_update_operator_values(_dev) then
 // repeats the VALUES and DIAGONAL steps alone on new numbers (kernels in k_sparse_refresh.hip).
+// DAV_CSR_DIAGONALS or-ed into the triangle of a CSR entry: the entry decides from the offsets of the whole matrix
+// whether it suits the storage by diagonals (dia_rule.h) before it builds anything, builds the canonical CSR as always, and a last step
+// moves the values into the diagonals (k_dia.hip) and releases the canonical arrays - unless the value map is kept: then rp / col / val
+// stay for the refresh, which fills the diagonals again (device memory: that of the CSR operator with its map plus 8 nd nloc bytes).
 #include "engine_internal.h"
+#include "dia_rule.h"
 
 void sparse_release(E* e, OpDesc& o) {
   SparseStore& s = o.sp;
-  if (!s.rp && !s.col && !s.val && !s.items && !s.longs && !s.part && !s.src && !s.doff && !s.dpos && !s.bdiag && !s.rbound) return;
+  if (!s.rp && !s.col && !s.val && !s.items && !s.longs && !s.part && !s.src && !s.doff && !s.dpos && !s.bdiag && !s.rbound && !s.dia_off && !s.dia_val)
+    return;
   (void)hipStreamSynchronize(e->stream);         // applies in flight may still read the arrays
   pool_free(s.rp); pool_free(s.col); pool_free(s.val);
   pool_free(s.items); pool_free(s.longs); pool_free(s.part);
   pool_free(s.src); pool_free(s.doff); pool_free(s.dpos);
   pool_free(s.bdiag);
   pool_free(s.rbound);
+  pool_free(s.dia_off); pool_free(s.dia_val);
   s = SparseStore();
 }
 
@@ -86,7 +93,8 @@ std::string bad_arguments(const SparseWords& w, int64_t n, bool bsr, int b, int 
     if (n / b >= ((int64_t)1 << 31)) return "n / block_size must be below 2^31 (int32 block columns)";
   }
   if (index_base != 0 && index_base != 1) return "index_base must be 0 or 1";
-  if (triangle != DAV_CSR_FULL && triangle != DAV_CSR_LOWER) return "triangle must be DAV_CSR_FULL or DAV_CSR_LOWER";
+  if ((triangle & ~(DAV_CSR_LOWER | DAV_CSR_DIAGONALS)) != 0) return "triangle must be DAV_CSR_FULL or DAV_CSR_LOWER";
+  if (bsr && (triangle & DAV_CSR_DIAGONALS)) return "DAV_CSR_DIAGONALS serves the CSR entries only (dav_set_operator_csr / dav_set_operator_csr_dev): a BSR matrix is not stored by diagonals";
   if (bsr && block_layout != DAV_BSR_ROW_MAJOR && block_layout != DAV_BSR_COL_MAJOR) return "block_layout must be DAV_BSR_ROW_MAJOR or DAV_BSR_COL_MAJOR";
   if (bits && bits[0] != 32 && bits[0] != 64) return "row_ptr_bits must be 32 or 64";
   if (bits && bits[1] != 32 && bits[1] != 64) return "col_bits must be 32 or 64";
@@ -263,6 +271,46 @@ int commit_host(const Entry& en, int kind, int b, int64_t grow0, const std::vect
   }
   return sparse_commit(en, kind, b, grow0, rp, diag, nullptr, oom);
 }
+
+// ---- storage by diagonals (DAV_CSR_DIAGONALS) ---------------------------------------------------------------------------------------------
+// the offsets of the whole matrix from its marks and the rule of dia_rule.h; false: *why says what the matrix has and what the rule asks
+bool dia_decide(const uint8_t* marks, int64_t n, int64_t nnz, int64_t ndiag, bool lower, std::vector<int32_t>& offs, std::string* why) {
+  dia_offsets_from_marks(marks, n, offs);
+  const int64_t entries = dia_canonical_entries(nnz, ndiag, lower);
+  if (dia_eligible((int64_t)offs.size(), n, entries)) return true;
+  *why = dia_refusal((int64_t)offs.size(), n, entries);
+  return false;
+}
+
+// the slots of this rank from its canonical rows (rp / col / val of the store, on the device)
+void dia_fill(E* e, const SparseStore& s) {
+  launch_dia_fill(e->stream, s.rp, s.col, s.val, e->nloc, e->row0, s.dia_off, s.dia_nd, s.dia_val, s.dia_ld);
+}
+
+// The last step of a CSR entry called with DAV_CSR_DIAGONALS, behind the commit: the diagonals are allocated and filled, the operator
+// becomes DAV_KIND_DIA and what only the CSR product reads is released (with the value map kept: the work list alone).
+int dia_commit(const Entry& en, const std::vector<int32_t>& offs) {
+  E* e = en.e;
+  OpDesc& o = e->op[en.which];
+  SparseStore& s = o.sp;
+  s.dia_nd = (int)offs.size();
+  s.dia_ld = dia_leading_dimension(e->nloc);
+  const size_t slots = (size_t)s.dia_nd * (size_t)s.dia_ld;
+  if (!upload(&s.dia_off, offs) || !keep(&s.dia_val, slots))
+    return en.refuse(no_memory(std::to_string(s.dia_nd) + " diagonals of this rank (" + std::to_string((8 * slots) >> 20) + " MiB)"));
+  dia_fill(e, s);
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipGetLastError());
+  pool_free(s.items); pool_free(s.longs); pool_free(s.part);
+  s.items = nullptr; s.longs = nullptr; s.part = nullptr;
+  s.nitems = 0; s.nlong = 0;
+  if (!s.src) {
+    pool_free(s.rp); pool_free(s.col); pool_free(s.val);
+    s.rp = nullptr; s.col = nullptr; s.val = nullptr;
+  }
+  o.kind = DAV_KIND_DIA;
+  return 0;
+}
 }  // namespace
 
 extern "C" int dav_set_operator_csr(dav_handle_t e, int which, const int64_t* row_ptr, const int32_t* col_idx, const double* vals,
@@ -272,8 +320,15 @@ extern "C" int dav_set_operator_csr(dav_handle_t e, int which, const int64_t* ro
   const int64_t n = e->n;
   std::string why = bad_arguments(en.w, n, false, 0, index_base, triangle, 0, nullptr, row_ptr);
   if (!why.empty()) return en.refuse(why);
-  const HostPattern P{row_ptr, col_idx, n, e->row0, e->nloc, index_base, triangle == DAV_CSR_LOWER};
+  const HostPattern P{row_ptr, col_idx, n, e->row0, e->nloc, index_base, (triangle & DAV_CSR_LOWER) != 0};
   if (!pattern_validate(P, vals, en.w, &why)) return en.refuse(why);
+  std::vector<int32_t> dia_offsets;
+  if (triangle & DAV_CSR_DIAGONALS) {
+    std::vector<uint8_t> marks;
+    int64_t ndiag = 0;
+    dia_mark_host(row_ptr, col_idx, n, index_base, P.lower, marks, &ndiag);
+    if (!dia_decide(marks.data(), n, row_ptr[n] - index_base, ndiag, P.lower, dia_offsets, &why)) return en.refuse(why);
+  }
   std::vector<int64_t> rp;
   std::vector<int32_t> lcol;
   std::vector<double> lval;
@@ -285,7 +340,7 @@ extern "C" int dav_set_operator_csr(dav_handle_t e, int which, const int64_t* ro
     for (size_t q = 0; q < lval.size(); ++q) lval[q] = vals[map.src[q] >> 1];
     map.doff.assign((size_t)n + 1, 0);
     map.gcount = row_ptr[n] - index_base;
-    map.triangle = triangle;
+    map.triangle = triangle & DAV_CSR_LOWER;
   } else {
     pattern_order(P, [&](int64_t p, bool) { return vals[p]; }, rp, lcol, lval);
   }
@@ -299,7 +354,8 @@ extern "C" int dav_set_operator_csr(dav_handle_t e, int which, const int64_t* ro
       }
     if (keep_map) map.doff[(size_t)i + 1] = (int64_t)map.dpos.size();
   }
-  return commit_host(en, DAV_KIND_CSR, 1, 0, rp, lcol, lval, diag, 12 * rp.back() + 8 * e->nloc, keep_map ? &map : nullptr);
+  CHK(commit_host(en, DAV_KIND_CSR, 1, 0, rp, lcol, lval, diag, 12 * rp.back() + 8 * e->nloc, keep_map ? &map : nullptr));
+  return (triangle & DAV_CSR_DIAGONALS) ? dia_commit(en, dia_offsets) : 0;
 }
 
 extern "C" int dav_set_operator_bsr(dav_handle_t e, int which, int block_size, const int64_t* block_row_ptr, const int32_t* block_col_idx,
@@ -538,6 +594,23 @@ int pattern_begin_dev(const Entry& en, BuildScratch& sc, DevPattern& P, std::vec
   return pattern_offsets_dev(en.e, sc, P, en.w, &en.e->op[en.which].sp.rp, rp, why);
 }
 
+// (DAV_CSR_DIAGONALS) the marks of the caller's validated arrays on the device, read back: the list and the decision of the host entry
+int dia_decide_dev(E* e, BuildScratch& sc, const DevPattern& P, std::vector<int32_t>& offs, std::string* why) {
+  const size_t nmarks = P.n > 0 ? (size_t)(2 * P.n - 1) : 0;
+  uint8_t* marks = nullptr;
+  unsigned long long* ndiag = nullptr;
+  sc.take(&marks, nmarks); sc.take(&ndiag, 1);
+  if (sc.oom) { *why = no_memory("the marks of " + std::to_string(nmarks) + " offsets"); return 1; }
+  HIPCHK(hipMemsetAsync(marks, 0, std::max<size_t>(nmarks, 1), e->stream));
+  HIPCHK(hipMemsetAsync(ndiag, 0, sizeof(unsigned long long), e->stream));
+  launch_dia_mark(e->stream, P.row_ptr, P.rp64, P.col_idx, P.ci64, P.n, P.nnz, P.base, P.lower ? 1 : 0, marks, ndiag);
+  std::vector<uint8_t> hmarks(std::max<size_t>(nmarks, 1));
+  unsigned long long hdiag = 0;
+  CHK(readback(e->stream, hmarks.data(), marks, nmarks));
+  CHK(readback(e->stream, &hdiag, ndiag, sizeof(hdiag)));
+  return dia_decide(hmarks.data(), P.n, P.nnz, (int64_t)hdiag, P.lower, offs, why) ? 0 : 1;
+}
+
 // the diagonal of the whole matrix on the device
 double* diag_scratch(BuildScratch& sc, int64_t n, std::string* why) {
   double* d = nullptr;
@@ -577,9 +650,12 @@ extern "C" int dav_set_operator_csr_dev(dav_handle_t e, int which, const void* r
   std::string why = bad_arguments(en.w, e->n, false, 0, index_base, triangle, 0, bits, row_ptr);
   if (!why.empty()) return en.refuse(why);
   BuildScratch sc(e->stream);
-  DevPattern P{row_ptr, row_ptr_bits == 64, col_idx, col_bits == 64, vals, 8, e->n, e->row0, e->nloc, index_base, triangle == DAV_CSR_LOWER};
+  DevPattern P{row_ptr, row_ptr_bits == 64, col_idx, col_bits == 64, vals, 8, e->n, e->row0, e->nloc, index_base, (triangle & DAV_CSR_LOWER) != 0};
   std::vector<int64_t> rp;
   if (int rc = pattern_begin_dev(en, sc, P, rp, &why)) return en.step(rc, why);
+  std::vector<int32_t> dia_offsets;
+  if (triangle & DAV_CSR_DIAGONALS)
+    if (int rc = dia_decide_dev(e, sc, P, dia_offsets, &why)) return en.step(rc, why);
   SparseStore& s = e->op[which].sp;
   const int64_t lnnz = rp.back();
   if (!keep(&s.col, (size_t)lnnz) || !keep(&s.val, (size_t)lnnz)) return en.refuse(no_memory(stored(en.w, lnnz, 12 * lnnz + 8 * e->nloc)));
@@ -595,9 +671,10 @@ extern "C" int dav_set_operator_csr_dev(dav_handle_t e, int which, const void* r
   if (!diag) return en.refuse(why);
   launch_csr_build_diag(e->stream, row_ptr, P.rp64, col_idx, P.ci64, vals, e->n, index_base, P.dcount, P.dfirst, diag);
   if (keep_map)
-    if (int rc = keep_diag_sources(en, sc, P, triangle, 0, &why)) return en.step(rc, why);
+    if (int rc = keep_diag_sources(en, sc, P, triangle & DAV_CSR_LOWER, 0, &why)) return en.step(rc, why);
   std::vector<double> hdiag;
-  return sparse_commit(en, DAV_KIND_CSR, 1, 0, rp, hdiag, diag, no_memory(work_list(en.w, lnnz)));
+  CHK(sparse_commit(en, DAV_KIND_CSR, 1, 0, rp, hdiag, diag, no_memory(work_list(en.w, lnnz))));
+  return (triangle & DAV_CSR_DIAGONALS) ? dia_commit(en, dia_offsets) : 0;
 }
 
 // The index level is the CSR device build over the n / b block rows, local block rows = those that touch the slab, with the SOURCE of a
@@ -654,10 +731,10 @@ namespace {
 // a refused update leaves the operator as it is: set, with its old values
 int update_refuse(const char* name, const std::string& msg) { return fail(std::string(name) + ": " + msg); }
 
-// "" = the operator can take new values: CSR or BSR, set with its value map
+// "" = the operator can take new values: CSR (also stored by diagonals) or BSR, set with its value map
 std::string not_updatable(const OpDesc& o) {
   if (o.kind == DAV_KIND_NONE) return "operator not set";
-  if (o.kind != DAV_KIND_CSR && o.kind != DAV_KIND_BSR)
+  if (o.kind != DAV_KIND_CSR && o.kind != DAV_KIND_BSR && o.kind != DAV_KIND_DIA)
     return "the operator is not a CSR or BSR operator (only a sparse operator set after dav_keep_value_map(h, which, 1) takes new values)";
   if (!o.sp.src || !o.sp.doff || !o.sp.dpos)
     return "the operator was set without its value map: call dav_keep_value_map(h, which, 1) before the set call";
@@ -672,8 +749,9 @@ int update_from_device(E* e, int which, const char* name, BuildScratch& sc, cons
   double* diag = nullptr;          // the diagonal of the whole matrix (o.diag holds the local rows)
   sc.take(&diag, (size_t)e->n);
   if (sc.oom) return update_refuse(name, no_memory("the diagonal"));
-  if (o.kind == DAV_KIND_CSR) launch_sparse_refresh_csr(st, s.src, s.nnz, vals, s.val);
-  else launch_bsr_build_gather(st, s.b, s.src, s.nnz, vals, s.rowmaj, s.val);
+  if (o.kind == DAV_KIND_BSR) launch_bsr_build_gather(st, s.b, s.src, s.nnz, vals, s.rowmaj, s.val);
+  else launch_sparse_refresh_csr(st, s.src, s.nnz, vals, s.val);
+  if (o.kind == DAV_KIND_DIA) dia_fill(e, s);        // the slots follow the values, as the set call filled them
   o.sp.bdiag_valid = false;          // the diagonal blocks of a BDPR correction follow the values: rebuilt at the next one
   o.sp.rbound_valid = false;         // ... and the row-sum bound of a CHEB correction
   launch_sparse_refresh_diag(st, s.b, s.doff, s.dpos, vals, e->n, diag);

@@ -10,6 +10,8 @@
 //                  rows, per wave by a __shfl_xor butterfly, per workgroup through LDS, one partial per workgroup; a second one-workgroup
 //                  launch takes the maximum of the partials into this rank's slot and writes +0.0 into the slots of the other ranks (the
 //                  all-reduce that follows SUMS, x + 0 is exact).  A maximum is independent of the order it is taken in.  NaN propagates.
+//                  dia_row_bound: the same for a CSR operator stored by diagonals (k_dia.hip) - one thread per row, its slots added in
+//                  ascending offset; a fill slot adds +0.0, so without duplicates the bits are those of the CSR bound.
 // cheb_coef        one lane per column: the interval rule from the device copy of theta and the bound, s_k, alpha_k, beta_k (the same in
 //                  every lane; lane 0 writes them) and pi_k of the lane's column.  No host round trip between the Ritz values and the steps.
 // cheb_step        the recurrence step on panel columns, two rows (16 bytes) per lane and array, arithmetic by cheb_combine (kernels.h):
@@ -46,6 +48,21 @@ __global__ __launch_bounds__(CH_THREADS) void cheb_row_bound_kernel(int b, const
     double s = 0.0;
     for (int64_t p = rp[I]; p < p1; ++p)
       for (int k = 0; k < b; ++k) s += __builtin_fabs(val[p * bb + (int64_t)k * b + row]);
+    m = ch_max(m, s);
+  }
+  m = ch_block_max(m, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = m;
+}
+
+// an operator stored by diagonals (k_dia.hip): one thread per local row, its slots in ascending offset (coalesced: lane = row)
+__global__ __launch_bounds__(CH_THREADS) void dia_row_bound_kernel(const double* __restrict__ dval, int64_t ld, int nd, int64_t nloc,
+                                                                   double* __restrict__ partial) {
+  __shared__ double sh[CH_THREADS / 64];
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  double m = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nloc; i += stride) {
+    double s = 0.0;
+    for (int d = 0; d < nd; ++d) s += __builtin_fabs(dval[(int64_t)d * ld + i]);
     m = ch_max(m, s);
   }
   m = ch_block_max(m, sh);
@@ -144,6 +161,12 @@ void launch_cheb_row_bound(hipStream_t st, int bs, const int64_t* rp, const doub
   const int64_t rows = nbl * bs;
   const int grid = (int)std::min<int64_t>(std::max<int64_t>((rows + CH_THREADS - 1) / CH_THREADS, 1), CHEB_BOUND_PARTIALS);
   hipLaunchKernelGGL(cheb_row_bound_kernel, dim3(grid), dim3(CH_THREADS), 0, st, bs, rp, val, nbl, partial);
+  hipLaunchKernelGGL(cheb_bound_finish_kernel, dim3(1), dim3(CH_THREADS), 0, st, partial, grid, slots, rank, nranks);
+}
+
+void launch_dia_row_bound(hipStream_t st, const double* dval, int64_t ld, int nd, int64_t nloc, double* partial, double* slots, int rank, int nranks) {
+  const int grid = (int)std::min<int64_t>(std::max<int64_t>((nloc + CH_THREADS - 1) / CH_THREADS, 1), CHEB_BOUND_PARTIALS);
+  hipLaunchKernelGGL(dia_row_bound_kernel, dim3(grid), dim3(CH_THREADS), 0, st, dval, ld, nd, nloc, partial);
   hipLaunchKernelGGL(cheb_bound_finish_kernel, dim3(1), dim3(CH_THREADS), 0, st, partial, grid, slots, rank, nranks);
 }
 

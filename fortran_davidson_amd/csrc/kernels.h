@@ -199,6 +199,21 @@ void launch_spmm_csr_cheb(hipStream_t st, const CsrItem* items, int nitems, cons
 void launch_spmm_csr_finish_cheb(hipStream_t st, const CsrLong* longs, int nlong, const double* part, int kk, double* dst, int64_t ldd,
                                  const ChebEpi& epi);
 
+// ---- K1d: a CSR operator stored by diagonals (k_dia.hip; DAV_CSR_DIAGONALS) ------------------------------------------------------------
+// marks[col - row + n - 1] = 1 for every entry of the caller's validated arrays (lower: and for its mirror image), *ndiag += the diagonal
+// entries; marks (2 n - 1 bytes) and *ndiag zeroed by the caller
+void launch_dia_mark(hipStream_t st, const void* row_ptr, int rp64, const void* col_idx, int ci64, int64_t n, int64_t nnz, int base, int lower,
+                     uint8_t* marks, unsigned long long* ndiag);
+int64_t dia_leading_dimension(int64_t nloc);     // nloc rounded up to 16 doubles: every diagonal starts 128-byte aligned
+// dval[d][i], d < nd, i < ld, from the canonical local rows rp / col / val: +0.0, or the sum from +0.0 of the entries at (i, row0 + i + off[d])
+void launch_dia_fill(hipStream_t st, const int64_t* rp, const int32_t* col, const double* val, int64_t nloc, int64_t row0, const int32_t* off,
+                     int nd, double* dval, int64_t ld);
+// rows [0, nloc) of dst[:, 0:kk] = A X from the packed operand; groups as for launch_spmm_csr; padding rows are not touched
+void launch_spmm_dia(hipStream_t st, const int32_t* off, int nd, const double* dval, int64_t ld, int64_t nloc, int64_t row0, int64_t n,
+                     const double* xt, int64_t xt_gstride, int groups, int kk, double* dst, int64_t ldd);
+void launch_spmm_dia_cheb(hipStream_t st, const int32_t* off, int nd, const double* dval, int64_t ld, int64_t nloc, int64_t row0, int64_t n,
+                          const double* xt, int64_t xt_gstride, int groups, int kk, double* dst, int64_t ldd, const ChebEpi& epi);
+
 // ---- K1c': device build of a CSR operator (k_csr_build.hip; dav_set_operator_csr_dev) -----------------------------------------------
 // The caller's global arrays: row_ptr and col_idx of 32 (rp64 / ci64 = 0) or 64 bits, numbered from `base`.  info[4] (set to ~0 first):
 // [0] first row where row_ptr decreases, [1] row_ptr[0], [2] row_ptr[n], [3] first row of 2^32 or more entries.
@@ -347,6 +362,9 @@ __device__ __forceinline__ double cheb_combine(double y, double z, double r, dou
 // entries added in stored order from +0.0; NaN propagates), slots[p] = +0.0 for the other p < nranks; partial: CHEB_BOUND_PARTIALS doubles
 void launch_cheb_row_bound(hipStream_t st, int bs, const int64_t* rp, const double* val, int64_t nbl, double* partial, double* slots, int rank,
                            int nranks);
+// the same bound of an operator stored by diagonals: the row sums of |dval[d][i]|, d ascending from +0.0, over the nloc local rows (fill
+// slots add +0.0: without duplicates the bits of the CSR bound of the same matrix)
+void launch_dia_row_bound(hipStream_t st, const double* dval, int64_t ld, int nd, int64_t nloc, double* partial, double* slots, int rank, int nranks);
 // the interval and the coefficients of a correction of `degree` from theta[0 .. ncorr) and max(slots[0 .. nranks)): one lane per column
 void launch_cheb_coef(hipStream_t st, const double* theta, int ncorr, int lowest, int degree, const double* slots, int nranks, double* coef,
                       int pstride);

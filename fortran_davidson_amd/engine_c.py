@@ -52,6 +52,12 @@ def _dp(a):
 
 
 CSR_FULL, CSR_LOWER = 0, 1
+CSR_DIAGONALS = 2          # or-ed to either: the matrix is stored by diagonals (DAV_CSR_DIAGONALS)
+
+
+def csr_flag_word(lower=False, diagonals=False):
+    """the `triangle` argument of the CSR set entries (and the `lower` integer of the Fortran doors): bit 0 lower, bit 1 diagonals"""
+    return (CSR_LOWER if lower else CSR_FULL) | (CSR_DIAGONALS if diagonals else 0)
 
 
 def csr_arrays(indptr, indices=None, data=None, n=None):
@@ -476,35 +482,36 @@ class CEngine:
         self._device_ops[which] = (fn, ctx)                # keep the callback alive as long as the engine
         self._chk(self.lib.dav_set_operator_device(self.h, which, fn, ctx, _dp(d)))
 
-    def set_operator_csr(self, which, indptr, indices=None, data=None, base=0, lower=False):
+    def set_operator_csr(self, which, indptr, indices=None, data=None, base=0, lower=False, diagonals=False):
         """dav_set_operator_csr: a symmetric matrix in CSR form (the global arrays; indptr / indices numbered from `base`), every nonzero
         (lower=False) or only the entries with column <= row (lower=True).  Three numpy arrays, or one object with .tocsr(), or a
         torch.sparse_csr_tensor (one on the GPU goes to set_operator_csr_dev).  The engine validates the input (DavidsonHipError) and
-        leaves the operator unset when it refuses it."""
+        leaves the operator unset when it refuses it.  diagonals=True (DAV_CSR_DIAGONALS): the matrix is stored by its diagonals - for
+        stencils and banded matrices; one with too many diagonals for its entries is refused, never stored as CSR instead."""
         if is_torch_csr(indptr):
             parts = torch_csr_parts(indptr)
             if indptr.device.type != "cpu":
-                return self.set_operator_csr_dev(which, *parts, base=base, lower=lower)
+                return self.set_operator_csr_dev(which, *parts, base=base, lower=lower, diagonals=diagonals)
             indptr, indices, data = parts
         rp, ci, vv = csr_arrays(indptr, indices, data, self.n)
         ci_p = ci.ctypes.data_as(C.POINTER(C.c_int32)) if ci.size else (C.c_int32 * 1)()
         vv_p = _dp(vv) if vv.size else (C.c_double * 1)()
         self._saw_values(which, None)
         self._chk(self.lib.dav_set_operator_csr(self.h, which, rp.ctypes.data_as(C.POINTER(C.c_int64)), ci_p, vv_p, base,
-                                                CSR_LOWER if lower else CSR_FULL))
+                                                csr_flag_word(lower, diagonals)))
         self._saw_values(which, int(rp[-1] - rp[0]))
 
-    def set_operator_csr_dev(self, which, row_ptr, col_idx, vals, base=0, lower=False):
+    def set_operator_csr_dev(self, which, row_ptr, col_idx, vals, base=0, lower=False, diagonals=False):
         """dav_set_operator_csr_dev: the matrix of set_operator_csr as torch tensors on the engine's device, built on the GPU - row_ptr
         (n + 1) and col_idx int32 or int64, vals float64, all contiguous.  Other dtypes are a TypeError (never converted).  Torch's
         current stream on the device is synchronised first, so work queued on it that writes the arrays is complete.  The engine's
-        refusal is a DavidsonHipError; the operator is then unset."""
+        refusal is a DavidsonHipError; the operator is then unset.  diagonals: as for set_operator_csr."""
         rpb, cib, nnz = _device_csr_tensors(row_ptr, col_idx, vals, self.n, self.device)
         import torch
         torch.cuda.current_stream(row_ptr.device).synchronize()
         self._saw_values(which, None)
         self._chk(self.lib.dav_set_operator_csr_dev(self.h, which, row_ptr.data_ptr(), rpb, col_idx.data_ptr() or None, cib,
-                                                    vals.data_ptr() or None, base, CSR_LOWER if lower else CSR_FULL))
+                                                    vals.data_ptr() or None, base, csr_flag_word(lower, diagonals)))
         self._saw_values(which, nnz)
 
     def set_operator_bsr(self, which, indptr, indices=None, data=None, base=0, lower=False, layout=BSR_ROW_MAJOR):

@@ -9,6 +9,7 @@ module davidson_c_api
   use davidson_free, only: free_matmul
   use davidson_sparse, only: csr_matrix, bsr_matrix, engine_set_sparse, engine_set_sparse_device, engine_set_block_sparse_device, &
        engine_keep_value_map, engine_update_sparse_values, engine_update_sparse_values_device
+  use davidson_hip_c, only: DAV_CSR_LOWER, DAV_CSR_DIAGONALS, DAV_BSR_ROW_MAJOR, DAV_BSR_COL_MAJOR, dav_set_operator_bsr_dev
   use lapack_wrapper
   use array_utils
   implicit none
@@ -70,7 +71,8 @@ contains
     iters = it
   end subroutine fd_dense_solve
 
-  !> A csr_matrix from C arrays (row_ptr: n + 1 int64 offsets, col_idx: int32) numbered from `base` (0 or 1): renumbered from 1
+  !> A csr_matrix from C arrays (row_ptr: n + 1 int64 offsets, col_idx: int32) numbered from `base` (0 or 1): renumbered from 1.
+  !> `lower` is the flag word of the CSR set entries: bit 0 = lower triangle, bit 1 = stored by diagonals (DAV_CSR_DIAGONALS)
   function csr_from_c(n, row_ptr, col_idx, vals, base, lower) result(a)
     integer(c_int), intent(in) :: n, base, lower
     integer(c_int64_t), intent(in) :: row_ptr(n + 1)
@@ -83,7 +85,8 @@ contains
     a%row_ptr = row_ptr + (1 - base)
     a%col_idx = col_idx(1:nnz) + int(1 - base, c_int32_t)
     a%values = vals(1:nnz)
-    a%lower = lower /= 0
+    a%lower = iand(lower, DAV_CSR_LOWER) /= 0
+    a%diagonals = iand(lower, DAV_CSR_DIAGONALS) /= 0
   end function csr_from_c
 
   !> generalized_eigensolver(a_csr, ...) - sparse specific.  max_dim < 0: argument absent; has_b: B given (same base and triangle).
@@ -125,13 +128,17 @@ contains
     real(c_double), intent(in) :: vals(b, b, *)
     type(bsr_matrix) :: a
     integer(c_int64_t) :: nnzb
+    if (iand(lower, DAV_CSR_DIAGONALS) /= 0) then
+       print *, "bsr_matrix: DAV_CSR_DIAGONALS serves CSR matrices only - a BSR matrix is not stored by diagonals"
+       error stop
+    end if
     nnzb = row_ptr(n / b + 1) - base
     a%n = n
     a%block_size = b
     a%row_ptr = row_ptr + (1 - base)
     a%col_idx = col_idx(1:nnzb) + int(1 - base, c_int32_t)
     a%values = vals(:, :, 1:nnzb)
-    a%lower = lower /= 0
+    a%lower = iand(lower, DAV_CSR_LOWER) /= 0
   end function bsr_from_c
 
   !> generalized_eigensolver(a_bsr, ...) - block-sparse specific.  max_dim < 0: argument absent; has_b: B given (same block size, base
@@ -315,8 +322,8 @@ contains
     type(davidson_engine), pointer :: eng
     integer :: st
     call c_f_pointer(p, eng)
-    call engine_set_sparse_device(eng, int(which), int(n), rp, col, vals, base=int(base), lower=lower /= 0, &
-         row_ptr_bits=int(rp_bits), col_bits=int(col_bits), stat=st)
+    call engine_set_sparse_device(eng, int(which), int(n), rp, col, vals, base=int(base), lower=iand(lower, DAV_CSR_LOWER) /= 0, &
+         row_ptr_bits=int(rp_bits), col_bits=int(col_bits), stat=st, diagonals=iand(lower, DAV_CSR_DIAGONALS) /= 0)
     stat = int(st, c_int)
   end function fd_engine_set_sparse_device
 
@@ -343,6 +350,11 @@ contains
     type(davidson_engine), pointer :: eng
     integer :: st
     call c_f_pointer(p, eng)
+    if (iand(lower, DAV_CSR_DIAGONALS) /= 0) then          ! the engine refuses the flag by its own message (dav_last_error)
+       stat = dav_set_operator_bsr_dev(eng%h, int(which - 1, c_int), b, rp, rp_bits, col, col_bits, vals, base, lower, &
+            merge(DAV_BSR_ROW_MAJOR, DAV_BSR_COL_MAJOR, row_major /= 0))
+       return
+    end if
     call engine_set_block_sparse_device(eng, int(which), int(n), int(b), rp, col, vals, base=int(base), lower=lower /= 0, &
          row_major=row_major /= 0, row_ptr_bits=int(rp_bits), col_bits=int(col_bits), stat=st)
     stat = int(st, c_int)

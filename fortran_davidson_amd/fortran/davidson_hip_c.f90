@@ -13,6 +13,7 @@ module davidson_hip_c
   integer(c_int), parameter :: DAV_NO_SUCH_ENTRY = 2
   !> dav_set_operator_csr: every nonzero given / only j <= i given (the engine mirrors the strict lower part)
   integer(c_int), parameter :: DAV_CSR_FULL = 0, DAV_CSR_LOWER = 1
+  integer(c_int), parameter :: DAV_CSR_DIAGONALS = 2   ! or-ed to either: the matrix is stored by diagonals
   !> dav_set_operator_bsr: order of the b * b values of one block (C / scipy row-major, Fortran values(b, b, nnzb) column-major)
   integer(c_int), parameter :: DAV_BSR_ROW_MAJOR = 0, DAV_BSR_COL_MAJOR = 1
 

@@ -15,15 +15,18 @@ module davidson_sparse
   !> A symmetric real matrix of order n in CSR form, 1-based: the entries of row i are col_idx / values(row_ptr(i) : row_ptr(i+1) - 1).
   !> lower = .true.: only the entries with column <= row are given (the engine mirrors the strict lower part); .false.: every nonzero
   !> is given, and the matrix being symmetric is the caller's promise, as for a dense matrix.
+  !> diagonals = .true. (DAV_CSR_DIAGONALS): the engine stores the matrix by its diagonals - for stencils, banded and tight-binding
+  !> matrices; it refuses one with too many diagonals for its entries (nd * n > 4 * max(entries, n)), it never falls back to CSR.
   type :: csr_matrix
      integer :: n = 0
      integer(c_int64_t), allocatable :: row_ptr(:)
      integer(c_int32_t), allocatable :: col_idx(:)
      real(dp), allocatable :: values(:)
      logical :: lower = .false.
+     logical :: diagonals = .false.
   end type csr_matrix
 
-  !> csr_matrix(n, row_ptr, col_idx, values [, lower]) from default-kind integer arrays, 1-based
+  !> csr_matrix(n, row_ptr, col_idx, values [, lower] [, diagonals]) from default-kind integer arrays, 1-based
   interface csr_matrix
      module procedure new_csr_matrix
   end interface csr_matrix
@@ -121,11 +124,11 @@ contains
     end if
   end subroutine engine_update_sparse_values_device
 
-  function new_csr_matrix(n, row_ptr, col_idx, values, lower) result(a)
+  function new_csr_matrix(n, row_ptr, col_idx, values, lower, diagonals) result(a)
     integer, intent(in) :: n
     integer, intent(in) :: row_ptr(:), col_idx(:)
     real(dp), intent(in) :: values(:)
-    logical, intent(in), optional :: lower
+    logical, intent(in), optional :: lower, diagonals
     type(csr_matrix) :: a
     if (size(row_ptr) /= n + 1) then
        print *, "csr_matrix: row_ptr must hold n + 1 = ", n + 1, " offsets, not ", size(row_ptr)
@@ -141,6 +144,7 @@ contains
     a%col_idx = int(col_idx, c_int32_t)
     a%values = values
     if (present(lower)) a%lower = lower
+    if (present(diagonals)) a%diagonals = diagonals
   end function new_csr_matrix
 
   !> Operator A (which = 1) or B (which = 2) of the engine from a csr_matrix: the engine keeps the rows of its slab in HBM and applies
@@ -150,17 +154,20 @@ contains
     integer, intent(in) :: which
     type(csr_matrix), intent(in) :: a
     real(dp) :: nothing(1)
+    integer(c_int) :: tri
+    tri = merge(DAV_CSR_LOWER, DAV_CSR_FULL, a%lower)
+    if (a%diagonals) tri = ior(tri, DAV_CSR_DIAGONALS)
     if (a%n /= eng%n .or. .not. allocated(a%row_ptr)) then
        print *, "engine_set_sparse: the matrix must be of order ", eng%n
        error stop
     end if
     if (size(a%values) > 0) then
-       call check_dav(dav_set_operator_csr(eng%h, int(which - 1, c_int), a%row_ptr, a%col_idx, a%values, 1_c_int, &
-            merge(DAV_CSR_LOWER, DAV_CSR_FULL, a%lower)), "dav_set_operator_csr")
+       call check_dav(dav_set_operator_csr(eng%h, int(which - 1, c_int), a%row_ptr, a%col_idx, a%values, 1_c_int, tri), &
+            "dav_set_operator_csr")
     else
        nothing = 0.0_dp
-       call check_dav(dav_set_operator_csr(eng%h, int(which - 1, c_int), a%row_ptr, [0_c_int32_t], nothing, 1_c_int, &
-            merge(DAV_CSR_LOWER, DAV_CSR_FULL, a%lower)), "dav_set_operator_csr")
+       call check_dav(dav_set_operator_csr(eng%h, int(which - 1, c_int), a%row_ptr, [0_c_int32_t], nothing, 1_c_int, tri), &
+            "dav_set_operator_csr")
     end if
     ! a stored matrix: the dense driver's sticky convergence flags, as for engine_set_dense
     if (which == 1) eng%free_semantics = .false.
@@ -172,14 +179,15 @@ contains
   !> entries with column <= row are given; row_ptr_bits / col_bits: 64 (default for row_ptr) or 32 (default for col_idx).  The arrays
   !> must be complete when the call is made (a caller that writes them asynchronously synchronises first) and are free again when it
   !> returns.  stat present: a refused matrix returns its non-zero status here (dav_last_error says why; the operator is left unset),
-  !> otherwise the program stops.
-  subroutine engine_set_sparse_device(eng, which, n, row_ptr, col_idx, vals, base, lower, row_ptr_bits, col_bits, stat)
+  !> otherwise the program stops.  diagonals = .true.: the matrix is stored by its diagonals, as for a csr_matrix with that component.
+  subroutine engine_set_sparse_device(eng, which, n, row_ptr, col_idx, vals, base, lower, row_ptr_bits, col_bits, stat, diagonals)
     type(davidson_engine), intent(inout) :: eng
     integer, intent(in) :: which, n
     type(c_ptr), intent(in) :: row_ptr, col_idx, vals
     integer, intent(in), optional :: base, row_ptr_bits, col_bits
     logical, intent(in), optional :: lower
     integer, intent(out), optional :: stat
+    logical, intent(in), optional :: diagonals
     integer(c_int) :: ib, rb, cb, tri, ierr
     if (n /= eng%n) then
        if (present(stat)) then
@@ -198,6 +206,9 @@ contains
     if (present(col_bits)) cb = int(col_bits, c_int)
     if (present(lower)) then
        if (lower) tri = DAV_CSR_LOWER
+    end if
+    if (present(diagonals)) then
+       if (diagonals) tri = ior(tri, DAV_CSR_DIAGONALS)
     end if
     ierr = dav_set_operator_csr_dev(eng%h, int(which - 1, c_int), row_ptr, rb, col_idx, cb, vals, ib, tri)
     if (present(stat)) then

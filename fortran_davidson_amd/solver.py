@@ -17,7 +17,7 @@ import numpy as np
 
 from ._lib import fortran_lib, hip_lib
 from .engine_c import (CEngine, DavidsonHipError, _device_bsr_tensors, _device_csr_tensors, _dp, _f, _optional, check_bsr, check_csr,
-                       device_bsr_tensors, device_csr_tensors, guess_array, is_torch_bsr, is_torch_csr, torch_bsr_parts, torch_csr_parts,
+                       csr_flag_word, device_bsr_tensors, device_csr_tensors, guess_array, is_torch_bsr, is_torch_csr, torch_bsr_parts, torch_csr_parts,
                        update_values_array)
 
 _METHOD = {"DPR": 0, "GJD": 1, "BDPR": 3}
@@ -151,13 +151,14 @@ def _is_device_csr(a):
 
 
 def generalized_eigensolver_sparse(indptr, indices, data, lowest, method, max_iterations, tolerance, max_dim_sub=None, second=None,
-                                   lower=False, initial_vectors=None):
+                                   lower=False, initial_vectors=None, diagonals=False):
     """`call generalized_eigensolver(a_csr, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters [, max_dim_sub]
     [, b_csr])` (the csr_matrix specific of module davidson) with A in CSR form, 0-based: three arrays, or `indptr` an object with
     .tocsr() and indices = data = None.  `second`: B the same way - a tuple (indptr, indices, data) or an object with .tocsr().  Either
     may also be a torch.sparse_csr_tensor; one on the GPU is built there (DavidsonEngine.set_sparse on the tensor's device).
     lower=True: only the entries with column <= row are given, for A and B.  initial_vectors (n, g): the solve starts from these
-    columns instead of unit vectors.  Returns (eigenvalues, eigenvectors, iters)."""
+    columns instead of unit vectors.  diagonals=True: A and B are stored by their diagonals (csr_matrix(..., diagonals=.true.); a
+    matrix that does not suit the storage is refused).  Returns (eigenvalues, eigenvectors, iters)."""
     _check_bdpr(method, (None, None), where="generalized_eigensolver_sparse")
     _check_cheb(method, True, second is not None, "generalized_eigensolver_sparse")
     a = indptr if indices is None and data is None else (indptr, indices, data)
@@ -166,9 +167,9 @@ def generalized_eigensolver_sparse(indptr, indices, data, lowest, method, max_it
         n = a.shape[0] if hasattr(a, "shape") else len(a[0]) - 1
         device = (a if _is_device_csr(a) else second).device.index
         with DavidsonEngine(n, lowest, max_dim_sub, gev=second is not None, device=device) as eng:
-            eng.set_sparse(1, a, lower=lower)
+            eng.set_sparse(1, a, lower=lower, diagonals=diagonals)
             if second is not None:
-                eng.set_sparse(2, second, lower=lower)
+                eng.set_sparse(2, second, lower=lower, diagonals=diagonals)
             return eng.solve(method, max_iterations, tolerance, initial_vectors=initial_vectors)
     n, rp, ci, vv = _sparse_input(a, None, lower)
     if second is not None:
@@ -181,12 +182,12 @@ def generalized_eigensolver_sparse(indptr, indices, data, lowest, method, max_it
     if initial_vectors is not None:
         x0 = _initial_vectors(initial_vectors, n, lowest)
         fortran_lib().fd_sparse_solve_guess(n, _i64(rp), _i32(ci), _dp(vv), int(second is not None), _i64(rpb), _i32(cib), _dp(vvb), 0,
-                                            int(lower), lowest, _method_code(method), max_iterations, tolerance,
+                                            csr_flag_word(lower, diagonals), lowest, _method_code(method), max_iterations, tolerance,
                                             -1 if max_dim_sub is None else max_dim_sub, x0.shape[1], _dp(x0), _dp(evals), _dp(evecs),
                                             C.byref(iters))
         return evals, evecs, iters.value
-    fortran_lib().fd_sparse_solve(n, _i64(rp), _i32(ci), _dp(vv), int(second is not None), _i64(rpb), _i32(cib), _dp(vvb), 0, int(lower),
-                                  lowest, _method_code(method), max_iterations, tolerance, -1 if max_dim_sub is None else max_dim_sub,
+    fortran_lib().fd_sparse_solve(n, _i64(rp), _i32(ci), _dp(vv), int(second is not None), _i64(rpb), _i32(cib), _dp(vvb), 0,
+                                  csr_flag_word(lower, diagonals), lowest, _method_code(method), max_iterations, tolerance, -1 if max_dim_sub is None else max_dim_sub,
                                   _dp(evals), _dp(evecs), C.byref(iters))
     return evals, evecs, iters.value
 
@@ -342,29 +343,31 @@ class DavidsonEngine:
         self._kept.pop(which, None)
         self.lib.fd_engine_keep_value_map(self.p, which, int(keep_map))
 
-    def set_sparse(self, which, indptr, indices=None, data=None, lower=False, keep_map=False):
+    def set_sparse(self, which, indptr, indices=None, data=None, lower=False, keep_map=False, diagonals=False):
         """Operator A (which=1) or B (which=2) as a symmetric matrix in CSR form, 0-based (Fortran: engine_set_sparse): three arrays,
         or `indptr` an object with .tocsr(), or a torch.sparse_csr_tensor - one on the engine's GPU is built there (Fortran:
         engine_set_sparse_device; a refused matrix raises DavidsonHipError and leaves the operator unset).  lower=True: only the
         entries with column <= row are given.  keep_map=True: the operator also keeps where its values came from (Fortran:
-        engine_keep_value_map), so that update_values can replace them on the kept pattern."""
+        engine_keep_value_map), so that update_values can replace them on the kept pattern.  diagonals=True: the matrix is stored by
+        its diagonals (csr_matrix(..., diagonals=.true.)) - for stencils and banded matrices, also a scipy dia_matrix, for which the
+        keyword stays explicit; a matrix with too many diagonals for its entries is refused (DavidsonHipError), never stored as CSR."""
         a = indptr if indices is None and data is None else (indptr, indices, data)
         if _is_device_csr(a):
-            return self._set_sparse_device(which, *torch_csr_parts(a), lower=lower, keep_map=keep_map)
+            return self._set_sparse_device(which, *torch_csr_parts(a), lower=lower, keep_map=keep_map, diagonals=diagonals)
         _, rp, ci, vv = _sparse_input(a, self.n, lower)
         self._keep_map(which, keep_map)
-        self.lib.fd_engine_set_sparse(self.p, which, self.n, _i64(rp), _i32(ci), _dp(vv), 0, int(lower))
+        self.lib.fd_engine_set_sparse(self.p, which, self.n, _i64(rp), _i32(ci), _dp(vv), 0, csr_flag_word(lower, diagonals))
         self._note_blocks(which, None, sparse=True)
         if keep_map:
             self._kept[which] = {"count": int(rp[-1] - rp[0]), "b": 1, "fortran_blocks": False}
 
-    def _set_sparse_device(self, which, row_ptr, col_idx, vals, lower=False, keep_map=False):
+    def _set_sparse_device(self, which, row_ptr, col_idx, vals, lower=False, keep_map=False, diagonals=False):
         rpb, cib, nnz = _device_csr_tensors(row_ptr, col_idx, vals, self.n, self.device)
         self._keep_map(which, keep_map)
         import torch
         torch.cuda.current_stream(row_ptr.device).synchronize()
         st = self.lib.fd_engine_set_sparse_device(self.p, which, self.n, row_ptr.data_ptr(), rpb, col_idx.data_ptr() or None, cib,
-                                                  vals.data_ptr() or None, 0, int(lower))
+                                                  vals.data_ptr() or None, 0, csr_flag_word(lower, diagonals))
         if st != 0:
             raise DavidsonHipError(hip_lib().dav_last_error().decode())
         self._note_blocks(which, None, sparse=True)

@@ -242,8 +242,29 @@ int dav_set_operator_device(dav_handle_t h, int which, dav_device_apply_fn fn, v
  * dav_get_diagonal.  Device storage per rank: int64 row offsets, int32 columns, fp64 values, released when the operator is set again and
  * at dav_destroy.  The block product is the engine's own kernel and bitwise reproducible: the same bits for every rank count and every
  * repetition (not necessarily for another block width).  The sweeps inside the GJD correction solve stay fp64 on a CSR operator
- * (dav_set_inner_precision(32) does not apply to it).  The caller's arrays are not referenced after the call returns. */
-enum { DAV_CSR_FULL = 0, DAV_CSR_LOWER = 1 };
+ * (dav_set_inner_precision(32) does not apply to it).  The caller's arrays are not referenced after the call returns.
+ *
+ * triangle is a small flag word: DAV_CSR_FULL or DAV_CSR_LOWER, with DAV_CSR_DIAGONALS or-ed to either (0..3; purely additive within ABI
+ * 109 - without the flag a set call builds, stores and computes bit for bit what it did).  DAV_CSR_DIAGONALS asks for STORAGE BY
+ * DIAGONALS, for finite-difference Laplacians, stencils, banded and tight-binding matrices whose entries lie on a handful of diagonals:
+ * input, validation, messages and canonical form are those of the entry called; from the canonical matrix the engine takes the nd
+ * distinct offsets column - row of the WHOLE matrix (from the global arrays: every rank reaches the same set without a collective) and
+ * keeps, per rank, the sorted offsets (int32) and val[d][local row] in fp64 with every diagonal 128-byte aligned.  A slot with no stored
+ * entry, or whose column falls outside [0, n), holds +0.0; duplicate entries of one position are ADDED into their slot at build time, from
+ * +0.0 in canonical order (the CSR storage keeps them as separate terms).  A fill slot is multiplied like any other: a non-finite entry of
+ * X can reach rows whose stored pattern does not touch it (0 * inf = NaN).  ELIGIBILITY, a design constant: the matrix is stored by
+ * diagonals when  nd * n <= DIA_MAX_FILL * max(entries of the canonical matrix, n)  with DIA_MAX_FILL = 4 - at most 32 stored bytes per
+ * entry against CSR's 12; beyond that the format reads more than it saves.  Otherwise the call is refused (dav_last_error names nd, the
+ * entry count and the rule) before any storage by diagonals is allocated, the operator is left UNSET and the engine usable; there is no
+ * silent fall-back to CSR.  The product (one accumulator per row and column, the diagonals in ascending offset from +0.0) is bitwise
+ * reproducible for every rank count, repetition AND block width.  The diagonal, dav_init_basis, the corrections DPR / GJD / CHEB (with its
+ * fused step) work as for CSR; BDPR refuses it.  Statistics: apply_bytes = 8 nd nloc + 4 nd + 8 N k + 8 nloc k (plus the epilogue's reads
+ * of a fused CHEB step), apply_flops = 2 k x the canonical entries of this rank (the useful work, comparable with CSR's figure).  Device
+ * storage per rank: 4 nd + 8 nd roundup(nloc, 16) bytes; the canonical CSR arrays are released once the diagonals are filled - except
+ * after dav_keep_value_map(h, which, 1), which keeps them and the maps for dav_update_operator_values(_dev): the memory is then that of
+ * the CSR operator with its map PLUS 8 nd nloc bytes; an update runs the CSR refresh, fills the diagonals again and equals bit for bit
+ * a fresh set call with DAV_CSR_DIAGONALS.  The two BSR entries refuse the flag. */
+enum { DAV_CSR_FULL = 0, DAV_CSR_LOWER = 1, DAV_CSR_DIAGONALS = 2 /* or-ed to either */ };
 int dav_set_operator_csr(dav_handle_t h, int which, const int64_t* row_ptr /* n+1 */, const int32_t* col_idx, const double* vals,
                          int index_base /* 0 or 1 */, int triangle);
 /* The same matrix from DEVICE arrays, built on the GPU by the engine's own kernels.  Purely additive within ABI 109.  The arguments mean
