@@ -530,6 +530,7 @@ extern "C" int dav_destroy(dav_handle_t e) {
   lt.lap("arenas");
   pool_free(e->gjd_ws);
   pool_free(e->cheb_ws);
+  pool_free(e->lanczos_ws);
   ingest_release(e);
   shm_release(e);
   pool_free(e->sym_slab);
@@ -574,6 +575,7 @@ extern "C" int dav_destroy(dav_handle_t e) {
     pool_free(e->op[w].e_table);
     pool_free(e->op[w].l2_table);
     pool_free(e->op[w].dadd_table);
+    pool_free(e->op[w].lbound);
     sparse_release(e, e->op[w]);
   }
   lt.lap("operators");

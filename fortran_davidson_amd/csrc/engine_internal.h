@@ -193,6 +193,11 @@ struct OpDesc {
   // DAV_KIND_DEVICE: the caller's own block apply on device memory (dav_set_operator_device)
   dav_device_apply_fn dev_fn = nullptr;
   void* dev_ctx = nullptr;
+  // operator A of any kind the engine applies on the device, built at the first DAV_METHOD_LCHEB correction (engine_cheb.hip): the Lanczos
+  // bound, in every one of the nranks slots cheb_coef reads.  Stale after a set call on the slot, new values of a sparse operator and
+  // streamed rows of a dense one; released with the engine
+  double* lbound = nullptr;
+  bool lbound_valid = false;
   SparseStore sp;            // DAV_KIND_CSR / DAV_KIND_BSR / DAV_KIND_DIA
 };
 
@@ -279,6 +284,7 @@ struct dav_engine {
   unsigned* counters = nullptr;   // zeroed words of the last-workgroup finishes: [0, GRAM_MAX_COUNTERS) Gram tiles, [GRAM_MAX_COUNTERS] the panel norms
   double* gjd_ws = nullptr;       // GJD inner-solver workspace (lazy)
   double* cheb_ws = nullptr;      // Chebyshev correction (engine_cheb.hip, lazy): three column blocks of the GJD workspace's width, then the coefficients
+  double* lanczos_ws = nullptr;   // Lanczos bound of DAV_METHOD_LCHEB (lazy): two columns, nranks slots, the partials of a dot product
   int storage = 0;                // storage mode for dense operators set after dav_set_storage
   int sym_nb = 0;                 // symmetric-tiled sweep: block rows of the whole matrix
   SymSet sym;                     // work lists over the block rows this rank stores (or generates)
@@ -392,7 +398,9 @@ struct Watchdog {
 
 // the method of a method code: the Chebyshev correction keeps its degree above the low byte (bits 8..15, 0 = the default), every other
 // code is its own method.  Every comparison of a method code goes through this.
-static inline int method_kind(int code) { return code > 0 && (code & 0xff) == DAV_METHOD_CHEB ? DAV_METHOD_CHEB : code; }
+static inline int method_kind(int code) {
+  return code > 0 && ((code & 0xff) == DAV_METHOD_CHEB || (code & 0xff) == DAV_METHOD_LCHEB) ? code & 0xff : code;
+}
 static inline int64_t roundup(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // several small matrices in ONE staging buffer and ONE host-to-device copy (each H2D command costs
@@ -506,4 +514,6 @@ void bdpr_correct(E* e, int m, int ncorr, const double* theta_dev);
 // ---- engine_cheb.hip -------------------------------------------------------------------------------------
 int cheb_prepare(E* e, int degree);
 int cheb_correct(E* e, int m, int ncorr, int lowest, int degree, const double* theta_dev);
+int lcheb_prepare(E* e, int degree);
+int lcheb_correct(E* e, int m, int ncorr, int lowest, int degree, const double* theta_dev);
 #pragma GCC visibility pop

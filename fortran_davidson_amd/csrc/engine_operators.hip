@@ -254,6 +254,7 @@ int operator_goes(E* e, int which, bool unset) {
   sym_resident_release(o);
   sparse_release(e, o);
   o.res_decided = false;
+  o.lbound_valid = false;    // the Lanczos bound of an LCHEB correction belongs to the definition that goes
   if (unset) {
     o.kind = DAV_KIND_NONE;
     e->diag_host[which].clear();
@@ -433,6 +434,7 @@ int ingest_commit(E* e, int64_t row0, int64_t nrows) {
   if (nrows == 0) return 0;
   CHK(bind(e));
   OpDesc& o = e->op[e->ing_which];
+  o.lbound_valid = false;    // new rows: the Lanczos bound of an LCHEB correction is built again
   int b = e->ing_flip;
   HIPCHK(hipMemcpyAsync(e->ing_dev[b], e->ing_host[b], sizeof(double) * (size_t)(nrows * e->n), hipMemcpyHostToDevice, e->stream));
   launch_rows_scatter(e->stream, e->ing_dev[b], e->n, row0, nrows, e->n, o.a, e->nloc_pad, e->row0, e->nloc, o.storage == 1, e->sym.row_off);
@@ -482,6 +484,7 @@ extern "C" int dav_dense_end(dav_handle_t e, int which) {
   if (e->ing_which != which) return fail("dav_dense_end: no streaming upload open for this operator");
   CHK(bind(e));
   OpDesc& o = e->op[which];
+  o.lbound_valid = false;
   int rc = 0;
   if (o.storage == 1) rc = sym_diag(e, o);
   else launch_diag_dense(e->stream, o.a, e->nloc_pad, e->row0, e->nloc, o.diag);

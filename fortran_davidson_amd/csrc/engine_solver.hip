@@ -285,15 +285,16 @@ int ritz_impl(E* e, int m, int ncorr, int lowest, const double* Y, int64_t ldy, 
   CHK(bind(e));
   // the code of the Chebyshev correction carries its degree in bits 8..15 (0 = the default); every other code is its own low byte
   const int method = method_kind(method_code);
-  const bool cheb = method == DAV_METHOD_CHEB;
-  const int cheb_degree = cheb && (method_code >> 8) != 0 ? method_code >> 8 : CHEB_DEFAULT_DEGREE;     // checked by cheb_prepare
+  const bool cheb = method == DAV_METHOD_CHEB, lcheb = method == DAV_METHOD_LCHEB;
+  const int cheb_degree = (cheb || lcheb) && (method_code >> 8) != 0 ? method_code >> 8 : CHEB_DEFAULT_DEGREE;     // checked by cheb_prepare / lcheb_prepare
   const bool dev = Y == nullptr;
   if (m <= 0 || lowest <= 0 || lowest > ncorr || ncorr > m || (!dev && ldy < m)) return fail("dav_ritz_residual_correction: bad shape");
   const bool bdpr = method == DAV_METHOD_BDPR;
-  if ((method == DAV_METHOD_DPR || bdpr || cheb) && m + ncorr > e->cols_alloc) return fail("basis panel too narrow for the correction block");
+  if ((method == DAV_METHOD_DPR || bdpr || cheb || lcheb) && m + ncorr > e->cols_alloc) return fail("basis panel too narrow for the correction block");
   CHK(check_panel(e, DAV_PANEL_V, 0, m));
   if (bdpr) CHK(bdpr_prepare(e));            // the method's contract, before any panel is written
   if (cheb) CHK(cheb_prepare(e, cheb_degree));
+  if (lcheb) CHK(lcheb_prepare(e, cheb_degree));      // ... and, while the bound of A is stale, the Lanczos run: before the phase's event pair opens
   const double *dY, *dY2, *dTheta;
   int64_t ldm_y, ldm_y2;
   std::vector<double> y2;
@@ -342,11 +343,12 @@ int ritz_impl(E* e, int m, int ncorr, int lowest, const double* Y, int64_t ldy, 
   r.pin = e->tune.pg_pin;
   launch_panel_gemm(e->stream, r);
   if (bdpr) bdpr_correct(e, m, ncorr, dTheta);       // T = blocksolve(R) into V[:, m:m+ncorr]
-  if (cheb) {
+  if (cheb || lcheb) {
     // T = z_d by d - 1 block products into V[:, m:m+ncorr].  Every product is timed like any apply; the phase's own pair is closed
     // around them, because event pairs are collected only while none is open and a correction of a high degree has more than fit
     CHK(timed_end(e, slot));
-    CHK(cheb_correct(e, m, ncorr, lowest, cheb_degree, dTheta));
+    if (cheb) CHK(cheb_correct(e, m, ncorr, lowest, cheb_degree, dTheta));
+    else CHK(lcheb_correct(e, m, ncorr, lowest, cheb_degree, dTheta));
     CHK(timed_begin(e, 2, 0, &slot));
   }
   if (!fuse_norms) launch_norm_finish(e->stream, e->norm_partial, (int)(e->nloc_pad / PG_ROWS), lowest, result_target(e));

@@ -754,6 +754,7 @@ int update_from_device(E* e, int which, const char* name, BuildScratch& sc, cons
   if (o.kind == DAV_KIND_DIA) dia_fill(e, s);        // the slots follow the values, as the set call filled them
   o.sp.bdiag_valid = false;          // the diagonal blocks of a BDPR correction follow the values: rebuilt at the next one
   o.sp.rbound_valid = false;         // ... and the row-sum bound of a CHEB correction
+  o.lbound_valid = false;            // ... and the Lanczos bound of an LCHEB correction
   launch_sparse_refresh_diag(st, s.b, s.doff, s.dpos, vals, e->n, diag);
   if (e->nloc > 0) HIPCHK(hipMemcpyAsync(o.diag, diag + e->row0, sizeof(double) * e->nloc, hipMemcpyDeviceToDevice, st));
   // what depends on the numbers: the diagonal on the host and the start-vector order of A

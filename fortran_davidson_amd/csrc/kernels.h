@@ -372,3 +372,18 @@ void launch_cheb_coef(hipStream_t st, const double* theta, int ncorr, int lowest
 // nrows_pad) are written as +0.0.  k = 0: out = alpha_0 r (az, z, zprev not read).  zprev == nullptr: not read.  out may be zprev.
 void launch_cheb_step(hipStream_t st, int k, const double* coef, int pstride, const double* az, const double* z, const double* r, const double* zprev,
                       double* out, int64_t ld, int ncols, int64_t nloc, int64_t nrows_pad);
+
+// ---- k_lanczos.hip: the vector work of the Lanczos bound (DAV_METHOD_LCHEB; engine_cheb.hip) ---------------------------------------------
+constexpr int LANCZOS_STEPS = 12;
+// Each launch leaves the sum of its dot product over this rank's rows in slots[rank] and +0.0 in slots[p] of the other p < nranks; partial:
+// lanczos_partials(nrows_pad) doubles, one per workgroup.  Vectors: nrows_pad doubles (even), rows [nloc, nrows_pad) are written as +0.0.
+int lanczos_partials(int64_t nrows_pad);
+// u[i] = (splitmix64(row0 + i + 1) >> 11) * 2^-52 - 1;  <u, u>
+void launch_lanczos_start(hipStream_t st, double* u, int64_t row0, int64_t nloc, int64_t nrows_pad, double* partial, double* slots, int rank,
+                          int nranks);
+// v = u / nrm over u,  w = au / nrm - beta * vprev over au (vprev == nullptr: not read);  <v, w>
+void launch_lanczos_first(hipStream_t st, double* u, double* au, const double* vprev, double nrm, double beta, int64_t nloc, int64_t nrows_pad,
+                          double* partial, double* slots, int rank, int nranks);
+// w -= alpha * v;  <w, w>
+void launch_lanczos_second(hipStream_t st, double* w, const double* v, double alpha, int64_t nloc, int64_t nrows_pad, double* partial,
+                           double* slots, int rank, int nranks);

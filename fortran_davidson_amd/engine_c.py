@@ -21,6 +21,14 @@ def method_cheb(degree=0):
     return METHOD_CHEB | (int(degree) << 8)
 
 
+METHOD_LCHEB = 5         # the same correction with a Lanczos bound, for any operator applied on the device (DAV_METHOD_LCHEB)
+
+
+def method_lcheb(degree=0):
+    """the method code of the Chebyshev correction with a Lanczos bound (the header's DAV_METHOD_LCHEB_DEGREE), as method_cheb"""
+    return METHOD_LCHEB | (int(degree) << 8)
+
+
 # int fn(ctx, hip_stream, n, row0, nloc, k, x_dev, ldx, y_dev, ldy) - include/davidson_hip.h: dav_device_apply_fn
 DEVICE_APPLY_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64)
 

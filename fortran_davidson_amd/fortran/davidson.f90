@@ -194,10 +194,13 @@ contains
           ! "CHEB" / "CHEB<degree>": the Chebyshev-filtered correction for CSR / BSR operators (opt-in, not in the reference).  Like BDPR
           ! its block comes out of the Ritz phase, so it takes the DPR side below; the engine refuses what the method does not serve
           meth = cheb_method_code(trim(method))
+          ! "LCHEB" / "LCHEB<degree>": the same correction with a Lanczos bound, for any operator the engine applies on the device
+          if (meth < 0) meth = lcheb_method_code(trim(method))
           if (meth < 0) then
              ! the reference leaves the correction undefined here (src/davidson.f90:656-669)
              print *, "generalized_eigensolver: unknown correction method '", trim(method), "' (DPR, GJD or BDPR)", &
-                  ", or CHEB / CHEB<degree 1..64>"
+                  ", or CHEB / CHEB<degree 1..64>", &
+                  ", or LCHEB / LCHEB<degree 1..64>"
              error stop
           end if
        end select
@@ -350,7 +353,8 @@ contains
        if (drr) then
           ! 3 + 4 on the device: eigenpairs of the device-resident projected matrices, then the same fused phase from
           ! where they lie; one synchronisation brings back the Ritz values, the residual norms and the Gram blocks
-          if (phase == DAV_METHOD_DPR .or. phase == DAV_METHOD_BDPR .or. method_kind(phase) == DAV_METHOD_CHEB) then
+          if (phase == DAV_METHOD_DPR .or. phase == DAV_METHOD_BDPR .or. method_kind(phase) == DAV_METHOD_CHEB &
+               .or. method_kind(phase) == DAV_METHOD_LCHEB) then
              if (allocated(c_pre)) deallocate(c_pre, g_pre)
              allocate(c_pre(m, ncorr), g_pre(ncorr, ncorr))
              call check_dav(dav_rr_ritz(h, int(m, c_int), int(ncorr, c_int), int(lowest, c_int), int(phase, c_int), theta, &
@@ -369,7 +373,7 @@ contains
                "dav_ritz_residual_correction")
           have_pre = .true.
        else
-          ! (BDPR and CHEB too: the entry above has no method argument; the first Gram pass is then made by the orthonormalisation, as for GJD)
+          ! (BDPR, CHEB and LCHEB too: the entry above has no method argument; the first Gram pass is then made by the orthonormalisation, as for GJD)
           call check_dav(dav_ritz_residual_correction_n(h, int(m, c_int), int(ncorr, c_int), int(lowest, c_int), y, &
                int(m, c_int64_t), theta, int(phase, c_int), errors), "dav_ritz_residual_correction")
        end if

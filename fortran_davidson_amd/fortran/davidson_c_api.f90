@@ -37,12 +37,17 @@ contains
   end function method_name
 
   !> what the doors hand to generalized_eigensolver: method_name, and behind "CHEB" the degree of bits 8.. of the code ("CHEB16"; none =
-  !> the default degree).  A degree the driver does not take (outside 1..64) makes a name it does not know.
+  !> the default degree).  A degree the driver does not take (outside 1..64) makes a name it does not know.  Low byte 5 is "LCHEB", the
+  !> same correction with a Lanczos bound, and carries its degree the same way ("LCHEB16").
   function method_label(code) result(label)
     integer(c_int), intent(in) :: code
     character(len=12) :: label
     label = method_name(code)
     if (label == "CHEB" .and. ishft(code, -8) /= 0) write (label(5:12), "(i0)") ishft(code, -8)
+    if (code > 3 .and. iand(code, 255) == 5) then
+       label = "LCHEB"
+       if (ishft(code, -8) /= 0) write (label(6:12), "(i0)") ishft(code, -8)
+    end if
   end function method_label
 
   !> generalized_eigensolver(matrix, ...) - dense specific.  max_dim < 0: argument absent.

@@ -57,10 +57,41 @@ def _cheb_degree(method):
     return int(tail)
 
 
+def _lcheb_degree(method):
+    """the degree of method "LCHEB" / "LCHEB<d>" (0 = the default), None when `method` is not such a string.  ValueError: a degree
+    outside 1..64, as _cheb_degree"""
+    if not isinstance(method, str) or not method.startswith("LCHEB"):
+        return None
+    tail = method[5:]
+    if tail == "":
+        return 0
+    if not (tail.isascii() and tail.isdigit()) or not 1 <= int(tail) <= 64:
+        raise ValueError(f"method {method!r}: the degree of the Chebyshev correction is 'LCHEB' (default) or 'LCHEB<d>' with 1 <= d <= 64")
+    return int(tail)
+
+
 def _method_code(method):
-    """the integer the doors take: _METHOD's, or 4 | degree << 8 for "CHEB" / "CHEB<d>" (engine_c.method_cheb); unknown names: 2"""
+    """the integer the doors take: _METHOD's, or 4 | degree << 8 for "CHEB" / "CHEB<d>" (engine_c.method_cheb), 5 | degree << 8 for
+    "LCHEB" / "LCHEB<d>" (engine_c.method_lcheb); unknown names: 2"""
+    d = _lcheb_degree(method)
+    if d is not None:
+        return 5 | (d << 8)
     d = _cheb_degree(method)
     return _METHOD.get(method, 2) if d is None else 4 | (d << 8)
+
+
+def _check_lcheb(method, gev=False, host_callbacks=False, where="generalized_eigensolver"):
+    """method "LCHEB" / "LCHEB<d>" (Chebyshev-filtered correction with a Lanczos bound) serves standard problems whose operator A the
+    engine applies on the device - every kind but a host callback.  The engine refuses anything else at the first correction and the
+    Fortran doors stop the process on an engine error, so the front ends refuse here (ValueError), before any engine call."""
+    if _lcheb_degree(method) is None:
+        return
+    if host_callbacks:
+        raise ValueError(f"{where}: method {method!r} needs an operator A the engine applies on the device; host callbacks are not "
+                         "served (DavidsonEngine.set_device_operator takes a device callback)")
+    if gev:
+        raise ValueError(f"{where}: method {method!r} serves standard problems only (the filter of a generalized problem would need "
+                         "the inverse of B)")
 
 
 def _check_cheb(method, sparse_a, gev=False, where="generalized_eigensolver"):
@@ -102,6 +133,7 @@ def generalized_eigensolver(matrix, lowest, method, max_iterations, tolerance, m
     """initial_vectors (n, g): the solve starts from these columns instead of unit vectors (Fortran: initial_vectors=)."""
     _check_bdpr(method, (None, None))
     _check_cheb(method, False)
+    _check_lcheb(method, second_matrix is not None)
     lib = fortran_lib()
     iters = C.c_int(-1)
     evals = np.zeros(lowest)
@@ -161,6 +193,7 @@ def generalized_eigensolver_sparse(indptr, indices, data, lowest, method, max_it
     matrix that does not suit the storage is refused).  Returns (eigenvalues, eigenvectors, iters)."""
     _check_bdpr(method, (None, None), where="generalized_eigensolver_sparse")
     _check_cheb(method, True, second is not None, "generalized_eigensolver_sparse")
+    _check_lcheb(method, second is not None, where="generalized_eigensolver_sparse")
     a = indptr if indices is None and data is None else (indptr, indices, data)
     if _is_device_csr(a) or _is_device_csr(second):
         # a matrix in device memory: an engine of its own, built on the GPU (DavidsonEngine.set_sparse)
@@ -223,6 +256,7 @@ def generalized_eigensolver_bsr(indptr, indices, data, lowest, method, max_itera
     for A and B.  n: the order (default: block rows x b).  initial_vectors (n, g): the solve starts from these columns instead of unit
     vectors.  Returns (eigenvalues, eigenvectors, iters)."""
     _check_cheb(method, True, second is not None, "generalized_eigensolver_bsr")
+    _check_lcheb(method, second is not None, where="generalized_eigensolver_bsr")
     a = indptr if indices is None and data is None else (indptr, indices, data)
     if _is_device_bsr(a) or _is_device_bsr(second):
         # a matrix in device memory: an engine of its own, built on the GPU (DavidsonEngine.set_block_sparse)
@@ -266,6 +300,7 @@ def generalized_eigensolver_free(fun_matrix_gemv, n, lowest, method, max_iterati
     """Matrix-free specific with numpy callbacks X(n,k) -> Y(n,k) (reference: src/davidson.f90:277-337).  initial_vectors (n, g): the
     solve starts from these columns instead of unit vectors."""
     _check_cheb(method, False, where="generalized_eigensolver_free")
+    _check_lcheb(method, True, True, "generalized_eigensolver_free")
     lib = fortran_lib()
 
     def wrap(fn):
@@ -503,7 +538,11 @@ class DavidsonEngine:
         starts from the previous solve's Ritz vectors when they are still in place.  method "BDPR": the block-diagonal form of DPR,
         for operators set with set_block_sparse (ValueError otherwise, before the engine is called).  method "CHEB" / "CHEB<d>": the
         Chebyshev-filtered correction of degree d (1..64, default 10) for a standard problem whose A was set with set_sparse or
-        set_block_sparse (ValueError otherwise, before the engine is called)."""
+        set_block_sparse (ValueError otherwise, before the engine is called).  method "LCHEB" / "LCHEB<d>": the same correction with
+        a Lanczos bound, for a standard problem whose A is anything the engine applies on the device - set_dense, set_device_operator,
+        set_hashed_operator, set_sparse, set_block_sparse ... (a generalized problem: ValueError before the engine is called)."""
+        if _lcheb_degree(method) is not None:
+            _check_lcheb(method, self.gev, where="DavidsonEngine.solve")
         if _cheb_degree(method) is not None:
             _check_cheb(method, getattr(self, "_sparse", [False, False])[0], self.gev, "DavidsonEngine.solve")
         if method == "BDPR":

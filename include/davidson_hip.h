@@ -71,6 +71,27 @@ enum { DAV_METHOD_DPR = 0, DAV_METHOD_GJD = 1,
  * dav_ritz_residual_correction_g has no method argument and stays DPR; dav_rr_ritz takes the method with C / G. */
 enum { DAV_METHOD_CHEB = 4 };
 #define DAV_METHOD_CHEB_DEGREE(d) (4 | ((d) << 8))
+/* The same correction for ANY operator A the engine applies on the device (opt-in, not in the reference; purely additive within ABI 109): a
+ * dense matrix in either storage, a generated operator (hashed, harness), the identity, a device callback (dav_set_operator_device: a
+ * stencil has a constant diagonal, where DPR degenerates), CSR, BSR, DIA.  The degree rides in bits 8..15 as for DAV_METHOD_CHEB; recurrence,
+ * interval rule and the +0.0 block of a degenerate interval are those of DAV_METHOD_CHEB word for word - only b differs: instead of the row
+ * sum of stored entries it is a Lanczos bound, needing nothing but products with A.  j = min(12, n) steps of the three-term recurrence
+ * without reorthogonalisation from the start vector u[g] = (splitmix64(g + 1) >> 11) * 2^-52 - 1 of the global row g (in [-1, 1), the same
+ * for any number of ranks), normalised:  w = A v - beta v_prev, alpha = <v, w>, w -= alpha v, beta = |w|, v_next = w / beta (the product is
+ * taken of the unnormalised w and divided by beta afterwards); stopped early once beta <= 1e-12 max|alpha|.  With alpha_0.., beta_0.. of the
+ * k steps made, b = max_i (alpha_i + beta_{i-1} + beta_i) + beta_{k-1}, beta_{-1} = 0 and beta_{k-1} left out of the last row: Gershgorin
+ * on the tridiagonal matrix plus the last beta, which is at least the safeguarded bound of Zhou & Li (2011) and needs no eigensolver.  It
+ * is an estimate that was never seen below lambda_max (1.25 .. 1.46 times above it on the test matrices), not a proof, and it is looser
+ * than the row sum where one can be had.  The scalars live on the host; a dot product is the sum of per-workgroup partials in fixed order
+ * and the engine's all-reduce, added in rank order: every rank of a run holds the same bits.  Runs on different rank counts agree to
+ * rounding, not to bits.  The bound is kept with operator A: built at the first such correction - twelve one-column products, counted in
+ * dav_stats like any apply -, built again after any set call on slot A, dav_update_operator_values(_dev), dav_dense_put_rows and
+ * dav_dense_end.  A device callback makes it stale only at its set call: the caller promises a fixed operator.  CONTRACT, refused
+ * (non-zero, dav_last_error starts with "LCHEB correction: ", every panel as it was): a generalized problem; an operator A that is not set or
+ * is a host callback; a degree outside 1..64; no memory for the workspace (three column blocks and two columns).  The fused step of CSR /
+ * DIA operators (DAV_CHEB_FUSE) is kept; every other kind runs the step as a launch of its own. */
+enum { DAV_METHOD_LCHEB = 5 };
+#define DAV_METHOD_LCHEB_DEGREE(d) (5 | ((d) << 8))
 
 typedef struct dav_stats {
   int64_t n;               /* global order                                                          */
