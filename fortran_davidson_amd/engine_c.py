@@ -663,6 +663,47 @@ class CEngine:
         self._chk(self.lib.dav_ritz_residual_correction(self.h, m, lowest, _dp(Y), Y.shape[0], _dp(theta), method, _dp(res)))
         return res
 
+    def ritz_residual_correction_n(self, m, ncorr, lowest, Y, theta, method=METHOD_DPR):
+        """dav_ritz_residual_correction_n: corrections / residues for the first ncorr Ritz pairs, norms of the first `lowest`"""
+        Y = _f(Y)
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        res = np.zeros(lowest)
+        self._chk(self.lib.dav_ritz_residual_correction_n(self.h, m, ncorr, lowest, _dp(Y), Y.shape[0], _dp(theta), method, _dp(res)))
+        return res
+
+    def ritz_residual_correction_g(self, m, ncorr, lowest, Y, theta):
+        """dav_ritz_residual_correction_g: the DPR phase with (resnorm, C = V^T T, G = T^T T) of the new block in the same fetch"""
+        Y = _f(Y)
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        res = np.zeros(lowest)
+        Cm, G = np.zeros((m, ncorr), order="F"), np.zeros((ncorr, ncorr), order="F")
+        self._chk(self.lib.dav_ritz_residual_correction_g(self.h, m, ncorr, lowest, _dp(Y), Y.shape[0], _dp(theta), _dp(res), _dp(Cm), m,
+                                                          _dp(G), ncorr))
+        return res, Cm, G
+
+    def set_lazy_ritz_vectors(self, on=True):
+        """dav_set_lazy_ritz_vectors: while on, the Ritz phases write X only for GJD; ritz_vectors makes it on demand"""
+        self._chk(self.lib.dav_set_lazy_ritz_vectors(self.h, int(on)))
+
+    def ritz_vectors(self, m, nx, Y):
+        """dav_ritz_vectors: X[:, :nx] = V[:, :m] Y[:, :nx]"""
+        Y = _f(Y)
+        self._chk(self.lib.dav_ritz_vectors(self.h, m, nx, _dp(Y), Y.shape[0]))
+
+    def panel_select(self, panel, c0, sel):
+        """dav_panel_select: column c0 + i of the panel <- column c0 + sel[i] (ascending indices, sel[i] >= i)"""
+        s = np.ascontiguousarray(sel, dtype=np.int32)
+        self._chk(self.lib.dav_panel_select(self.h, panel, c0, s.size, s.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def gjd_correction_steps(self, mbasis, ncols, theta, steps):
+        """dav_gjd_correction_n with inner_tol = 0 and no per-column tolerances: every column that starts takes `steps` inner steps
+        (unless it breaks down).  T lands in V[:, mbasis:mbasis + ncols]; returns the steps taken."""
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        assert theta.size >= ncols
+        it = C.c_int(-1)
+        self._chk(self.lib.dav_gjd_correction_n(self.h, mbasis, ncols, _dp(theta), steps, 0.0, None, C.byref(it)))
+        return it.value
+
     def gjd_correction(self, m, theta, max_inner=500, inner_tol=1e-12):
         theta = np.ascontiguousarray(theta, dtype=np.float64)
         it = C.c_int(0)

@@ -1,5 +1,6 @@
 """Inputs whose block products are exact, their references, and the write fences around one apply - shared by
-tests/test_exact_products_gpu.py.
+tests/test_exact_products_gpu.py; behind them the integer inputs, references and the numpy restatement of the GJD correction that
+tests/test_exact_phases_gpu.py holds the other phases of an outer iteration to (tests/test_exact_phase_inputs_cpu.py checks those).
 
 Exact-integer design: symmetric integer A with |a| <= 255 (exact in fp32 too), integer X with |x| < 2^28, most entries odd and above
 2^24 (not representable in fp32), n < 2^17.  Every partial sum of A X in any order is an integer below 2^53, so every schedule, rank
@@ -153,3 +154,205 @@ def run_ranks(nranks, make, work, timeout=300):
         e.close()
     assert all(x is None for x in err), err
     return out
+
+
+# ---- the phases of an outer iteration besides the block products (tests/test_exact_phases_gpu.py) ------------------------------------
+# Exact-integer design of parts A - C: every panel holds integers, every small matrix the host builds from the caller's (-Y theta,
+# -C M) is an exact integer product, and every partial sum of a panel product stays below 2^53 (test_exact_phase_inputs_cpu.py checks
+# the bounds on the generated inputs), so any order of summation, with or without FMA, returns the integer result bit for bit.
+#   wide:   panels from int_block(bits=20), |y| <= 7, integer 1 <= |theta| <= 8:  |X| < 128 2^20 7 < 2^30, |R| <= 128 2^20 63 < 2^33
+#   narrow: panels from unit_block, |y| <= 3, theta in {+-1, +-2}:  |R| <= 128 (3 + 6) = 1152, R^2 < 2^22, and with n < 2^14 the squared
+#           norms are exact integers below 2^36 - the host's one sqrt of them is correctly rounded
+def cols_alloc(max_cols):
+    """columns of every panel of an engine created with max_cols (dav_create)"""
+    return (max_cols + 15) // 16 * 16 + 16
+
+
+def int_matrix(p, q, rng, amax=7):
+    return np.asfortranarray(rng.integers(-amax, amax + 1, (p, q)).astype(np.float64))
+
+
+def int_product(p, m):
+    """P M for integer-valued float64 P and M, in int64"""
+    return p.astype(np.int64) @ m.astype(np.int64)
+
+
+def phase_block(kind, n, k, rng):
+    return unit_block(n, k, rng) if kind == "narrow" else int_block(n, k, rng, bits=20)
+
+
+def ritz_inputs(kind, n, m, ncorr, gev, rng, dyadic=False):
+    """(V, W, Z, Y, theta) of one Ritz phase: Z = V, or the B V panel when gev.  dyadic: |theta| a power of two"""
+    v, w = phase_block(kind, n, m, rng), phase_block(kind, n, m, rng)
+    z = phase_block(kind, n, m, rng) if gev else v
+    y = int_matrix(m, ncorr, rng, 3 if kind == "narrow" else 7)
+    mags = [1, 2] if kind == "narrow" else [1, 2, 4, 8] if dyadic else list(range(1, 9))
+    theta = rng.choice(mags, ncorr) * rng.choice([-1, 1], ncorr)
+    return v, w, z, y, theta.astype(np.float64)
+
+
+def ritz_reference(v, w, z, y, theta):
+    """(X = V Y, R = W Y + Z (-Y theta), squared column norms of R) in int64"""
+    yi = y.astype(np.int64)
+    x = v.astype(np.int64) @ yi
+    r = w.astype(np.int64) @ yi + z.astype(np.int64) @ (-(yi * theta.astype(np.int64)[None, :]))
+    return x, r, np.sum(r * r, axis=0)
+
+
+def dpr_diagonals(n, gev, theta, rng, jstar=None):
+    """integer diagonals (dA, dB | None).  jstar None: the dyadic set - dA = 0, dB in {1, 2, 4}, every denominator theta_j dB_i a power of
+    two.  Otherwise dA in [-40, 40] with theta_jstar dB_i == dA_i in the guard rows (also returned): the first row, the last, and
+    the rows on both sides of every 128-row block edge up to three blocks"""
+    db = rng.choice([1.0, 2.0, 4.0], n) if gev else None
+    if jstar is None:
+        return np.zeros(n), db, np.zeros(0, dtype=np.int64)
+    da = rng.integers(-40, 41, n).astype(np.float64)
+    rows = np.array(sorted({r for r in (0, 127, 128, 255, 256, 383, n // 2, n - 1) if 0 <= r < n}))
+    da[rows] = theta[jstar] * (db[rows] if gev else 1.0)
+    return da, db, rows
+
+
+def dpr_reference(r, theta, da, db):
+    """T = R / (theta_j dB_i - dA_i), exactly 0 where the denominator is 0: numpy's correctly rounded fp64 division"""
+    den = theta[None, :] * (db[:, None] if db is not None else 1.0) - da[:, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.asfortranarray(np.where(den != 0.0, r.astype(np.float64) / den, 0.0)), den
+
+
+def fenced(n, cols, fill, c0=0, block=None):
+    """an n x cols panel of `fill` with `block` in the columns from c0"""
+    p = np.full((n, cols), fill, order="F")
+    if block is not None:
+        p[:, c0:c0 + block.shape[1]] = block
+    return p
+
+
+# ---- the GJD correction at fixed step counts --------------------------------------------------------------------------------------------
+def tridiag_csr(d, off):
+    """(indptr, indices, data) of the symmetric tridiagonal matrix with diagonal d and off-diagonal off (off[i] couples rows i, i + 1)"""
+    n = d.size
+    i = np.arange(n)
+    rows = np.concatenate([i, i[:-1], i[1:]])
+    cols = np.concatenate([i, i[1:], i[:-1]])
+    vals = np.concatenate([d, off, off])
+    order = np.lexsort((cols, rows))
+    indptr = np.searchsorted(rows[order], np.arange(n + 1)).astype(np.int64)
+    return indptr, cols[order].astype(np.int32), vals[order].astype(np.float64)
+
+
+def tridiag_mul(d, off, v):
+    y = d[:, None] * v
+    y[:-1] += off[:, None] * v[1:]
+    y[1:] += off[:, None] * v[:-1]
+    return y
+
+
+class GjdInputs:
+    """One block of projected systems for dav_gjd_correction_n, from a seeded default_rng: A tridiagonal with dA_i = 1 + 8 i / n + U(0, 1)
+    and off-diagonals 0.25 N(0, 1); generalized: B tridiagonal with dB_i = 1 + 0.1 U(0, 1) and off-diagonals 0.02 N(0, 1); X = qr(N(0, 1))
+    used as it is; R = 1e-2 N(0, 1) (zero_cols: exactly zero); theta_j = 0.5 + 0.05 j.  floor: row i0 = n // 2 has dA_i0 = theta_0 dB_i0
+    (the preconditioner's 1e-10 floor in column 0), X[i0, :] = 0 and R[i0, 0] = 2^-40."""
+
+    def __init__(self, n, m, gev, seed, zero_cols=(), floor=False):
+        rng = np.random.default_rng(seed)
+        self.n, self.m, self.gev = n, m, gev
+        self.da = 1.0 + 8.0 * np.arange(n) / n + rng.random(n)
+        self.offa = 0.25 * rng.standard_normal(n - 1)
+        self.db = 1.0 + 0.1 * rng.random(n) if gev else None
+        self.offb = 0.02 * rng.standard_normal(n - 1) if gev else None
+        self.x = np.asfortranarray(np.linalg.qr(rng.standard_normal((n, m)))[0])
+        self.r = np.asfortranarray(1e-2 * rng.standard_normal((n, m)))
+        self.r[:, list(zero_cols)] = 0.0
+        self.theta = 0.5 + 0.05 * np.arange(m)
+        if floor:
+            i0 = n // 2
+            self.da[i0] = self.theta[0] * (self.db[i0] if gev else 1.0)
+            self.x[i0, :] = 0.0
+            self.r[i0, 0] = 2.0 ** -40
+
+    def set_operators(self, e):
+        from fortran_davidson_amd.engine_c import OP_A, OP_B
+        e.set_operator_csr(OP_A, *tridiag_csr(self.da, self.offa))
+        if self.gev:
+            e.set_operator_csr(OP_B, *tridiag_csr(self.db, self.offb))
+
+    def restate(self, steps, dtype, inner_tol=0.0):
+        t = dtype
+        mul_a = lambda v: tridiag_mul(self.da.astype(t), self.offa.astype(t), v)          # noqa: E731
+        mul_b = (lambda v: tridiag_mul(self.db.astype(t), self.offb.astype(t), v)) if self.gev else None
+        return gjd_restatement(mul_a, mul_b, self.da, self.db, self.x, self.r, self.theta, steps, t, inner_tol)
+
+
+def gjd_restatement(mul_a, mul_b, da, db, x, r, theta, max_inner, dtype=np.float64, inner_tol=0.0):
+    """dav_gjd_correction_n (csrc/engine_gjd.hip) restated in numpy at precision `dtype`: block MINRES on
+    (I - x x^T)(A - theta B)(I - x x^T) t = -r with the Jacobi preconditioner K = max(|dA - theta dB|, 1e-10) restricted to the
+    complement of x.  mul_a / mul_b: v -> A v / B v on an n x m block of `dtype` (mul_b None: B = I).  Returns (T, steps taken)."""
+    t = dtype
+    x, r1, th = x.astype(t), -r.astype(t), theta.astype(t)
+    n, m = x.shape
+    one, zero = t(1.0), t(0.0)
+    kd = np.maximum(np.abs(da.astype(t)[:, None] - th[None, :] * (db.astype(t)[:, None] if db is not None else one)), t(1e-10))
+    dot = lambda a, b: np.sum(a * b, axis=0)                                             # noqa: E731
+    r2 = r1.copy()
+    mx, y = x / kd, r1 / kd                                   # the Jacobi preconditioner, with its floor
+    xmx = dot(x, mx)
+    cy = np.where(xmx > 0, -dot(x, y) / np.where(xmx > 0, xmx, one), zero)              # the projection coefficient
+    b2 = dot(r1, y) + cy * dot(r1, mx)
+    beta1 = np.where(b2 > 0, np.sqrt(np.maximum(b2, zero)), zero)
+    beta, phibar = beta1.copy(), beta1.copy()
+    active = beta1 > 0                                        # a column with beta1 == 0 never starts
+    oldb, dbar, epsln = np.zeros(m, t), np.zeros(m, t), np.zeros(m, t)
+    cs, sn = -np.ones(m, t), np.zeros(m, t)
+    tt, w, w1, w2 = (np.zeros((n, m), t) for _ in range(4))
+    stall = np.zeros(m, dtype=int)
+    itn = 0
+    while itn < max_inner and active.any():
+        itn += 1
+        act = active.astype(t)
+        safe_beta = np.where(active, beta, one)
+        c0 = act / safe_beta
+        v = c0 * y + (c0 * cy) * mx
+        ua = mul_a(v)
+        ub = mul_b(v) if mul_b is not None else v
+        # the Lanczos step, the four-term update: y = (A v - theta B v) - (x^T (A v - theta B v)) x - (beta / oldb) r1
+        c2 = -(dot(x, ua) - th * dot(x, ub)) * act
+        c3 = np.where(active & (itn >= 2), -beta / np.where(oldb != 0, oldb, one), zero)
+        y = act * ua + (-th * act) * ub + c2 * x + c3 * r1
+        alfa = dot(v, y)
+        y = act * y + np.where(active, -alfa / safe_beta, zero) * r2
+        r1, r2 = r2, y
+        y = act * (r2 / kd)
+        xy, ry, rmx = dot(x, y), dot(r2, y), dot(r2, mx)
+        # the Paige - Saunders scalars, per column
+        cy = np.where(active, -xy / np.where(xmx != 0, xmx, one), cy)
+        b2 = ry + cy * rmx
+        oldb = np.where(active, beta, oldb)
+        beta = np.where(active, np.where(b2 > 0, np.sqrt(np.maximum(b2, zero)), zero), beta)
+        oldeps = np.where(active, epsln, zero)
+        delta = np.where(active, cs * dbar + sn * alfa, zero)
+        gbar = sn * dbar - cs * alfa
+        epsln = np.where(active, sn * beta, epsln)
+        dbar = np.where(active, -cs * beta, dbar)
+        gam = np.where(active, np.maximum(np.sqrt(gbar * gbar + beta * beta), t(1e-300)), one)
+        cs = np.where(active, gbar / gam, cs)
+        sn = np.where(active, beta / gam, sn)
+        phi = np.where(active, cs * phibar, zero)
+        stall = np.where(active, np.where(sn > 0.95, stall + 1, 0), stall)
+        phibar = np.where(active, sn * phibar, phibar)
+        # w_new = (v - oldeps w1 - delta w2) / gamma;  t += phi w_new
+        w1, w2 = w2, w
+        w = (act / gam) * v + (-oldeps * act / gam) * w1 + (-delta * act / gam) * w2
+        tt = tt + (phi * act) * w
+        active = active & (phibar > t(inner_tol) * beta1) & (beta > 0) & ~((stall >= 8) & (phibar < t(1e-6) * beta1))
+    return tt, itn
+
+
+def gjd_error(t, t_ref):
+    """max over the columns of ||T_j - Tref_j||_inf / ||Tref_j||_inf (a column of the reference that is entirely zero: 0 if T's is
+    too, inf otherwise)"""
+    worst = 0.0
+    for j in range(t_ref.shape[1]):
+        scale = np.max(np.abs(t_ref[:, j]))
+        err = np.max(np.abs(t[:, j].astype(np.longdouble) - t_ref[:, j]))
+        worst = max(worst, float(err / scale) if scale > 0 else (0.0 if err == 0 else np.inf))
+    return worst
