@@ -493,19 +493,19 @@ static int apply_sparse(E* e, int which, OpDesc& o, const double* src, int k, do
     CHK(pack_operand(e, src + (int64_t)c * e->ldp, kk, has_comm(e)));
     double* out = dst + (int64_t)c * e->ldp;
     if (timed && which == DAV_OP_A) CHK(timed_begin(e, 4, flops, &kslot));
+    ChebEpi ep{};                   // the epilogue's operands at column c
+    if (epi) {
+      ep = *epi;
+      ep.z += (int64_t)c * ep.ld; ep.r += (int64_t)c * ep.ld; ep.pi += c;
+      if (ep.zprev) ep.zprev += (int64_t)c * ep.ld;
+    }
     if (o.kind == DAV_KIND_DIA) {
       if (epi) {
-        ChebEpi ep = *epi;
-        ep.z += (int64_t)c * ep.ld; ep.r += (int64_t)c * ep.ld; ep.pi += c;
-        if (ep.zprev) ep.zprev += (int64_t)c * ep.ld;
         launch_spmm_dia_cheb(e->stream, s.dia_off, s.dia_nd, s.dia_val, s.dia_ld, e->nloc, e->row0, e->n, e->xt, e->xt_group_stride, gp, kk, out, e->ldp, ep);
       } else {
         launch_spmm_dia(e->stream, s.dia_off, s.dia_nd, s.dia_val, s.dia_ld, e->nloc, e->row0, e->n, e->xt, e->xt_group_stride, gp, kk, out, e->ldp);
       }
     } else if (o.kind == DAV_KIND_CSR && epi) {
-      ChebEpi ep = *epi;
-      ep.z += (int64_t)c * ep.ld; ep.r += (int64_t)c * ep.ld; ep.pi += c;
-      if (ep.zprev) ep.zprev += (int64_t)c * ep.ld;
       launch_spmm_csr_cheb(e->stream, s.items, s.nitems, s.rp, s.col, s.val, e->xt, e->xt_group_stride, gp, kk, s.part, out, e->ldp, ep);
       launch_spmm_csr_finish_cheb(e->stream, s.longs, s.nlong, s.part, kk, out, e->ldp, ep);
     } else if (o.kind == DAV_KIND_CSR) {

@@ -396,10 +396,19 @@ struct Watchdog {
   int device = 0, rank = 0, nranks = 1;
 };
 
-// the method of a method code: the Chebyshev correction keeps its degree above the low byte (bits 8..15, 0 = the default), every other
-// code is its own method.  Every comparison of a method code goes through this.
-static inline int method_kind(int code) {
-  return code > 0 && ((code & 0xff) == DAV_METHOD_CHEB || (code & 0xff) == DAV_METHOD_LCHEB) ? code & 0xff : code;
+// A method code, parsed once where the Ritz phase begins.  The two Chebyshev corrections keep their degree above the low byte (bits 8..,
+// 0 = CHEB_DEFAULT_DEGREE; cheb_prepare checks the range): the low byte is taken as the kind only when it is DAV_METHOD_CHEB or
+// DAV_METHOD_LCHEB and the code is positive.  Every other code is its own kind, with degree 0.  A kind that is none of the six known ones
+// is not refused: no case below matches it, so the phase writes the residues and the norms and no correction block, as for DAV_METHOD_NONE.
+struct MethodSpec { int kind; int degree; };
+static inline MethodSpec parse_method(int code) {
+  const int low = code & 0xff;
+  if (code > 0 && (low == DAV_METHOD_CHEB || low == DAV_METHOD_LCHEB)) return {low, (code >> 8) != 0 ? code >> 8 : CHEB_DEFAULT_DEGREE};
+  return {code, 0};
+}
+// the correction block V[:, m:m+ncorr] comes out of the Ritz phase itself (GJD's is made behind it, from X and R)
+static inline bool block_in_ritz_phase(int kind) {
+  return kind == DAV_METHOD_DPR || kind == DAV_METHOD_BDPR || kind == DAV_METHOD_CHEB || kind == DAV_METHOD_LCHEB;
 }
 static inline int64_t roundup(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
@@ -512,8 +521,6 @@ void basis_order_ensure(E* e, int ncols);
 int bdpr_prepare(E* e);
 void bdpr_correct(E* e, int m, int ncorr, const double* theta_dev);
 // ---- engine_cheb.hip -------------------------------------------------------------------------------------
-int cheb_prepare(E* e, int degree);
-int cheb_correct(E* e, int m, int ncorr, int lowest, int degree, const double* theta_dev);
-int lcheb_prepare(E* e, int degree);
-int lcheb_correct(E* e, int m, int ncorr, int lowest, int degree, const double* theta_dev);
+int cheb_prepare(E* e, const MethodSpec& method);            // DAV_METHOD_CHEB and DAV_METHOD_LCHEB
+int cheb_correct(E* e, const MethodSpec& method, int m, int ncorr, int lowest, const double* theta_dev);
 #pragma GCC visibility pop

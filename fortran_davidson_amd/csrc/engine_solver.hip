@@ -283,18 +283,20 @@ int ritz_impl(E* e, int m, int ncorr, int lowest, const double* Y, int64_t ldy, 
                      double* resnorm, double* C, int64_t ldc, double* G, int64_t ldg, double* theta_out,
                      double* info_out) {
   CHK(bind(e));
-  // the code of the Chebyshev correction carries its degree in bits 8..15 (0 = the default); every other code is its own low byte
-  const int method = method_kind(method_code);
-  const bool cheb = method == DAV_METHOD_CHEB, lcheb = method == DAV_METHOD_LCHEB;
-  const int cheb_degree = (cheb || lcheb) && (method_code >> 8) != 0 ? method_code >> 8 : CHEB_DEFAULT_DEGREE;     // checked by cheb_prepare / lcheb_prepare
+  const MethodSpec spec = parse_method(method_code);
+  const int method = spec.kind;
   const bool dev = Y == nullptr;
   if (m <= 0 || lowest <= 0 || lowest > ncorr || ncorr > m || (!dev && ldy < m)) return fail("dav_ritz_residual_correction: bad shape");
-  const bool bdpr = method == DAV_METHOD_BDPR;
-  if ((method == DAV_METHOD_DPR || bdpr || cheb || lcheb) && m + ncorr > e->cols_alloc) return fail("basis panel too narrow for the correction block");
+  if (block_in_ritz_phase(method) && m + ncorr > e->cols_alloc) return fail("basis panel too narrow for the correction block");
   CHK(check_panel(e, DAV_PANEL_V, 0, m));
-  if (bdpr) CHK(bdpr_prepare(e));            // the method's contract, before any panel is written
-  if (cheb) CHK(cheb_prepare(e, cheb_degree));
-  if (lcheb) CHK(lcheb_prepare(e, cheb_degree));      // ... and, while the bound of A is stale, the Lanczos run: before the phase's event pair opens
+  // the method's contract, before any panel is written - and, while the bound of A is stale, the Lanczos run of LCHEB: before the phase's
+  // event pair opens
+  switch (method) {
+    case DAV_METHOD_BDPR: CHK(bdpr_prepare(e)); break;
+    case DAV_METHOD_CHEB:
+    case DAV_METHOD_LCHEB: CHK(cheb_prepare(e, spec)); break;
+    default: break;
+  }
   const double *dY, *dY2, *dTheta;
   int64_t ldm_y, ldm_y2;
   std::vector<double> y2;
@@ -342,14 +344,17 @@ int ritz_impl(E* e, int m, int ncorr, int lowest, const double* Y, int64_t ldy, 
   }
   r.pin = e->tune.pg_pin;
   launch_panel_gemm(e->stream, r);
-  if (bdpr) bdpr_correct(e, m, ncorr, dTheta);       // T = blocksolve(R) into V[:, m:m+ncorr]
-  if (cheb || lcheb) {
-    // T = z_d by d - 1 block products into V[:, m:m+ncorr].  Every product is timed like any apply; the phase's own pair is closed
-    // around them, because event pairs are collected only while none is open and a correction of a high degree has more than fit
-    CHK(timed_end(e, slot));
-    if (cheb) CHK(cheb_correct(e, m, ncorr, lowest, cheb_degree, dTheta));
-    else CHK(lcheb_correct(e, m, ncorr, lowest, cheb_degree, dTheta));
-    CHK(timed_begin(e, 2, 0, &slot));
+  switch (method) {
+    case DAV_METHOD_BDPR: bdpr_correct(e, m, ncorr, dTheta); break;       // T = blocksolve(R) into V[:, m:m+ncorr]
+    case DAV_METHOD_CHEB:
+    case DAV_METHOD_LCHEB:
+      // T = z_d by d - 1 block products into V[:, m:m+ncorr].  Every product is timed like any apply; the phase's own pair is closed
+      // around them, because event pairs are collected only while none is open and a correction of a high degree has more than fit
+      CHK(timed_end(e, slot));
+      CHK(cheb_correct(e, spec, m, ncorr, lowest, dTheta));
+      CHK(timed_begin(e, 2, 0, &slot));
+      break;
+    default: break;
   }
   if (!fuse_norms) launch_norm_finish(e->stream, e->norm_partial, (int)(e->nloc_pad / PG_ROWS), lowest, result_target(e));
   // optionally the Gram block the first orthonormalisation pass needs, [V T]^T T with T = V[:, m:m+ncorr] just
@@ -620,7 +625,7 @@ extern "C" int dav_rr_ritz(dav_handle_t e, int m, int ncorr, int lowest, int met
   CHK(timed_begin(e, 1, 0, &slot));
   if (!launch_small_eig(e->stream, e->rr_H, e->rr_ld, e->rr_S, e->rr_ld, m, e->gev != 0, e->rr_theta, e->rr_Y, e->rr_ld, e->rr_work, e->rr_info))
     return fail("dav_rr_ritz: order out of range");
-  const int nq = method_kind(method) == DAV_METHOD_GJD ? ncorr : std::max(ncorr, lowest);
+  const int nq = parse_method(method).kind == DAV_METHOD_GJD ? ncorr : std::max(ncorr, lowest);
   launch_rr_pack(e->stream, e->rr_Y, e->rr_ld, e->rr_theta, m, nq, (int)roundup(m, 4), (int)roundup(nq, 64), e->rr_Ypk, e->rr_Y2pk, e->rr_thpk,
                  e->rr_info, e->rr_thpk + roundup(ncorr, 64));
   e->rr_tp = roundup(nq, 64) / 16;

@@ -10,23 +10,25 @@ from ._lib import hip_lib
 
 OP_A, OP_B = 0, 1
 PANEL_V, PANEL_W, PANEL_BV, PANEL_X, PANEL_R, PANEL_S = range(6)
-METHOD_DPR, METHOD_GJD = 0, 1
-METHOD_BDPR = 3          # block-diagonal DPR of a BSR operator (DAV_METHOD_BDPR)
-METHOD_CHEB = 4          # Chebyshev-filtered correction of a CSR / BSR operator (DAV_METHOD_CHEB), default degree
+# the method codes (the header's DAV_METHOD_*); a new method is one row here
+METHOD_DPR, METHOD_GJD, METHOD_NONE = 0, 1, 2
+METHOD_BDPR = 3          # block-diagonal DPR of a BSR operator
+METHOD_CHEB = 4          # Chebyshev-filtered correction of a CSR / BSR operator, default degree
+METHOD_LCHEB = 5         # the same correction with a Lanczos bound, for any operator applied on the device
+
+
+def method_code(kind, degree=0):
+    """the method code of `kind` with the degree of the Chebyshev corrections in bits 8..15 (the header's DAV_METHOD_CHEB_DEGREE /
+    DAV_METHOD_LCHEB_DEGREE), 0 = the engine's default of 10.  The engine itself refuses a degree outside 1..64."""
+    return kind | (int(degree) << 8)
 
 
 def method_cheb(degree=0):
-    """the method code of the Chebyshev correction of `degree` (the header's DAV_METHOD_CHEB_DEGREE): the degree rides in bits 8..15,
-    0 = the engine's default of 10.  The engine itself refuses a degree outside 1..64."""
-    return METHOD_CHEB | (int(degree) << 8)
-
-
-METHOD_LCHEB = 5         # the same correction with a Lanczos bound, for any operator applied on the device (DAV_METHOD_LCHEB)
+    return method_code(METHOD_CHEB, degree)
 
 
 def method_lcheb(degree=0):
-    """the method code of the Chebyshev correction with a Lanczos bound (the header's DAV_METHOD_LCHEB_DEGREE), as method_cheb"""
-    return METHOD_LCHEB | (int(degree) << 8)
+    return method_code(METHOD_LCHEB, degree)
 
 
 # int fn(ctx, hip_stream, n, row0, nloc, k, x_dev, ldx, y_dev, ldy) - include/davidson_hip.h: dav_device_apply_fn

@@ -17,6 +17,7 @@ module davidson_device
   use, intrinsic :: iso_c_binding
   use numeric_kinds, only: dp
   use davidson_hip_c
+  use davidson_method
   use lapack_wrapper, only: lapack_rayleigh_ritz, lapack_matmul
   use davidson_knobs
   use davidson_ortho
@@ -181,29 +182,12 @@ contains
     if (host_ops) then
        meth = DAV_METHOD_DPR       ! the matrix-free driver never looks at `method`: always DPR (src/davidson.f90:428)
     else
-       select case (trim(method))
-       case ("DPR")
-          meth = DAV_METHOD_DPR
-       case ("GJD")
-          meth = DAV_METHOD_GJD
-       case ("BDPR")
-          ! block-diagonal DPR for BSR operators (opt-in, not in the reference): the correction block comes out of the Ritz phase like
-          ! DPR's, so everything below that asks for GJD takes the DPR side; the engine refuses operators the method does not serve
-          meth = DAV_METHOD_BDPR
-       case default
-          ! "CHEB" / "CHEB<degree>": the Chebyshev-filtered correction for CSR / BSR operators (opt-in, not in the reference).  Like BDPR
-          ! its block comes out of the Ritz phase, so it takes the DPR side below; the engine refuses what the method does not serve
-          meth = cheb_method_code(trim(method))
-          ! "LCHEB" / "LCHEB<degree>": the same correction with a Lanczos bound, for any operator the engine applies on the device
-          if (meth < 0) meth = lcheb_method_code(trim(method))
-          if (meth < 0) then
-             ! the reference leaves the correction undefined here (src/davidson.f90:656-669)
-             print *, "generalized_eigensolver: unknown correction method '", trim(method), "' (DPR, GJD or BDPR)", &
-                  ", or CHEB / CHEB<degree 1..64>", &
-                  ", or LCHEB / LCHEB<degree 1..64>"
-             error stop
-          end if
-       end select
+       meth = method_code(trim(method))
+       if (meth < 0) then
+          ! the reference leaves the correction undefined here (src/davidson.f90:656-669)
+          print *, unknown_method_message(trim(method))
+          error stop
+       end if
     end if
     pol = POLICY_ALL
     if (present(policy)) pol = policy
@@ -353,8 +337,7 @@ contains
        if (drr) then
           ! 3 + 4 on the device: eigenpairs of the device-resident projected matrices, then the same fused phase from
           ! where they lie; one synchronisation brings back the Ritz values, the residual norms and the Gram blocks
-          if (phase == DAV_METHOD_DPR .or. phase == DAV_METHOD_BDPR .or. method_kind(phase) == DAV_METHOD_CHEB &
-               .or. method_kind(phase) == DAV_METHOD_LCHEB) then
+          if (method_block_in_ritz_phase(phase)) then
              if (allocated(c_pre)) deallocate(c_pre, g_pre)
              allocate(c_pre(m, ncorr), g_pre(ncorr, ncorr))
              call check_dav(dav_rr_ritz(h, int(m, c_int), int(ncorr, c_int), int(lowest, c_int), int(phase, c_int), theta, &

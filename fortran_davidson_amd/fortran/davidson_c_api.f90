@@ -5,6 +5,7 @@ module davidson_c_api
   use, intrinsic :: iso_c_binding
   use numeric_kinds, only: dp
   use davidson, only: generalized_eigensolver
+  use davidson_method, only: method_label
   use davidson_device
   use davidson_free, only: free_matmul
   use davidson_sparse, only: csr_matrix, bsr_matrix, engine_set_sparse, engine_set_sparse_device, engine_set_block_sparse_device, &
@@ -26,31 +27,33 @@ module davidson_c_api
 
 contains
 
-  function method_name(code) result(name)
-    integer(c_int), intent(in) :: code
-    character(len=4) :: name
-    name = "DPR"
-    if (code == 1) name = "GJD"
-    if (code > 1) name = "XXX"
-    if (code == 3) name = "BDPR"
-    if (code > 3 .and. iand(code, 255) == 4) name = "CHEB"      ! the Chebyshev correction: its degree rides above the low byte
-  end function method_name
+  ! The solve doors.  max_dim < 0: max_dim_sub is absent; has_b = 0: second_matrix is absent - an unallocated allocatable and a
+  ! disassociated pointer are absent optional arguments (Fortran 2008), so each body calls generalized_eigensolver once per specific:
+  ! the reference's argument list, and with x0 present the one with initial_vectors=.
 
-  !> what the doors hand to generalized_eigensolver: method_name, and behind "CHEB" the degree of bits 8.. of the code ("CHEB16"; none =
-  !> the default degree).  A degree the driver does not take (outside 1..64) makes a name it does not know.  Low byte 5 is "LCHEB", the
-  !> same correction with a Lanczos bound, and carries its degree the same way ("LCHEB16").
-  function method_label(code) result(label)
-    integer(c_int), intent(in) :: code
-    character(len=12) :: label
-    label = method_name(code)
-    if (label == "CHEB" .and. ishft(code, -8) /= 0) write (label(5:12), "(i0)") ishft(code, -8)
-    if (code > 3 .and. iand(code, 255) == 5) then
-       label = "LCHEB"
-       if (ishft(code, -8) /= 0) write (label(6:12), "(i0)") ishft(code, -8)
+  !> the body of fd_dense_solve and fd_dense_solve_guess (x0 present)
+  subroutine dense_solve(n, a, has_b, b, lowest, method, max_it, tol, max_dim, evals, evecs, iters, x0)
+    integer(c_int), intent(in) :: n, has_b, lowest, method, max_it, max_dim
+    real(c_double), intent(in) :: tol
+    real(c_double), intent(in), target :: a(n, n), b(n, *)
+    real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
+    integer(c_int), intent(out) :: iters
+    real(c_double), intent(in), optional :: x0(:, :)
+    integer, allocatable :: md
+    real(c_double), pointer :: bp(:, :)
+    integer :: it
+    if (max_dim >= 0) md = max_dim
+    bp => null()
+    if (has_b /= 0) bp => b(:, 1:n)
+    if (present(x0)) then
+       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, bp, initial_vectors=x0)
+    else
+       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, bp)
     end if
-  end function method_label
+    iters = it
+  end subroutine dense_solve
 
-  !> generalized_eigensolver(matrix, ...) - dense specific.  max_dim < 0: argument absent.
+  !> generalized_eigensolver(matrix, ...) - dense specific
   subroutine fd_dense_solve(n, a, has_b, b, lowest, method, max_it, tol, max_dim, evals, evecs, iters) &
        bind(C, name="fd_dense_solve")
     integer(c_int), value :: n, has_b, lowest, method, max_it, max_dim
@@ -58,22 +61,7 @@ contains
     real(c_double), intent(in) :: a(n, n), b(n, *)
     real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
     integer(c_int), intent(out) :: iters
-    integer :: it
-    if (has_b /= 0) then
-       if (max_dim >= 0) then
-          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, max_dim, b(:, 1:n))
-       else
-          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, &
-               second_matrix=b(:, 1:n))
-       end if
-    else
-       if (max_dim >= 0) then
-          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, max_dim)
-       else
-          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it)
-       end if
-    end if
-    iters = it
+    call dense_solve(n, a, has_b, b, lowest, method, max_it, tol, max_dim, evals, evecs, iters)
   end subroutine fd_dense_solve
 
   !> A csr_matrix from C arrays (row_ptr: n + 1 int64 offsets, col_idx: int32) numbered from `base` (0 or 1): renumbered from 1.
@@ -94,7 +82,32 @@ contains
     a%diagonals = iand(lower, DAV_CSR_DIAGONALS) /= 0
   end function csr_from_c
 
-  !> generalized_eigensolver(a_csr, ...) - sparse specific.  max_dim < 0: argument absent; has_b: B given (same base and triangle).
+  !> the body of fd_sparse_solve and fd_sparse_solve_guess (x0 present); B has the base and the triangle of A
+  subroutine sparse_solve(n, rp, col, vals, has_b, rpb, colb, valsb, base, lower, lowest, method, max_it, tol, max_dim, evals, evecs, &
+       iters, x0)
+    integer(c_int), intent(in) :: n, has_b, base, lower, lowest, method, max_it, max_dim
+    integer(c_int64_t), intent(in) :: rp(n + 1), rpb(*)
+    integer(c_int32_t), intent(in) :: col(*), colb(*)
+    real(c_double), intent(in) :: vals(*), valsb(*), tol
+    real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
+    integer(c_int), intent(out) :: iters
+    real(c_double), intent(in), optional :: x0(:, :)
+    type(csr_matrix) :: a
+    type(csr_matrix), allocatable :: b
+    integer, allocatable :: md
+    integer :: it
+    if (max_dim >= 0) md = max_dim
+    a = csr_from_c(n, rp, col, vals, base, lower)
+    if (has_b /= 0) b = csr_from_c(n, rpb, colb, valsb, base, lower)
+    if (present(x0)) then
+       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, b, initial_vectors=x0)
+    else
+       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, b)
+    end if
+    iters = it
+  end subroutine sparse_solve
+
+  !> generalized_eigensolver(a_csr, ...) - sparse specific
   subroutine fd_sparse_solve(n, rp, col, vals, has_b, rpb, colb, valsb, base, lower, lowest, method, max_it, tol, max_dim, evals, &
        evecs, iters) bind(C, name="fd_sparse_solve")
     integer(c_int), value :: n, has_b, base, lower, lowest, method, max_it, max_dim
@@ -104,24 +117,7 @@ contains
     real(c_double), value :: tol
     real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
     integer(c_int), intent(out) :: iters
-    type(csr_matrix) :: a, b
-    integer :: it
-    a = csr_from_c(n, rp, col, vals, base, lower)
-    if (has_b /= 0) then
-       b = csr_from_c(n, rpb, colb, valsb, base, lower)
-       if (max_dim >= 0) then
-          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, max_dim, b)
-       else
-          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, second_matrix=b)
-       end if
-    else
-       if (max_dim >= 0) then
-          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, max_dim)
-       else
-          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it)
-       end if
-    end if
-    iters = it
+    call sparse_solve(n, rp, col, vals, has_b, rpb, colb, valsb, base, lower, lowest, method, max_it, tol, max_dim, evals, evecs, iters)
   end subroutine fd_sparse_solve
 
   !> A bsr_matrix from C arrays (row_ptr: n / b + 1 int64 offsets, col_idx: int32 block columns, vals: b * b values per block in
@@ -146,8 +142,32 @@ contains
     a%lower = iand(lower, DAV_CSR_LOWER) /= 0
   end function bsr_from_c
 
-  !> generalized_eigensolver(a_bsr, ...) - block-sparse specific.  max_dim < 0: argument absent; has_b: B given (same block size, base
-  !> and triangle).
+  !> the body of fd_bsr_solve and fd_bsr_solve_guess (x0 present); B has the block size, the base and the triangle of A
+  subroutine bsr_solve(n, b, rp, col, vals, has_b, rpb, colb, valsb, base, lower, lowest, method, max_it, tol, max_dim, evals, evecs, &
+       iters, x0)
+    integer(c_int), intent(in) :: n, b, has_b, base, lower, lowest, method, max_it, max_dim
+    integer(c_int64_t), intent(in) :: rp(*), rpb(*)
+    integer(c_int32_t), intent(in) :: col(*), colb(*)
+    real(c_double), intent(in) :: vals(*), valsb(*), tol
+    real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
+    integer(c_int), intent(out) :: iters
+    real(c_double), intent(in), optional :: x0(:, :)
+    type(bsr_matrix) :: a
+    type(bsr_matrix), allocatable :: bm
+    integer, allocatable :: md
+    integer :: it
+    if (max_dim >= 0) md = max_dim
+    a = bsr_from_c(n, b, rp, col, vals, base, lower)
+    if (has_b /= 0) bm = bsr_from_c(n, b, rpb, colb, valsb, base, lower)
+    if (present(x0)) then
+       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, bm, initial_vectors=x0)
+    else
+       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, bm)
+    end if
+    iters = it
+  end subroutine bsr_solve
+
+  !> generalized_eigensolver(a_bsr, ...) - block-sparse specific
   subroutine fd_bsr_solve(n, b, rp, col, vals, has_b, rpb, colb, valsb, base, lower, lowest, method, max_it, tol, max_dim, evals, &
        evecs, iters) bind(C, name="fd_bsr_solve")
     integer(c_int), value :: n, b, has_b, base, lower, lowest, method, max_it, max_dim
@@ -157,24 +177,7 @@ contains
     real(c_double), value :: tol
     real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
     integer(c_int), intent(out) :: iters
-    type(bsr_matrix) :: a, bm
-    integer :: it
-    a = bsr_from_c(n, b, rp, col, vals, base, lower)
-    if (has_b /= 0) then
-       bm = bsr_from_c(n, b, rpb, colb, valsb, base, lower)
-       if (max_dim >= 0) then
-          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, max_dim, bm)
-       else
-          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, second_matrix=bm)
-       end if
-    else
-       if (max_dim >= 0) then
-          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, max_dim)
-       else
-          call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it)
-       end if
-    end if
-    iters = it
+    call bsr_solve(n, b, rp, col, vals, has_b, rpb, colb, valsb, base, lower, lowest, method, max_it, tol, max_dim, evals, evecs, iters)
   end subroutine fd_bsr_solve
 
   function apply_cb_a(input_vect) result(output_vect)
@@ -193,6 +196,25 @@ contains
     call cb_b(int(size(x, 1), c_int), int(size(x, 2), c_int), x, output_vect)
   end function apply_cb_b
 
+  !> the body of fd_free_solve and fd_free_solve_guess (x0 present)
+  subroutine free_solve(fa, fb, n, lowest, max_it, tol, max_dim, evals, evecs, iters, x0)
+    type(c_funptr), intent(in) :: fa, fb
+    integer(c_int), intent(in) :: n, lowest, max_it, max_dim
+    real(c_double), intent(in) :: tol
+    real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
+    integer(c_int), intent(out) :: iters
+    real(c_double), intent(in), optional :: x0(:, :)
+    integer :: it
+    call c_f_procpointer(fa, cb_a)
+    call c_f_procpointer(fb, cb_b)
+    if (present(x0)) then
+       call generalized_eigensolver(apply_cb_a, evals, evecs, lowest, "DPR", max_it, tol, it, max_dim, apply_cb_b, initial_vectors=x0)
+    else
+       call generalized_eigensolver(apply_cb_a, evals, evecs, lowest, "DPR", max_it, tol, it, max_dim, apply_cb_b)
+    end if
+    iters = it
+  end subroutine free_solve
+
   !> generalized_eigensolver(fun_A, ..., fun_B) - matrix-free specific with C callbacks.
   subroutine fd_free_solve(n, fa, fb, lowest, max_it, tol, max_dim, evals, evecs, iters) bind(C, name="fd_free_solve")
     integer(c_int), value :: n, lowest, max_it, max_dim
@@ -200,11 +222,7 @@ contains
     real(c_double), value :: tol
     real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
     integer(c_int), intent(out) :: iters
-    integer :: it
-    call c_f_procpointer(fa, cb_a)
-    call c_f_procpointer(fb, cb_b)
-    call generalized_eigensolver(apply_cb_a, evals, evecs, lowest, "DPR", max_it, tol, it, max_dim, apply_cb_b)
-    iters = it
+    call free_solve(fa, fb, n, lowest, max_it, tol, max_dim, evals, evecs, iters)
   end subroutine fd_free_solve
 
   ! ---- device-resident engine ---------------------------------------------------------------------
@@ -212,12 +230,10 @@ contains
     integer(c_int), value :: n, lowest, max_dim, gev, device, rank, nranks
     type(c_ptr) :: p
     type(davidson_engine), pointer :: eng
+    integer, allocatable :: md                  ! max_dim < 0: max_dim_sub is absent
     allocate(eng)
-    if (max_dim >= 0) then
-       call engine_create(eng, n, lowest, max_dim, gev /= 0, device, rank, nranks)
-    else
-       call engine_create(eng, n, lowest, gev=gev /= 0, device=device, rank=rank, nranks=nranks)
-    end if
+    if (max_dim >= 0) md = max_dim
+    call engine_create(eng, n, lowest, md, gev /= 0, device, rank, nranks)
     p = c_loc(eng)
   end function fd_engine_create
 
@@ -445,15 +461,7 @@ contains
     real(c_double), intent(in) :: a(n, n), b(n, *), x0(n, g)
     real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
     integer(c_int), intent(out) :: iters
-    integer :: it, md
-    md = max_dim
-    if (md < 0) md = 10 * lowest
-    if (has_b /= 0) then
-       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, b(:, 1:n), initial_vectors=x0)
-    else
-       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, initial_vectors=x0)
-    end if
-    iters = it
+    call dense_solve(n, a, has_b, b, lowest, method, max_it, tol, max_dim, evals, evecs, iters, x0)
   end subroutine fd_dense_solve_guess
 
   subroutine fd_sparse_solve_guess(n, rp, col, vals, has_b, rpb, colb, valsb, base, lower, lowest, method, max_it, tol, max_dim, g, x0, &
@@ -465,18 +473,7 @@ contains
     real(c_double), value :: tol
     real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
     integer(c_int), intent(out) :: iters
-    type(csr_matrix) :: a, b
-    integer :: it, md
-    md = max_dim
-    if (md < 0) md = 10 * lowest
-    a = csr_from_c(n, rp, col, vals, base, lower)
-    if (has_b /= 0) then
-       b = csr_from_c(n, rpb, colb, valsb, base, lower)
-       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, b, initial_vectors=x0)
-    else
-       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, initial_vectors=x0)
-    end if
-    iters = it
+    call sparse_solve(n, rp, col, vals, has_b, rpb, colb, valsb, base, lower, lowest, method, max_it, tol, max_dim, evals, evecs, iters, x0)
   end subroutine fd_sparse_solve_guess
 
   subroutine fd_bsr_solve_guess(n, b, rp, col, vals, has_b, rpb, colb, valsb, base, lower, lowest, method, max_it, tol, max_dim, g, x0, &
@@ -488,18 +485,7 @@ contains
     real(c_double), value :: tol
     real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
     integer(c_int), intent(out) :: iters
-    type(bsr_matrix) :: a, bm
-    integer :: it, md
-    md = max_dim
-    if (md < 0) md = 10 * lowest
-    a = bsr_from_c(n, b, rp, col, vals, base, lower)
-    if (has_b /= 0) then
-       bm = bsr_from_c(n, b, rpb, colb, valsb, base, lower)
-       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, bm, initial_vectors=x0)
-    else
-       call generalized_eigensolver(a, evals, evecs, lowest, method_label(method), max_it, tol, it, md, initial_vectors=x0)
-    end if
-    iters = it
+    call bsr_solve(n, b, rp, col, vals, has_b, rpb, colb, valsb, base, lower, lowest, method, max_it, tol, max_dim, evals, evecs, iters, x0)
   end subroutine fd_bsr_solve_guess
 
   subroutine fd_free_solve_guess(n, fa, fb, lowest, max_it, tol, max_dim, g, x0, evals, evecs, iters) bind(C, name="fd_free_solve_guess")
@@ -509,11 +495,7 @@ contains
     real(c_double), intent(in) :: x0(n, g)
     real(c_double), intent(out) :: evals(lowest), evecs(n, lowest)
     integer(c_int), intent(out) :: iters
-    integer :: it
-    call c_f_procpointer(fa, cb_a)
-    call c_f_procpointer(fb, cb_b)
-    call generalized_eigensolver(apply_cb_a, evals, evecs, lowest, "DPR", max_it, tol, it, max_dim, apply_cb_b, initial_vectors=x0)
-    iters = it
+    call free_solve(fa, fb, n, lowest, max_it, tol, max_dim, evals, evecs, iters, x0)
   end subroutine fd_free_solve_guess
 
   !> kind 0: dense generated in HBM, 1: hashed matrix-free operator, 2: harness operator, 3: identity
@@ -523,20 +505,14 @@ contains
     integer(c_int), value :: which, kind, seed, use_diag_val
     real(c_double), value :: sparsity, diag_val
     type(davidson_engine), pointer :: eng
+    real(dp), allocatable :: dv                 ! use_diag_val = 0: diag_val is absent
     call c_f_pointer(p, eng)
+    if (use_diag_val /= 0) dv = diag_val
     select case (kind)
     case (0)
-       if (use_diag_val /= 0) then
-          call engine_generate_diagonal_dominant(eng, int(which), sparsity, diag_val, int(seed))
-       else
-          call engine_generate_diagonal_dominant(eng, int(which), sparsity, seed=int(seed))
-       end if
+       call engine_generate_diagonal_dominant(eng, int(which), sparsity, dv, int(seed))
     case (1)
-       if (use_diag_val /= 0) then
-          call engine_set_hashed_operator(eng, int(which), sparsity, diag_val, int(seed))
-       else
-          call engine_set_hashed_operator(eng, int(which), sparsity, seed=int(seed))
-       end if
+       call engine_set_hashed_operator(eng, int(which), sparsity, dv, int(seed))
     case (2)
        call engine_set_harness_operator(eng, int(which))
     case default
@@ -555,17 +531,13 @@ contains
     integer(c_int), intent(out) :: iters
     type(davidson_engine), pointer :: eng
     real(c_double), pointer :: vec(:, :)
-    integer :: it, md
+    integer :: it
+    integer, allocatable :: md                  ! max_dim < 0: max_dim_sub is absent
     call c_f_pointer(p, eng)
-    md = max_dim
-    if (md < 0) md = 10 * lowest
-    if (want_vectors /= 0) then
-       call c_f_pointer(c_loc(evecs), vec, [eng%n, int(lowest)])
-       call generalized_eigensolver(eng, evals, vec, lowest, method_label(method), max_it, tol, it, md)
-    else
-       call generalized_eigensolver(eng, eigenvalues=evals, lowest=lowest, method=method_label(method), &
-            max_iterations=max_it, tolerance=tol, iters=it, max_dim_sub=md)
-    end if
+    if (max_dim >= 0) md = max_dim
+    vec => null()                               ! want_vectors = 0: eigenvectors is absent
+    if (want_vectors /= 0) call c_f_pointer(c_loc(evecs), vec, [eng%n, int(lowest)])
+    call generalized_eigensolver(eng, evals, vec, lowest, method_label(method), max_it, tol, it, md)
     iters = it
   end subroutine fd_engine_solve
 
@@ -592,24 +564,24 @@ contains
   ! ---- helper modules (unit tests mirror src/tests/test_call_lapack.f90) ----------------------------
   subroutine fd_lapack_eigensolver(n, mtx, has_stx, stx, evals, evecs) bind(C, name="fd_lapack_eigensolver")
     integer(c_int), value :: n, has_stx
-    real(c_double), intent(in) :: mtx(n, n), stx(n, *)
+    real(c_double), intent(in) :: mtx(n, n)
+    real(c_double), intent(in), target :: stx(n, *)
     real(c_double), intent(out) :: evals(n), evecs(n, n)
-    if (has_stx /= 0) then
-       call lapack_generalized_eigensolver(mtx, evals, evecs, stx(:, 1:n))
-    else
-       call lapack_generalized_eigensolver(mtx, evals, evecs)
-    end if
+    real(c_double), pointer :: sp(:, :)
+    sp => null()                                ! has_stx = 0: stx is absent
+    if (has_stx /= 0) sp => stx(:, 1:n)
+    call lapack_generalized_eigensolver(mtx, evals, evecs, sp)
   end subroutine fd_lapack_eigensolver
 
   subroutine fd_lapack_rayleigh_ritz(n, mtx, has_stx, stx, nvec, evals, evecs) bind(C, name="fd_lapack_rayleigh_ritz")
     integer(c_int), value :: n, has_stx, nvec
-    real(c_double), intent(in) :: mtx(n, n), stx(n, *)
+    real(c_double), intent(in) :: mtx(n, n)
+    real(c_double), intent(in), target :: stx(n, *)
     real(c_double), intent(out) :: evals(n), evecs(n, n)
-    if (has_stx /= 0) then
-       call lapack_rayleigh_ritz(mtx, evals, evecs, int(nvec), stx(:, 1:n))
-    else
-       call lapack_rayleigh_ritz(mtx, evals, evecs, int(nvec))
-    end if
+    real(c_double), pointer :: sp(:, :)
+    sp => null()
+    if (has_stx /= 0) sp => stx(:, 1:n)
+    call lapack_rayleigh_ritz(mtx, evals, evecs, int(nvec), sp)
   end subroutine fd_lapack_rayleigh_ritz
 
   subroutine fd_lapack_qr(m, n, basis) bind(C, name="fd_lapack_qr")
@@ -664,14 +636,11 @@ contains
     integer(c_int), value :: n, use_diag_val, seed
     real(c_double), value :: sparsity, diag_val
     real(c_double), intent(out) :: arr(n, n)
-    real(dp) :: sp, dv
+    real(dp) :: sp
+    real(dp), allocatable :: dv                 ! use_diag_val = 0: diag_val is absent
     sp = sparsity
-    dv = diag_val
-    if (use_diag_val /= 0) then
-       arr = generate_diagonal_dominant(n, sp, dv, int(seed))
-    else
-       arr = generate_diagonal_dominant(n, sp, seed=int(seed))
-    end if
+    if (use_diag_val /= 0) dv = diag_val
+    arr = generate_diagonal_dominant(n, sp, dv, int(seed))
   end subroutine fd_generate_diagonal_dominant
 
   subroutine fd_norm(n, v, res) bind(C, name="fd_norm")

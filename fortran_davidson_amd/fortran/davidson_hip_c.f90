@@ -2,13 +2,13 @@
 !> HIP engine (libdavidson_hip.so).  One interface per C entry point, same order as the header.
 module davidson_hip_c
   use, intrinsic :: iso_c_binding
+  use davidson_method, only: DAV_METHOD_DPR, DAV_METHOD_GJD, DAV_METHOD_NONE, DAV_METHOD_BDPR, DAV_METHOD_CHEB, DAV_METHOD_LCHEB
   implicit none
   public
 
   integer(c_int), parameter :: DAV_OP_A = 0, DAV_OP_B = 1
   integer(c_int), parameter :: DAV_PANEL_V = 0, DAV_PANEL_W = 1, DAV_PANEL_BV = 2, DAV_PANEL_X = 3, &
        DAV_PANEL_R = 4, DAV_PANEL_S = 5
-  integer(c_int), parameter :: DAV_METHOD_DPR = 0, DAV_METHOD_GJD = 1, DAV_METHOD_NONE = 2, DAV_METHOD_BDPR = 3
   !> dav_panel_unit_column: "the engine keeps no such entry of the start order" (not an error)
   integer(c_int), parameter :: DAV_NO_SUCH_ENTRY = 2
   !> dav_set_operator_csr: every nonzero given / only j <= i given (the engine mirrors the strict lower part)

@@ -7,55 +7,9 @@ module davidson_knobs
   implicit none
   private
   public :: env_device, env_storage, env_storage_symmetric, symmetry_probe, basis_capacity, gjd_tol_unwanted, gjd_tol_wanted, &
-       gjd_adaptive_factor, restart_refresh_interval, ascending_order, tick, trace_iterations, verbose, DAV_METHOD_CHEB, cheb_method_code, &
-       method_kind, DAV_METHOD_LCHEB, lcheb_method_code
-
-  !> Chebyshev-filtered correction for CSR / BSR operators (include/davidson_hip.h): the code of the method sits in the low byte of the
-  !> integer the engine takes, the degree (1..64, 0 = the engine's default) in bits 8..15
-  integer, parameter :: DAV_METHOD_CHEB = 4
-  !> the same correction with a Lanczos bound, for any operator the engine applies on the device; its degree rides the same way
-  integer, parameter :: DAV_METHOD_LCHEB = 5
+       gjd_adaptive_factor, restart_refresh_interval, ascending_order, tick, trace_iterations, verbose
 
 contains
-
-  !> "CHEB" -> 4, "CHEB<d>" with 1 <= d <= 64 -> 4 + 256 d (the header's DAV_METHOD_CHEB_DEGREE), anything else -> -1
-  function cheb_method_code(method) result(code)
-    character(len=*), intent(in) :: method
-    integer :: code, d, stat, i
-    code = -1
-    if (len_trim(method) < 4) return
-    if (method(1:4) /= "CHEB") return
-    if (len_trim(method) == 4) then
-       code = DAV_METHOD_CHEB
-       return
-    end if
-    if (len_trim(method) > 6) return
-    do i = 5, len_trim(method)
-       if (index("0123456789", method(i:i)) == 0) return
-    end do
-    read (method(5:len_trim(method)), *, iostat=stat) d
-    if (stat /= 0) return
-    if (d < 1 .or. d > 64) return
-    code = DAV_METHOD_CHEB + 256 * d
-  end function cheb_method_code
-
-  !> "LCHEB" -> 5, "LCHEB<d>" with 1 <= d <= 64 -> 5 + 256 d (the header's DAV_METHOD_LCHEB_DEGREE), anything else -> -1
-  function lcheb_method_code(method) result(code)
-    character(len=*), intent(in) :: method
-    integer :: code
-    code = -1
-    if (len_trim(method) < 5) return
-    if (method(1:1) /= "L") return
-    code = cheb_method_code(method(2:len_trim(method)))
-    if (code >= 0) code = code - DAV_METHOD_CHEB + DAV_METHOD_LCHEB
-  end function lcheb_method_code
-
-  !> the method of a method code: its low byte (the Chebyshev correction keeps its degree above it)
-  pure function method_kind(code) result(kind)
-    integer, intent(in) :: code
-    integer :: kind
-    kind = iand(code, 255)
-  end function method_kind
 
   !> Device index from the environment (DAVIDSON_DEVICE, default 0): an engine knob that does not
   !> touch the reference's argument lists (dense and matrix-free front ends alike).

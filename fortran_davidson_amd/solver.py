@@ -21,92 +21,83 @@ from .engine_c import (CEngine, DavidsonHipError, _device_bsr_tensors, _device_c
                        update_values_array)
 
 _METHOD = {"DPR": 0, "GJD": 1, "BDPR": 3}
+_DEGREE_METHOD = {"CHEB": 4, "LCHEB": 5}        # "<name>" (default degree) or "<name><d>" with 1 <= d <= 64: the degree rides in bits 8..15
 
 
-def _check_bdpr(method, blocks, gev=False, n=0, nranks=1, where="generalized_eigensolver"):
-    """method "BDPR" (block-diagonal DPR) serves BSR operators only - A of any block size 1..16, B (generalized problems) of the same
-    one, and with several ranks a block size that divides the rows of a rank's slab.  The engine refuses anything else at the first
-    correction and the Fortran doors stop the process on an engine error, so the front ends refuse here (ValueError), before any
-    engine call.  blocks: the block sizes of A and B as the caller set them, None = not a BSR operator."""
-    if method != "BDPR":
-        return
-    ba, bb = blocks
-    if ba is None:
-        raise ValueError(f"{where}: method 'BDPR' needs operator A in BSR form (generalized_eigensolver_bsr, "
-                         "DavidsonEngine.set_block_sparse)")
-    if gev and bb != ba:
-        raise ValueError(f"{where}: method 'BDPR' needs operator B in BSR form with the block size of A ({ba}), not "
-                         + ("another kind of operator" if bb is None else f"block size {bb}"))
-    if nranks > 1:
-        nslab = -(-(-(-n // nranks)) // 16) * 16
-        if nslab % ba != 0:
-            raise ValueError(f"{where}: method 'BDPR' on {nranks} ranks needs a block size that divides the {nslab} rows of a rank's "
-                             f"slab, not {ba}")
-
-
-def _cheb_degree(method):
-    """the degree of method "CHEB" / "CHEB<d>" (0 = the default), None when `method` is not such a string.  ValueError: a degree outside
-    1..64 - the Fortran doors stop the process on a name they do not know."""
-    if not isinstance(method, str) or not method.startswith("CHEB"):
-        return None
-    tail = method[4:]
-    if tail == "":
-        return 0
-    if not (tail.isascii() and tail.isdigit()) or not 1 <= int(tail) <= 64:
-        raise ValueError(f"method {method!r}: the degree of the Chebyshev correction is 'CHEB' (default) or 'CHEB<d>' with 1 <= d <= 64")
-    return int(tail)
-
-
-def _lcheb_degree(method):
-    """the degree of method "LCHEB" / "LCHEB<d>" (0 = the default), None when `method` is not such a string.  ValueError: a degree
-    outside 1..64, as _cheb_degree"""
-    if not isinstance(method, str) or not method.startswith("LCHEB"):
-        return None
-    tail = method[5:]
-    if tail == "":
-        return 0
-    if not (tail.isascii() and tail.isdigit()) or not 1 <= int(tail) <= 64:
-        raise ValueError(f"method {method!r}: the degree of the Chebyshev correction is 'LCHEB' (default) or 'LCHEB<d>' with 1 <= d <= 64")
-    return int(tail)
+def _parse_method(method):
+    """(kind, degree) of a method name: _METHOD's and _DEGREE_METHOD's codes (engine_c.METHOD_*), degree 0 = none given (the engine's
+    default); anything that is no method name: (2, 0) - the Fortran doors stop the process on a name they do not know.  ValueError: a
+    degree outside 1..64."""
+    for name in ("LCHEB", "CHEB"):
+        if isinstance(method, str) and method.startswith(name):
+            tail = method[len(name):]
+            if tail == "":
+                return _DEGREE_METHOD[name], 0
+            if not (tail.isascii() and tail.isdigit()) or not 1 <= int(tail) <= 64:
+                raise ValueError(f"method {method!r}: the degree of the Chebyshev correction is {name!r} (default) or '{name}<d>' with "
+                                 "1 <= d <= 64")
+            return _DEGREE_METHOD[name], int(tail)
+    return _METHOD.get(method, 2), 0
 
 
 def _method_code(method):
-    """the integer the doors take: _METHOD's, or 4 | degree << 8 for "CHEB" / "CHEB<d>" (engine_c.method_cheb), 5 | degree << 8 for
-    "LCHEB" / "LCHEB<d>" (engine_c.method_lcheb); unknown names: 2"""
-    d = _lcheb_degree(method)
-    if d is not None:
-        return 5 | (d << 8)
-    d = _cheb_degree(method)
-    return _METHOD.get(method, 2) if d is None else 4 | (d << 8)
+    """the integer the doors take (engine_c.method_code): kind | degree << 8; unknown names: 2"""
+    kind, degree = _parse_method(method)
+    return kind | degree << 8
 
 
-def _check_lcheb(method, gev=False, host_callbacks=False, where="generalized_eigensolver"):
-    """method "LCHEB" / "LCHEB<d>" (Chebyshev-filtered correction with a Lanczos bound) serves standard problems whose operator A the
-    engine applies on the device - every kind but a host callback.  The engine refuses anything else at the first correction and the
-    Fortran doors stop the process on an engine error, so the front ends refuse here (ValueError), before any engine call."""
-    if _lcheb_degree(method) is None:
-        return
-    if host_callbacks:
+def _check_method(method, *, a_sparse=False, blocks=None, gev=False, host_callbacks=False, n=0, nranks=1,
+                  where="generalized_eigensolver"):
+    """What a method does not serve, refused here (ValueError) before any engine call: the engine refuses it at the first correction and
+    the Fortran doors stop the process on an engine error.
+    "BDPR" (block-diagonal DPR) serves BSR operators only - A of any block size 1..16, B (generalized problems) of the same one, and
+    with several ranks a block size that divides the rows of a rank's slab.  blocks: the block sizes of A and B as the caller set them,
+    None = not a BSR operator; blocks=None: a front end that learns them only from its input leaves the check to the engine.
+    "CHEB" / "CHEB<d>" (Chebyshev-filtered correction) serves standard problems whose operator A is a CSR or BSR operator (a_sparse): its
+    spectral bound comes from the stored entries.
+    "LCHEB" / "LCHEB<d>" (the same correction with a Lanczos bound) serves standard problems whose operator A the engine applies on the
+    device - every kind but a host callback."""
+    kind, _ = _parse_method(method)
+    if kind == 3 and blocks is not None:
+        ba, bb = blocks
+        if ba is None:
+            raise ValueError(f"{where}: method 'BDPR' needs operator A in BSR form (generalized_eigensolver_bsr, "
+                             "DavidsonEngine.set_block_sparse)")
+        if gev and bb != ba:
+            raise ValueError(f"{where}: method 'BDPR' needs operator B in BSR form with the block size of A ({ba}), not "
+                             + ("another kind of operator" if bb is None else f"block size {bb}"))
+        if nranks > 1:
+            nslab = -(-(-(-n // nranks)) // 16) * 16
+            if nslab % ba != 0:
+                raise ValueError(f"{where}: method 'BDPR' on {nranks} ranks needs a block size that divides the {nslab} rows of a rank's "
+                                 f"slab, not {ba}")
+    if kind == 4 and not a_sparse:
+        raise ValueError(f"{where}: method {method!r} needs operator A in CSR or BSR form (generalized_eigensolver_sparse, "
+                         "generalized_eigensolver_bsr, DavidsonEngine.set_sparse / set_block_sparse)")
+    if kind == 5 and host_callbacks:
         raise ValueError(f"{where}: method {method!r} needs an operator A the engine applies on the device; host callbacks are not "
                          "served (DavidsonEngine.set_device_operator takes a device callback)")
-    if gev:
+    if kind in (4, 5) and gev:
         raise ValueError(f"{where}: method {method!r} serves standard problems only (the filter of a generalized problem would need "
                          "the inverse of B)")
+
+
+def _check_bdpr(method, blocks, gev=False, n=0, nranks=1, where="generalized_eigensolver"):
+    """_check_method for "BDPR" alone"""
+    if method == "BDPR":
+        _check_method(method, blocks=blocks, gev=gev, n=n, nranks=nranks, where=where)
 
 
 def _check_cheb(method, sparse_a, gev=False, where="generalized_eigensolver"):
-    """method "CHEB" / "CHEB<d>" (Chebyshev-filtered correction) serves standard problems whose operator A is a CSR or BSR operator: its
-    spectral bound comes from the stored entries.  The engine refuses anything else at the first correction and the Fortran doors stop
-    the process on an engine error, so the front ends refuse here (ValueError), before any engine call.  sparse_a: A was set in CSR or
-    BSR form."""
-    if _cheb_degree(method) is None:
-        return
-    if not sparse_a:
-        raise ValueError(f"{where}: method {method!r} needs operator A in CSR or BSR form (generalized_eigensolver_sparse, "
-                         "generalized_eigensolver_bsr, DavidsonEngine.set_sparse / set_block_sparse)")
-    if gev:
-        raise ValueError(f"{where}: method {method!r} serves standard problems only (the filter of a generalized problem would need "
-                         "the inverse of B)")
+    """_check_method for "CHEB" / "CHEB<d>" alone"""
+    if isinstance(method, str) and method.startswith("CHEB"):
+        _check_method(method, a_sparse=sparse_a, gev=gev, where=where)
+
+
+def _check_lcheb(method, gev=False, host_callbacks=False, where="generalized_eigensolver"):
+    """_check_method for "LCHEB" / "LCHEB<d>" alone"""
+    if isinstance(method, str) and method.startswith("LCHEB"):
+        _check_method(method, gev=gev, host_callbacks=host_callbacks, where=where)
 
 
 _CB = C.CFUNCTYPE(None, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
@@ -131,9 +122,7 @@ def _initial_vectors(x, n, lowest):
 def generalized_eigensolver(matrix, lowest, method, max_iterations, tolerance, max_dim_sub=None,
                             second_matrix=None, initial_vectors=None):
     """initial_vectors (n, g): the solve starts from these columns instead of unit vectors (Fortran: initial_vectors=)."""
-    _check_bdpr(method, (None, None))
-    _check_cheb(method, False)
-    _check_lcheb(method, second_matrix is not None)
+    _check_method(method, blocks=(None, None), gev=second_matrix is not None)
     lib = fortran_lib()
     iters = C.c_int(-1)
     evals = np.zeros(lowest)
@@ -191,9 +180,7 @@ def generalized_eigensolver_sparse(indptr, indices, data, lowest, method, max_it
     lower=True: only the entries with column <= row are given, for A and B.  initial_vectors (n, g): the solve starts from these
     columns instead of unit vectors.  diagonals=True: A and B are stored by their diagonals (csr_matrix(..., diagonals=.true.); a
     matrix that does not suit the storage is refused).  Returns (eigenvalues, eigenvectors, iters)."""
-    _check_bdpr(method, (None, None), where="generalized_eigensolver_sparse")
-    _check_cheb(method, True, second is not None, "generalized_eigensolver_sparse")
-    _check_lcheb(method, second is not None, where="generalized_eigensolver_sparse")
+    _check_method(method, a_sparse=True, blocks=(None, None), gev=second is not None, where="generalized_eigensolver_sparse")
     a = indptr if indices is None and data is None else (indptr, indices, data)
     if _is_device_csr(a) or _is_device_csr(second):
         # a matrix in device memory: an engine of its own, built on the GPU (DavidsonEngine.set_sparse)
@@ -255,8 +242,7 @@ def generalized_eigensolver_bsr(indptr, indices, data, lowest, method, max_itera
     (DavidsonEngine.set_block_sparse on the tensor's device).  lower=True: only the blocks with block column <= block row are given,
     for A and B.  n: the order (default: block rows x b).  initial_vectors (n, g): the solve starts from these columns instead of unit
     vectors.  Returns (eigenvalues, eigenvectors, iters)."""
-    _check_cheb(method, True, second is not None, "generalized_eigensolver_bsr")
-    _check_lcheb(method, second is not None, where="generalized_eigensolver_bsr")
+    _check_method(method, a_sparse=True, gev=second is not None, where="generalized_eigensolver_bsr")
     a = indptr if indices is None and data is None else (indptr, indices, data)
     if _is_device_bsr(a) or _is_device_bsr(second):
         # a matrix in device memory: an engine of its own, built on the GPU (DavidsonEngine.set_block_sparse)
@@ -299,8 +285,7 @@ def generalized_eigensolver_free(fun_matrix_gemv, n, lowest, method, max_iterati
                                  fun_second_matrix_gemv, initial_vectors=None):
     """Matrix-free specific with numpy callbacks X(n,k) -> Y(n,k) (reference: src/davidson.f90:277-337).  initial_vectors (n, g): the
     solve starts from these columns instead of unit vectors."""
-    _check_cheb(method, False, where="generalized_eigensolver_free")
-    _check_lcheb(method, True, True, "generalized_eigensolver_free")
+    _check_method(method, gev=True, host_callbacks=True, where="generalized_eigensolver_free")
     lib = fortran_lib()
 
     def wrap(fn):
@@ -541,12 +526,9 @@ class DavidsonEngine:
         set_block_sparse (ValueError otherwise, before the engine is called).  method "LCHEB" / "LCHEB<d>": the same correction with
         a Lanczos bound, for a standard problem whose A is anything the engine applies on the device - set_dense, set_device_operator,
         set_hashed_operator, set_sparse, set_block_sparse ... (a generalized problem: ValueError before the engine is called)."""
-        if _lcheb_degree(method) is not None:
-            _check_lcheb(method, self.gev, where="DavidsonEngine.solve")
-        if _cheb_degree(method) is not None:
-            _check_cheb(method, getattr(self, "_sparse", [False, False])[0], self.gev, "DavidsonEngine.solve")
-        if method == "BDPR":
-            _check_bdpr(method, getattr(self, "_blocks", [None, None]), self.gev, self.n, self.nranks, "DavidsonEngine.solve")
+        if _parse_method(method)[0] > 2:         # DPR, GJD and names that are none ask nothing of what the engine holds
+            _check_method(method, a_sparse=getattr(self, "_sparse", [False, False])[0], blocks=getattr(self, "_blocks", [None, None]),
+                          gev=self.gev, n=self.n, nranks=self.nranks, where="DavidsonEngine.solve")
         if reuse_vectors is not None:
             self.keep_result_as_guess(bool(reuse_vectors))
         if initial_vectors is not None:

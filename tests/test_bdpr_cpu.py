@@ -13,7 +13,6 @@ from fortran_davidson_amd import _abi, engine_c, solver
 import bdpr_inputs as I
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FSRC = os.path.join(ROOT, "fortran_davidson_amd", "fortran")
 LIBDIR = os.path.join(ROOT, "fortran_davidson_amd", "lib")
 
 
@@ -29,26 +28,10 @@ def test_the_method_code_is_three_in_every_layer():
     codes = {k: int(v) for k, v in re.findall(r"(DAV_METHOD_\w+)\s*=\s*(\d+)", enum)}
     assert codes == {"DAV_METHOD_DPR": 0, "DAV_METHOD_GJD": 1, "DAV_METHOD_NONE": 2, "DAV_METHOD_BDPR": 3}
     assert re.search(r"#define DAV_HIP_ABI_VERSION 109\b", hdr)
-    f90 = read(FSRC, "davidson_hip_c.f90")
-    params = {k: int(v) for k, v in re.findall(r"(DAV_METHOD_\w+)\s*=\s*(\d+)", f90)}
-    assert params == codes
     assert (engine_c.METHOD_DPR, engine_c.METHOD_GJD, engine_c.METHOD_BDPR) == (0, 1, 3)
     assert solver._METHOD == {"DPR": 0, "GJD": 1, "BDPR": 3}
-    api = read(FSRC, "davidson_c_api.f90")
-    body = re.search(r"function method_name\(code\).*?end function method_name", api, re.S).group(0)
-    assert re.search(r'if \(code == 3\) name = "BDPR"', body) and re.search(r"character\(len=4\)", body)
-    # the last assignment that applies to a code decides its name
-    names = {}
-    for code in range(4):
-        name = "DPR"
-        for cond, val in re.findall(r'if \(code (== \d+|> \d+)\) name = "(\w+)"', body):
-            if eval(f"{code} {cond}"):
-                name = val
-        names[code] = name
-    assert names == {0: "DPR", 1: "GJD", 2: "XXX", 3: "BDPR"}
-    drv = read(FSRC, "davidson.f90")
-    assert re.search(r'case \("BDPR"\)\s*\n(\s*!.*\n)*\s*meth = DAV_METHOD_BDPR', drv)
-    assert "(DPR, GJD or BDPR)" in drv
+    # (the Fortran parameters, the driver's parser, the names the doors hand it - 0: "DPR", 1: "GJD", 2: "XXX", 3: "BDPR" - and the
+    # driver's "(DPR, GJD or BDPR)" message: tests/test_methods_cpu.py, through the compiled module)
 
 
 def test_the_feature_adds_no_entry_point():

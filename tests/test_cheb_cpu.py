@@ -15,7 +15,6 @@ import bdpr_inputs as BI
 import cheb_inputs as I
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FSRC = os.path.join(ROOT, "fortran_davidson_amd", "fortran")
 CSRC = os.path.join(ROOT, "fortran_davidson_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "fortran_davidson_amd", "lib")
 
@@ -33,10 +32,7 @@ def test_the_method_code_is_four_and_carries_the_degree_in_every_layer():
     kern = read(CSRC, "kernels.h")
     assert re.search(r"CHEB_MAX_DEGREE = 64;", kern) and re.search(r"CHEB_DEFAULT_DEGREE = 10;", kern)
     assert I.DEFAULT_DEGREE == 10
-    # the engine splits the code before it compares it
-    eng = read(CSRC, "engine_solver.hip")
-    assert re.search(r"\(code & 0xff\) == DAV_METHOD_CHEB", read(CSRC, "engine_internal.h"))
-    assert eng.count("method_kind(") == 2 and re.search(r"method_code >> 8", eng)      # ritz_impl and dav_rr_ritz
+    # (the engine splits the code before it compares it: tests/test_exact_phases_gpu.py compares the codes with and without a degree)
     # Python
     assert engine_c.METHOD_CHEB == 4 and engine_c.method_cheb() == 4 and engine_c.method_cheb(16) == 4 | 16 << 8 == 4100
     assert solver._method_code("CHEB") == 4 and solver._method_code("CHEB1") == 260 and solver._method_code("CHEB64") == 4 | 64 << 8
@@ -44,18 +40,8 @@ def test_the_method_code_is_four_and_carries_the_degree_in_every_layer():
     for bad in ("CHEB0", "CHEB65", "CHEB-1", "CHEBx", "CHEB1.5", "CHEB 4"):
         with pytest.raises(ValueError, match="1 <= d <= 64"):
             solver._method_code(bad)
-    # Fortran: the parameter lives outside davidson_hip_c.f90, the driver parses the name, the doors carry the degree in the name
-    knobs = read(FSRC, "davidson_knobs.f90")
-    assert re.search(r"integer, parameter :: DAV_METHOD_CHEB = 4\b", knobs) and "code = DAV_METHOD_CHEB + 256 * d" in knobs
-    assert "DAV_METHOD_CHEB" not in read(FSRC, "davidson_hip_c.f90")
-    drv = read(FSRC, "davidson.f90")
-    assert "meth = cheb_method_code(trim(method))" in drv
-    assert "phase == DAV_METHOD_BDPR .or. method_kind(phase) == DAV_METHOD_CHEB" in drv
-    assert re.search(r"\(DPR, GJD or BDPR\)\", &\s*\n\s*\", or CHEB / CHEB<degree 1\.\.64>\"", drv)
-    api = read(FSRC, "davidson_c_api.f90")
-    body = re.search(r"function method_name\(code\).*?end function method_name", api, re.S).group(0)
-    assert re.search(r'if \(code > 3 \.and\. iand\(code, 255\) == 4\) name = "CHEB"', body)
-    assert "method_name(method)" not in api and api.count("method_label(method)") == 20
+    # (Fortran - the parameter, the driver's parser and its message, the DPR side of the loop, the names the doors carry the degree in:
+    # tests/test_methods_cpu.py, through the compiled module)
 
 
 def test_the_feature_adds_no_entry_point():

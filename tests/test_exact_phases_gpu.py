@@ -29,7 +29,9 @@ import numpy as np
 import pytest
 
 import fortran_davidson_amd as fd
-from fortran_davidson_amd.engine_c import METHOD_DPR, METHOD_GJD, OP_A, OP_B, PANEL_BV, PANEL_R, PANEL_V, PANEL_W, PANEL_X
+from fortran_davidson_amd.engine_c import (METHOD_CHEB, METHOD_DPR, METHOD_GJD, METHOD_LCHEB, METHOD_NONE, OP_A, OP_B, PANEL_BV, PANEL_R, PANEL_V,
+                                           PANEL_W, PANEL_X, method_cheb, method_lcheb)
+import cheb_inputs as CI
 from exact_inputs import (SENTINEL, GjdInputs, cols_alloc, dpr_diagonals, dpr_reference, fenced, gamma, gjd_error, gram_is_exact,
                           int_block, int_matrix, int_product, mismatch, ritz_inputs, ritz_reference, run_ranks, same_bits, unit_block)
 
@@ -222,6 +224,47 @@ def test_ritz_phase_is_exact_over_ranks(nranks):
     outs = run_ranks(nranks, lambda r: fd.CEngine(n=n, max_cols=shape[0] + shape[1], gev=gev, rank=r, nranks=nranks), work)
     for msgs in outs:
         assert not msgs, msgs
+
+
+# ---- A2. the method code ------------------------------------------------------------------------------------------------------------------
+def test_a_method_code_is_split_once_and_a_code_that_names_no_method_corrects_nothing():
+    """The Ritz phase of a CSR operator (n = 240, m = ncorr = 5, lowest = 4) under method codes that must mean the same: CHEB and LCHEB
+    without a degree are degree 10 bit for bit (norms, R, T).  A code that names no method - a degree above a low byte that takes none,
+    and a low byte no method has - is not refused: the phase returns 0, writes R and the norms as DAV_METHOD_NONE does and leaves the
+    columns of the correction block alone."""
+    n, m, lowest = 240, 5, 4
+    a = CI.random_sparse(n, 6.0 / n, 3, grade=0.5 / n)
+    v = np.asfortranarray(np.linalg.qr(np.random.default_rng(4).standard_normal((n, m)))[0])
+    w = np.asfortranarray(a @ v)
+    theta, y = np.linalg.eigh(v.T @ w)
+    mark = np.full((n, m), 3.25)
+
+    def phase(e, method):
+        e.panel_put(PANEL_V, m, mark)
+        e.panel_put(PANEL_R, 0, mark)
+        e.panel_put(PANEL_V, 0, v)
+        e.panel_put(PANEL_W, 0, w)
+        norms = e.ritz_residual_correction(m, lowest, y, theta, method)
+        return norms.reshape(1, -1), e.panel_get(PANEL_R, 0, m), e.panel_get(PANEL_V, m, m)
+
+    msgs = []
+    with fd.CEngine(n=n, max_cols=16) as e:
+        e.set_operator_csr(OP_A, *CI.csr_of(a))
+        none = phase(e, METHOD_NONE)
+        assert not same_bits(none[1], mark) and same_bits(none[2], mark) and np.isfinite(none[0]).all()
+        for name, default, ten, three in (("CHEB", METHOD_CHEB, method_cheb(10), method_cheb(3)),
+                                          ("LCHEB", METHOD_LCHEB, method_lcheb(10), method_lcheb(3))):
+            got, want, other = phase(e, default), phase(e, ten), phase(e, three)
+            for what, g, x in zip(("norms", "R", "T"), got, want):
+                _compare(msgs, f"{name} without a degree against degree 10, {what}", g, x)
+            _compare(msgs, f"{name}, R against DAV_METHOD_NONE's", got[1], none[1])
+            assert not same_bits(got[2], mark) and not same_bits(got[2], other[2]), name      # a block was written, and the degree counts
+        for code in (METHOD_DPR | 7 << 8, 6):
+            got = phase(e, code)
+            _compare(msgs, f"code {code}, norms against DAV_METHOD_NONE's", got[0], none[0])
+            _compare(msgs, f"code {code}, R against DAV_METHOD_NONE's", got[1], none[1])
+            _compare(msgs, f"code {code}, the columns of the correction block", got[2], mark)
+    assert not msgs, msgs
 
 
 # ---- B. orthogonalisation and projection ------------------------------------------------------------------------------------------------

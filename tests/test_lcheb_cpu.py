@@ -15,10 +15,8 @@ import cheb_inputs as CI
 import lcheb_inputs as I
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FSRC = os.path.join(ROOT, "fortran_davidson_amd", "fortran")
 CSRC = os.path.join(ROOT, "fortran_davidson_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "fortran_davidson_amd", "lib")
-FC = "/opt/rocm/lib/llvm/bin/flang"
 
 
 def read(*parts):
@@ -34,7 +32,6 @@ def test_the_method_code_is_five_and_carries_the_degree_in_every_layer():
     assert re.search(r"#define DAV_METHOD_LCHEB_DEGREE\(d\) \(5 \| \(\(d\) << 8\)\)", hdr)
     assert re.search(r"#define DAV_HIP_ABI_VERSION 109\b", hdr) and engine_c.ABI_VERSION == 109
     assert '"LCHEB correction: "' in hdr and "agree to\n * rounding, not to bits" in hdr
-    assert re.search(r"\(code & 0xff\) == DAV_METHOD_LCHEB", read(CSRC, "engine_internal.h"))
     assert re.search(r"LANCZOS_STEPS = 12;", read(CSRC, "kernels.h")) and I.STEPS == 12
     # Python
     assert engine_c.METHOD_LCHEB == 5 and engine_c.method_lcheb() == 5 and engine_c.method_lcheb(16) == 5 + 16 * 256 == 4101
@@ -44,33 +41,8 @@ def test_the_method_code_is_five_and_carries_the_degree_in_every_layer():
     for bad in ("LCHEB0", "LCHEB65", "LCHEB-1", "LCHEBx", "LCHEB1.5", "LCHEB 4"):
         with pytest.raises(ValueError, match="1 <= d <= 64"):
             solver._method_code(bad)
-    # Fortran: the parameter and the parser next to CHEB's, the driver takes the DPR side, the doors carry the degree in the name
-    knobs = read(FSRC, "davidson_knobs.f90")
-    assert re.search(r"integer, parameter :: DAV_METHOD_LCHEB = 5\b", knobs) and "function lcheb_method_code(method)" in knobs
-    assert "DAV_METHOD_LCHEB" not in read(FSRC, "davidson_hip_c.f90")
-    drv = read(FSRC, "davidson.f90")
-    assert "if (meth < 0) meth = lcheb_method_code(trim(method))" in drv
-    assert re.search(r"method_kind\(phase\) == DAV_METHOD_CHEB &\s*\n\s*\.or\. method_kind\(phase\) == DAV_METHOD_LCHEB\) then", drv)
-    api = read(FSRC, "davidson_c_api.f90")
-    body = re.search(r"function method_label\(code\).*?end function method_label", api, re.S).group(0)
-    assert re.search(r'if \(code > 3 \.and\. iand\(code, 255\) == 5\) then\s*\n\s*label = "LCHEB"', body)
-    assert api.count("method_label(method)") == 20
-
-
-@pytest.mark.skipif(not os.path.exists(FC), reason="flang not available")
-def test_the_fortran_parser_agrees_with_the_python_one(tmp_path):
-    """tests/fortran/prog_lcheb.f90 prints lcheb_method_code and cheb_method_code of a list of names"""
-    from test_fortran_programs import SRC, compile_link
-    exe = compile_link([os.path.join(SRC, "prog_lcheb.f90")], str(tmp_path / "prog_lcheb"), tmp_path)
-    out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout
-    got = {name: (int(a), int(b)) for name, a, b in re.findall(r"CODE (\S+)\s+(-?\d+)\s+(-?\d+)", out)}
-    want = {"LCHEB": (5, -1), "LCHEB16": (5 + 16 * 256, -1), "LCHEB1": (261, -1), "LCHEB64": (5 + 64 * 256, -1), "LCHEB0": (-1, -1),
-            "LCHEB65": (-1, -1), "LCHEBx": (-1, -1), "LCHEB123": (-1, -1), "CHEB": (-1, 4), "CHEB16": (-1, 4100), "LCHE": (-1, -1),
-            "DPR": (-1, -1)}
-    assert got == want
-    for name, (code, _) in want.items():
-        if code >= 0:
-            assert solver._method_code(name) == code
+    # (Fortran - the parameter, the parser, the DPR side of the loop, the names the doors carry the degree in: tests/test_methods_cpu.py,
+    # through the compiled module)
 
 
 def test_the_feature_adds_no_entry_point():
