@@ -450,7 +450,8 @@ int create_impl(E* e, int device, int64_t n, int max_cols, int gev, int rank, in
   for (int p = 0; p < 6; ++p)
     if (p != DAV_PANEL_BV || e->gev) off_panel[p] = carve(dev_total, pbytes);
   const size_t off_xt = carve(dev_total, sizeof(double) * e->xt_group_stride * 4);
-  const size_t off_diag0 = carve(dev_total, sizeof(double) * e->nloc_pad), off_diag1 = carve(dev_total, sizeof(double) * e->nloc_pad);
+  const size_t off_diag0 = carve(dev_total, sizeof(double) * e->nloc_pad), off_diag1 = carve(dev_total, sizeof(double) * e->nloc_pad),
+               off_diag2 = carve(dev_total, sizeof(double) * e->nloc_pad);
   const size_t off_counters = carve(dev_total, sizeof(unsigned) * (GRAM_MAX_COUNTERS + 8));
   const size_t zeroed = dev_total;                                  // everything up to here starts as zeros
   const size_t off_scratch = carve(dev_total, sizeof(double) * e->scratch_doubles);
@@ -486,6 +487,7 @@ int create_impl(E* e, int device, int64_t n, int max_cols, int gev, int rank, in
   e->xt = (double*)(e->arena + off_xt);
   e->op[0].diag = (double*)(e->arena + off_diag0);
   e->op[1].diag = (double*)(e->arena + off_diag1);
+  e->op[2].diag = (double*)(e->arena + off_diag2);
   e->counters = (unsigned*)(e->arena + off_counters);
   e->scratch = (double*)(e->arena + off_scratch);
   e->gram_dev = (double*)(e->arena + off_gram);
@@ -568,7 +570,7 @@ extern "C" int dav_destroy(dav_handle_t e) {
     if (e->ev[i][1]) hipEventDestroy(e->ev[i][1]);
   }
   lt.lap("wpart_events");
-  for (int w = 0; w < 2; ++w) {
+  for (int w = 0; w < N_OPS; ++w) {
     sym_resident_release(e->op[w]);
     pool_free(e->op[w].a);
     pool_free(e->op[w].a32);

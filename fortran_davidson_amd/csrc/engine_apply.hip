@@ -621,7 +621,7 @@ int apply_impl(E* e, int which, int src_panel, int c0, int k, int dst_panel, int
 }
 
 extern "C" int dav_apply(dav_handle_t e, int which, int src_panel, int c0, int k, int dst_panel, int d0) {
-  if (which < 0 || which > 1) return fail("dav_apply: bad operator id");
+  if (which < 0 || which >= N_OPS) return fail("dav_apply: bad operator id");
   CHK(bind(e));
   if (dst_panel == DAV_PANEL_X) guess_drop(e);
   return apply_impl(e, which, src_panel, c0, k, dst_panel, d0, true);
@@ -629,7 +629,7 @@ extern "C" int dav_apply(dav_handle_t e, int which, int src_panel, int c0, int k
 
 // dav_apply as the GJD correction solve issues it (csrc/davidson_hip_private.h): an inner sweep may read the fp32 copy of the tiles
 extern "C" int dav_apply_inner(dav_handle_t e, int which, int src_panel, int c0, int k, int dst_panel, int d0) {
-  if (which < 0 || which > 1) return fail("dav_apply_inner: bad operator id");
+  if (which < 0 || which >= N_OPS) return fail("dav_apply_inner: bad operator id");
   CHK(bind(e));
   if (dst_panel == DAV_PANEL_X) guess_drop(e);
   return apply_impl(e, which, src_panel, c0, k, dst_panel, d0, false, true);

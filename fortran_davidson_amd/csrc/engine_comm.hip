@@ -530,9 +530,13 @@ int coll_reduce_scatter(E* e, const double* send, double* recv, size_t count) {
 extern "C" int dav_agree_inputs(dav_handle_t e, const double* words, int nwords) {
   if (nwords <= 0 || nwords > 16 || !words) return fail("dav_agree_inputs: 1..16 words");
   if (e->nranks <= 1 || !has_comm(e)) return 0;
-  if ((int)e->agreed_inputs.size() == nwords && std::equal(words, words + nwords, e->agreed_inputs.begin())) return 0;
-  CHK(dav_ranks_agree(e, words, nwords));
-  e->agreed_inputs.assign(words, words + nwords);
+  // one more word behind the driver's: whether the preconditioner (slot M) is set - its applies are collective, so a rank without it
+  // would leave its peers in theirs
+  std::vector<double> all(words, words + nwords);
+  all.push_back(has_precond(e) ? 1.0 : 0.0);
+  if (all == e->agreed_inputs) return 0;
+  CHK(dav_ranks_agree(e, all.data(), (int)all.size()));
+  e->agreed_inputs = all;
   return 0;
 }
 

@@ -9,6 +9,7 @@
 // operator is the K1 block matvec: every inner step costs one sweep of A (and one of B) shared by all
 // m right-hand sides.  Inputs: X (Ritz vectors, m columns) and R (residues) as left by
 // dav_ritz_residual_correction(..., DAV_METHOD_GJD).  Output: T in V[:, m:2m].
+// With the caller's preconditioner set (slot M, DAV_OP_M) MINRES is preconditioned by M in place of the Jacobi diagonal.
 namespace {
 struct Gjd {
   E* e;
@@ -97,6 +98,14 @@ extern "C" int dav_gjd_correction_n(dav_handle_t e, int mbasis, int m, const dou
   CHK(small_upload(e, 0, th.data(), m, m, 1, &ld_th));
   const double* dA = e->op[DAV_OP_A].diag;
   const double* dB = gev ? e->op[DAV_OP_B].diag : nullptr;
+  // The caller's preconditioner (slot M) in place of the Jacobi diagonal: out = M in over the columns [c0, c1) that hold the active pairs.
+  // The other columns keep what they held: every coefficient that multiplies them below is zero.
+  const bool with_m = has_precond(e);
+  auto precond = [&](const double* in, double* out, int c0, int c1) -> int {
+    if (with_m) return apply_ptr(e, DAV_OP_M, in + (size_t)c0 * e->ldp, c1 - c0, out + (size_t)c0 * e->ldp, true);
+    launch_precond(e->stream, in, out, e->ldp, e->nloc, e->nloc_pad, m, e->sm[0].dev, dA, dB, e->sm[1].dev);
+    return 0;
+  };
 
   CHK(gjd_lincomb(g, r1, r1, &minus_one));                                     // b = -r
   CHK(gjd_lincomb(g, T, r1, &zero));                                           // t = 0
@@ -107,8 +116,8 @@ extern "C" int dav_gjd_correction_n(dav_handle_t e, int mbasis, int m, const dou
   // Jacobi preconditioner K = |diag(A) - theta_k diag(B)|, restricted to the complement of x_k:
   //   y = K^-1 r - (x^T K^-1 r / x^T K^-1 x) K^-1 x    (keeps every iterate orthogonal to x_k, so the
   //   null direction of the projected operator can never be amplified)
-  launch_precond(e->stream, X, mx, e->ldp, e->nloc, e->nloc_pad, m, e->sm[0].dev, dA, dB, e->sm[1].dev);
-  launch_precond(e->stream, r1, y, e->ldp, e->nloc, e->nloc_pad, m, e->sm[0].dev, dA, dB, e->sm[1].dev);
+  CHK(precond(X, mx, 0, m));
+  CHK(precond(r1, y, 0, m));
   {
     const double* a[4] = {X, X, r1, r1}; const double* b[4] = {mx, y, y, mx};
     CHK(gjd_dots(g, 4, a, b, res));
@@ -118,6 +127,10 @@ extern "C" int dav_gjd_correction_n(dav_handle_t e, int mbasis, int m, const dou
   for (int j = 0; j < m; ++j) {
     cy[j] = xmx[j] > 0 ? -res[1][j] / xmx[j] : 0.0;
     double b2 = res[2][j] + cy[j] * res[3][j];
+    // all that is checked of M: MINRES needs a positive definite preconditioner.  Only T, R and the workspace have been written
+    if (with_m && (!(xmx[j] > 0.0) || b2 < 0.0))
+      return fail("dav_gjd_correction: the preconditioner M (DAV_OP_M) is not positive definite: column " + std::to_string(j) + " has x^T M x = " +
+                  std::to_string(xmx[j]) + ", r^T y = " + std::to_string(b2));
     beta1[j] = b2 > 0 ? std::sqrt(b2) : 0.0;
     beta[j] = phibar[j] = beta1[j];
     if (!(beta1[j] > 0.0)) active[j] = 0.0;
@@ -194,7 +207,7 @@ extern "C" int dav_gjd_correction_n(dav_handle_t e, int mbasis, int m, const dou
     // rotate: r1 <- r2, r2 <- y, y <- (old r1 storage)
     { double* t = r1; r1 = r2; r2 = y; y = t; }
     CHK(small_upload(e, 1, active.data(), m, m, 1, &ld_act));
-    launch_precond(e->stream, r2, y, e->ldp, e->nloc, e->nloc_pad, m, e->sm[0].dev, dA, dB, e->sm[1].dev);
+    CHK(precond(r2, y, c_lo, c_hi));
     {
       const double* a[3] = {X, r2, r2}; const double* b[3] = {y, y, mx};
       CHK(gjd_dots(g, 3, a, b, res));

@@ -208,6 +208,7 @@ struct SmallBuf {            // device small matrix + pinned staging
   bool pending = false;
 };
 
+constexpr int N_OPS = 3;     // operator slots: DAV_OP_A, DAV_OP_B, DAV_OP_M
 constexpr int N_SMALL = 4;
 constexpr int N_EVPAIRS = 64;
 
@@ -338,9 +339,9 @@ struct dav_engine {
   int comm_ranks = 0;             // ncclCommCount of `comm`
   LocalGroup* lg = nullptr;       // loopback transport (tests); owned by rank 0
   ShmGroup* shm = nullptr;        // shared-memory transport (tests of the multi-process launch flow)
-  OpDesc op[2];
-  int keep_map[2] = {0, 0};           // dav_keep_value_map: the next sparse set call of the slot keeps its value map
-  std::vector<double> diag_host[2];
+  OpDesc op[N_OPS];                   // A, B and the caller's preconditioner M (sparse, device callback or identity only)
+  int keep_map[N_OPS] = {0, 0, 0};    // dav_keep_value_map: the next sparse set call of the slot keeps its value map
+  std::vector<double> diag_host[N_OPS];
   std::vector<int64_t> basis_order;   // indices of the smallest diagonal entries of A (cache of dav_init_basis)
   // streaming ingest (dav_dense_begin .. dav_dense_end): two pinned row-major staging buffers + device twins
   double* ing_host[2] = {nullptr, nullptr};
@@ -493,6 +494,9 @@ int ingest_commit(E* e, int64_t row0, int64_t nrows);
 void ingest_wanted(E* e, int64_t* first, int64_t* count);
 OpParams op_params(const OpDesc& o);
 int operator_goes(E* e, int which, bool unset = false);
+int refuse_slot_m(const char* name);     // the entries that serve A and B only: non-zero, with a message that names DAV_OP_M
+// slot M holds the caller's preconditioner: DPR and GJD apply it in place of the diagonal (engine_solver.hip, engine_gjd.hip)
+static inline bool has_precond(const E* e) { return e->op[DAV_OP_M].kind != DAV_KIND_NONE; }
 // ---- engine_sparse.hip -----------------------------------------------------------------------------------
 void sparse_release(E* e, OpDesc& o);
 bool device_array(E* e, const void* p, const char* name, size_t bytes, std::string* why);

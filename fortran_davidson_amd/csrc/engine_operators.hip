@@ -263,6 +263,10 @@ int operator_goes(E* e, int which, bool unset) {
   return 0;
 }
 
+int refuse_slot_m(const char* name) {
+  return fail(std::string(name) + ": DAV_OP_M (the preconditioner) takes a CSR, BSR, device or identity operator only");
+}
+
 int alloc_dense(E* e, int which) {
   OpDesc& o = e->op[which];
   CHK(operator_goes(e, which));
@@ -315,6 +319,7 @@ extern "C" int dav_set_storage(dav_handle_t e, int mode) {
 }
 
 int set_dense_from(E* e, int which, const double* a, int64_t lda, hipMemcpyKind kind) {
+  if (which == DAV_OP_M) return refuse_slot_m("dav_set_dense");
   if (which < 0 || which > 1 || !a || lda < e->n) return fail("dav_set_dense: bad arguments");
   CHK(bind(e));
   CHK(alloc_dense(e, which));
@@ -396,6 +401,7 @@ void ingest_release(E* e) {
 }
 
 extern "C" int dav_dense_begin(dav_handle_t e, int which) {
+  if (which == DAV_OP_M) return refuse_slot_m("dav_dense_begin");
   if (which < 0 || which > 1) return fail("dav_dense_begin: bad operator id");
   if (e->ing_which >= 0) return fail("dav_dense_begin: another streaming upload is open (call dav_dense_end)");
   CHK(bind(e));
@@ -451,6 +457,7 @@ void ingest_wanted(E* e, int64_t* first, int64_t* count) {
 }
 
 extern "C" int dav_dense_put_rows(dav_handle_t e, int which, int64_t row0, int64_t nrows, const double* rows, int64_t ldr) {
+  if (which == DAV_OP_M) return refuse_slot_m("dav_dense_put_rows");
   if (e->ing_which != which) return fail("dav_dense_put_rows: no streaming upload open for this operator");
   if (!rows || ldr < e->n || row0 < 0 || nrows < 0 || row0 + nrows > e->n) return fail("dav_dense_put_rows: bad arguments");
   int64_t w0, wn;
@@ -481,6 +488,7 @@ extern "C" int dav_dense_put_rows(dav_handle_t e, int which, int64_t row0, int64
 }
 
 extern "C" int dav_dense_end(dav_handle_t e, int which) {
+  if (which == DAV_OP_M) return refuse_slot_m("dav_dense_end");
   if (e->ing_which != which) return fail("dav_dense_end: no streaming upload open for this operator");
   CHK(bind(e));
   OpDesc& o = e->op[which];
@@ -506,6 +514,7 @@ struct EngineSink : IngestSink {
 extern "C" int dav_set_dense_file(dav_handle_t e, int which, const char* path, int format) {
   if (!path) return fail("dav_set_dense_file: null path");
   if (format != DAV_FILE_TEXT && format != DAV_FILE_F64) return fail("dav_set_dense_file: unknown format");
+  if (which == DAV_OP_M) return refuse_slot_m("dav_set_dense_file");
   CHK(dav_dense_begin(e, which));
   EngineSink sink(e);
   std::string err;
@@ -531,6 +540,7 @@ extern "C" int dav_parse_text_f64(const char* text, size_t len, double* out, siz
 
 extern "C" int dav_set_dense_generated(dav_handle_t e, int which, uint64_t seed, double sparsity, int use_diag_val,
                                        double diag_val) {
+  if (which == DAV_OP_M) return refuse_slot_m("dav_set_dense_generated");
   if (which < 0 || which > 1) return fail("dav_set_dense_generated: bad operator id");
   CHK(bind(e));
   CHK(alloc_dense(e, which));
@@ -557,6 +567,7 @@ OpParams op_params(const OpDesc& o) {
 
 extern "C" int dav_set_operator_hashed(dav_handle_t e, int which, uint64_t seed, double sparsity, int use_diag_val,
                                        double diag_val) {
+  if (which == DAV_OP_M) return refuse_slot_m("dav_set_operator_hashed");
   if (which < 0 || which > 1) return fail("dav_set_operator_hashed: bad operator id");
   CHK(bind(e));
   OpDesc& o = e->op[which];
@@ -572,6 +583,7 @@ extern "C" int dav_set_operator_hashed(dav_handle_t e, int which, uint64_t seed,
 }
 
 extern "C" int dav_set_operator_harness(dav_handle_t e, int which, const double* e_table) {
+  if (which == DAV_OP_M) return refuse_slot_m("dav_set_operator_harness");
   if (which < 0 || which > 1 || !e_table) return fail("dav_set_operator_harness: bad arguments");
   CHK(bind(e));
   OpDesc& o = e->op[which];
@@ -617,7 +629,7 @@ extern "C" int dav_set_operator_harness(dav_handle_t e, int which, const double*
 }
 
 extern "C" int dav_set_operator_identity(dav_handle_t e, int which) {
-  if (which < 0 || which > 1) return fail("dav_set_operator_identity: bad operator id");
+  if (which < 0 || which >= N_OPS) return fail("dav_set_operator_identity: bad operator id");
   CHK(bind(e));
   OpDesc& o = e->op[which];
   CHK(operator_goes(e, which));
@@ -628,6 +640,7 @@ extern "C" int dav_set_operator_identity(dav_handle_t e, int which) {
 }
 
 extern "C" int dav_set_operator_host(dav_handle_t e, int which, const double* diag) {
+  if (which == DAV_OP_M) return refuse_slot_m("dav_set_operator_host");
   if (which < 0 || which > 1 || !diag) return fail("dav_set_operator_host: bad arguments");
   CHK(bind(e));
   OpDesc& o = e->op[which];
@@ -642,8 +655,13 @@ extern "C" int dav_set_operator_host(dav_handle_t e, int which, const double* di
 }
 
 extern "C" int dav_set_operator_device(dav_handle_t e, int which, dav_device_apply_fn fn, void* ctx, const double* diag) {
-  if (which < 0 || which > 1 || !diag || !fn) return fail("dav_set_operator_device: bad arguments");
-  CHK(dav_set_operator_host(e, which, diag));          // the diagonal: device slab, host copy, start-vector order
+  if (which < 0 || which >= N_OPS || (!diag && which != DAV_OP_M) || !fn) return fail("dav_set_operator_device: bad arguments");
+  if (which == DAV_OP_M) {                             // the preconditioner's diagonal is never read: none is kept
+    CHK(bind(e));
+    CHK(operator_goes(e, which, true));
+  } else {
+    CHK(dav_set_operator_host(e, which, diag));        // the diagonal: device slab, host copy, start-vector order
+  }
   OpDesc& o = e->op[which];
   o.kind = DAV_KIND_DEVICE;
   o.dev_fn = fn;
@@ -652,7 +670,7 @@ extern "C" int dav_set_operator_device(dav_handle_t e, int which, dav_device_app
 }
 
 extern "C" int dav_get_diagonal(dav_handle_t e, int which, double* out) {
-  if (which < 0 || which > 1 || e->diag_host[which].empty()) return fail("dav_get_diagonal: operator not set");
+  if (which < 0 || which >= N_OPS || e->diag_host[which].empty()) return fail("dav_get_diagonal: operator not set");
   std::memcpy(out, e->diag_host[which].data(), sizeof(double) * e->n);
   return 0;
 }

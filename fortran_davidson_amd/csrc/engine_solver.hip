@@ -297,6 +297,8 @@ int ritz_impl(E* e, int m, int ncorr, int lowest, const double* Y, int64_t ldy, 
     case DAV_METHOD_LCHEB: CHK(cheb_prepare(e, spec)); break;
     default: break;
   }
+  // DPR with the caller's preconditioner set (slot M): T = M R by a block product behind the residues, in place of epilogue 1
+  const bool dpr_m = method == DAV_METHOD_DPR && has_precond(e);
   const double *dY, *dY2, *dTheta;
   int64_t ldm_y, ldm_y2;
   std::vector<double> y2;
@@ -337,7 +339,7 @@ int ritz_impl(E* e, int m, int ncorr, int lowest, const double* Y, int64_t ldy, 
   r.nnorm = lowest; r.norm_partial = e->norm_partial;
   const bool fuse_norms = e->nloc_pad / PG_ROWS <= PG_FUSE_BLOCKS;     // small grids: the last workgroup sums the partial norms itself
   if (fuse_norms) { r.norm_out = result_target(e); r.counter = e->counters + GRAM_MAX_COUNTERS; }
-  if (method == DAV_METHOD_DPR) {
+  if (method == DAV_METHOD_DPR && !dpr_m) {
     r.out = panel_ptr(e, DAV_PANEL_V, m); r.ldo = e->ldp; r.epilogue = 1;
   } else {
     r.out = panel_ptr(e, DAV_PANEL_R, 0); r.ldo = e->ldp; r.epilogue = 2;
@@ -352,6 +354,13 @@ int ritz_impl(E* e, int m, int ncorr, int lowest, const double* Y, int64_t ldy, 
       // around them, because event pairs are collected only while none is open and a correction of a high degree has more than fit
       CHK(timed_end(e, slot));
       CHK(cheb_correct(e, spec, m, ncorr, lowest, dTheta));
+      CHK(timed_begin(e, 2, 0, &slot));
+      break;
+    case DAV_METHOD_DPR:
+      if (!dpr_m) break;
+      // T = M R into V[:, m:m+ncorr]: one block product, timed and counted like any apply, the phase's pair closed around it as above
+      CHK(timed_end(e, slot));
+      CHK(apply_ptr(e, DAV_OP_M, panel_ptr(e, DAV_PANEL_R, 0), ncorr, panel_ptr(e, DAV_PANEL_V, m), true));
       CHK(timed_begin(e, 2, 0, &slot));
       break;
     default: break;

@@ -77,7 +77,7 @@ struct Entry {
 
 int entry_begin(E* e, int which, const char* name) {
   if (!e) return fail(std::string(name) + ": null engine");
-  if (which < 0 || which > 1) return fail(std::string(name) + ": bad operator id");
+  if (which < 0 || which >= N_OPS) return fail(std::string(name) + ": bad operator id");
   return bind(e);
 }
 
@@ -722,7 +722,7 @@ extern "C" int dav_set_operator_bsr_dev(dav_handle_t e, int which, int block_siz
 // left with the operator.  rp, col, the work list, the partial slots and the maps are read or left alone, never written.
 extern "C" int dav_keep_value_map(dav_handle_t e, int which, int on) {
   if (!e) return fail("dav_keep_value_map: null engine");
-  if (which < 0 || which > 1) return fail("dav_keep_value_map: bad operator id");
+  if (which < 0 || which >= N_OPS) return fail("dav_keep_value_map: bad operator id");
   e->keep_map[which] = on != 0 ? 1 : 0;
   return 0;
 }

@@ -9,6 +9,10 @@ import numpy as np
 from ._lib import hip_lib
 
 OP_A, OP_B = 0, 1
+# DAV_OP_M: the caller's preconditioner, an approximation of (A - sigma B)^-1 that DPR and GJD apply (include/davidson_hip.h).  The sparse,
+# device-callback and identity entries, keep_value_map / update_operator_values / get_diagonal and apply(_inner) take it; the dense, hashed,
+# harness and host entries refuse it (DavidsonHipError naming DAV_OP_M).  BDPR, CHEB and LCHEB do not read it; there is no unset.
+OP_M = 2
 PANEL_V, PANEL_W, PANEL_BV, PANEL_X, PANEL_R, PANEL_S = range(6)
 # the method codes (the header's DAV_METHOD_*); a new method is one row here
 METHOD_DPR, METHOD_GJD, METHOD_NONE = 0, 1, 2
@@ -486,11 +490,14 @@ class CEngine:
 
     def set_operator_device(self, which, fn, ctx, diag):
         """The caller's own block apply on device memory (dav_device_apply_fn): `fn` a ctypes function pointer (DEVICE_APPLY_FN or a
-        symbol of a loaded library), `ctx` an integer / c_void_p passed through, `diag` the operator's diagonal (n)."""
-        d = np.ascontiguousarray(diag, dtype=np.float64)
+        symbol of a loaded library), `ctx` an integer / c_void_p passed through, `diag` the operator's diagonal (n) - for which = OP_M it
+        is not read and may be None."""
+        if diag is None and which != OP_M:
+            raise ValueError("set_operator_device: only the preconditioner (which = OP_M) goes without its diagonal")
+        d = None if diag is None else np.ascontiguousarray(diag, dtype=np.float64)
         self._device_ops = getattr(self, "_device_ops", {})
         self._device_ops[which] = (fn, ctx)                # keep the callback alive as long as the engine
-        self._chk(self.lib.dav_set_operator_device(self.h, which, fn, ctx, _dp(d)))
+        self._chk(self.lib.dav_set_operator_device(self.h, which, fn, ctx, None if d is None else _dp(d)))
 
     def set_operator_csr(self, which, indptr, indices=None, data=None, base=0, lower=False, diagonals=False):
         """dav_set_operator_csr: a symmetric matrix in CSR form (the global arrays; indptr / indices numbered from `base`), every nonzero

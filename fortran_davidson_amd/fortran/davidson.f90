@@ -1254,17 +1254,21 @@ module davidson_csr
   implicit none
   private
   public :: generalized_eigensolver_sparse, generalized_eigensolver_bsr, generalized_eigensolver_sparse_guess, generalized_eigensolver_bsr_guess
+  public :: generalized_eigensolver_sparse_precond_csr, generalized_eigensolver_sparse_precond_bsr, generalized_eigensolver_bsr_precond_csr, &
+       generalized_eigensolver_bsr_precond_bsr
 
 contains
 
   !> Sparse front-end: the argument list of generalized_eigensolver_dense with csr_matrix operators (module davidson_sparse).  The
   !> matrices go to HBM as CSR rows, are solved there with the engine's CSR kernel and are released before returning.
   subroutine sparse_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
-       tolerance, iters, max_dim_sub, second_matrix, initial_vectors)
+       tolerance, iters, max_dim_sub, second_matrix, initial_vectors, precond_csr, precond_bsr)
     integer, intent(in) :: lowest
     real(dp), dimension(:, :), intent(in), optional :: initial_vectors
     type(csr_matrix), intent(in) :: matrix
     type(csr_matrix), intent(in), optional :: second_matrix
+    type(csr_matrix), intent(in), optional :: precond_csr      !< preconditioner= of the front ends: slot 3 of the engine
+    type(bsr_matrix), intent(in), optional :: precond_bsr
     real(dp), dimension(lowest), intent(out) :: eigenvalues
     real(dp), dimension(:, :), intent(out) :: eigenvectors
     integer, intent(in) :: max_iterations
@@ -1281,6 +1285,8 @@ contains
     call engine_create(eng, matrix%n, lowest, max_dim, present(second_matrix), env_device())
     call engine_set_sparse(eng, 1, matrix)
     if (present(second_matrix)) call engine_set_sparse(eng, 2, second_matrix)
+    if (present(precond_csr)) call engine_set_sparse(eng, 3, precond_csr)
+    if (present(precond_bsr)) call engine_set_sparse(eng, 3, precond_bsr)
     call device_solve_impl(eng, eigenvalues, eigenvectors, lowest, method, max_iterations, &
          tolerance, iters, max_dim, initial_vectors)
     call engine_destroy(eng)
@@ -1325,11 +1331,13 @@ contains
   !> Block-sparse front-end: the same argument list with bsr_matrix operators (module davidson_sparse).  The matrices go to HBM as
   !> blocks, are solved there with the engine's matrix-core BSR kernel and are released before returning.
   subroutine bsr_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
-       tolerance, iters, max_dim_sub, second_matrix, initial_vectors)
+       tolerance, iters, max_dim_sub, second_matrix, initial_vectors, precond_csr, precond_bsr)
     integer, intent(in) :: lowest
     real(dp), dimension(:, :), intent(in), optional :: initial_vectors
     type(bsr_matrix), intent(in) :: matrix
     type(bsr_matrix), intent(in), optional :: second_matrix
+    type(csr_matrix), intent(in), optional :: precond_csr      !< preconditioner= of the front ends: slot 3 of the engine
+    type(bsr_matrix), intent(in), optional :: precond_bsr
     real(dp), dimension(lowest), intent(out) :: eigenvalues
     real(dp), dimension(:, :), intent(out) :: eigenvectors
     integer, intent(in) :: max_iterations
@@ -1346,6 +1354,8 @@ contains
     call engine_create(eng, matrix%n, lowest, max_dim, present(second_matrix), env_device())
     call engine_set_sparse(eng, 1, matrix)
     if (present(second_matrix)) call engine_set_sparse(eng, 2, second_matrix)
+    if (present(precond_csr)) call engine_set_sparse(eng, 3, precond_csr)
+    if (present(precond_bsr)) call engine_set_sparse(eng, 3, precond_bsr)
     call device_solve_impl(eng, eigenvalues, eigenvectors, lowest, method, max_iterations, &
          tolerance, iters, max_dim, initial_vectors)
     call engine_destroy(eng)
@@ -1387,6 +1397,90 @@ contains
          max_dim_sub, second_matrix, initial_vectors)
   end subroutine generalized_eigensolver_bsr_guess
 
+  !> The same with preconditioner= (keyword; not in the reference), a csr_matrix: the caller's approximation of (A - sigma B)^-1, which
+  !> "DPR" and "GJD" apply in place of the diagonal (slot 3 of the engine: engine_set_identity says what it must be).  initial_vectors=
+  !> may accompany it.  A specific of its own, as for initial_vectors=.
+  subroutine generalized_eigensolver_sparse_precond_csr(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix, preconditioner, initial_vectors)
+    integer, intent(in) :: lowest
+    type(csr_matrix), intent(in) :: matrix
+    type(csr_matrix), intent(in), optional :: second_matrix
+    real(dp), dimension(:, :), intent(out) :: eigenvectors
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    type(csr_matrix), intent(in) :: preconditioner
+    real(dp), dimension(:, :), intent(in), optional :: initial_vectors
+    call sparse_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub, second_matrix, initial_vectors, precond_csr=preconditioner)
+  end subroutine generalized_eigensolver_sparse_precond_csr
+
+  !> The same with preconditioner= (keyword; not in the reference), a bsr_matrix: the caller's approximation of (A - sigma B)^-1, which
+  !> "DPR" and "GJD" apply in place of the diagonal (slot 3 of the engine: engine_set_identity says what it must be).  initial_vectors=
+  !> may accompany it.  A specific of its own, as for initial_vectors=.
+  subroutine generalized_eigensolver_sparse_precond_bsr(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix, preconditioner, initial_vectors)
+    integer, intent(in) :: lowest
+    type(csr_matrix), intent(in) :: matrix
+    type(csr_matrix), intent(in), optional :: second_matrix
+    real(dp), dimension(:, :), intent(out) :: eigenvectors
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    type(bsr_matrix), intent(in) :: preconditioner
+    real(dp), dimension(:, :), intent(in), optional :: initial_vectors
+    call sparse_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub, second_matrix, initial_vectors, precond_bsr=preconditioner)
+  end subroutine generalized_eigensolver_sparse_precond_bsr
+
+  !> The same with preconditioner= (keyword; not in the reference), a csr_matrix: the caller's approximation of (A - sigma B)^-1, which
+  !> "DPR" and "GJD" apply in place of the diagonal (slot 3 of the engine: engine_set_identity says what it must be).  initial_vectors=
+  !> may accompany it.  A specific of its own, as for initial_vectors=.
+  subroutine generalized_eigensolver_bsr_precond_csr(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix, preconditioner, initial_vectors)
+    integer, intent(in) :: lowest
+    type(bsr_matrix), intent(in) :: matrix
+    type(bsr_matrix), intent(in), optional :: second_matrix
+    real(dp), dimension(:, :), intent(out) :: eigenvectors
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    type(csr_matrix), intent(in) :: preconditioner
+    real(dp), dimension(:, :), intent(in), optional :: initial_vectors
+    call bsr_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub, second_matrix, initial_vectors, precond_csr=preconditioner)
+  end subroutine generalized_eigensolver_bsr_precond_csr
+
+  !> The same with preconditioner= (keyword; not in the reference), a bsr_matrix: the caller's approximation of (A - sigma B)^-1, which
+  !> "DPR" and "GJD" apply in place of the diagonal (slot 3 of the engine: engine_set_identity says what it must be).  initial_vectors=
+  !> may accompany it.  A specific of its own, as for initial_vectors=.
+  subroutine generalized_eigensolver_bsr_precond_bsr(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix, preconditioner, initial_vectors)
+    integer, intent(in) :: lowest
+    type(bsr_matrix), intent(in) :: matrix
+    type(bsr_matrix), intent(in), optional :: second_matrix
+    real(dp), dimension(:, :), intent(out) :: eigenvectors
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    type(bsr_matrix), intent(in) :: preconditioner
+    real(dp), dimension(:, :), intent(in), optional :: initial_vectors
+    call bsr_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub, second_matrix, initial_vectors, precond_bsr=preconditioner)
+  end subroutine generalized_eigensolver_bsr_precond_bsr
+
 end module davidson_csr
 
 
@@ -1398,7 +1492,8 @@ module davidson
        engine_set_initial_vectors_device, engine_keep_result_as_guess
   use davidson_sparse, only: csr_matrix, bsr_matrix
   use davidson_csr, only: generalized_eigensolver_sparse, generalized_eigensolver_bsr, generalized_eigensolver_sparse_guess, &
-       generalized_eigensolver_bsr_guess
+       generalized_eigensolver_bsr_guess, generalized_eigensolver_sparse_precond_csr, generalized_eigensolver_sparse_precond_bsr, &
+       generalized_eigensolver_bsr_precond_csr, generalized_eigensolver_bsr_precond_bsr
   implicit none
   private
   public :: generalized_eigensolver, davidson_free_buffers, csr_matrix, bsr_matrix, engine_set_initial_vectors, &
@@ -1417,6 +1512,10 @@ module davidson
      procedure generalized_eigensolver_device_guess
      procedure generalized_eigensolver_sparse_guess
      procedure generalized_eigensolver_bsr_guess
+     procedure generalized_eigensolver_sparse_precond_csr
+     procedure generalized_eigensolver_sparse_precond_bsr
+     procedure generalized_eigensolver_bsr_precond_csr
+     procedure generalized_eigensolver_bsr_precond_bsr
   end interface generalized_eigensolver
 
 end module davidson

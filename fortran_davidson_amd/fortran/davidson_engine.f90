@@ -301,6 +301,13 @@ contains
     if (which == 1) eng%free_semantics = .true.
   end subroutine engine_set_harness_operator
 
+  !> B = I (which = 2) - or the preconditioner M = I (which = 3).
+  !> Slot 3 (DAV_OP_M of include/davidson_hip.h, which says what M must be) holds the caller's preconditioner: an approximation of
+  !> (A - sigma B)^-1 that "DPR" (T = M R) and "GJD" (the preconditioner of its MINRES) apply in place of the diagonal; "BDPR", "CHEB" and
+  !> "LCHEB" do not read it.  It is set through engine_set_sparse, engine_set_sparse_device, engine_set_block_sparse_device,
+  !> engine_set_device_operator and this routine, refreshed through engine_keep_value_map / engine_update_sparse_values(_device), replaced
+  !> by setting it again and never unset.  Every other engine_set_* / engine_read_matrix / engine_dense_* / engine_generate_* routine
+  !> stops with the engine's message when it is handed which = 3.
   subroutine engine_set_identity(eng, which)
     type(davidson_engine), intent(inout) :: eng
     integer, intent(in) :: which
@@ -311,13 +318,14 @@ contains
   !> (src/davidson.f90:277-337 takes a procedure on host arrays).  `fn` = c_funloc of a bind(C) function with the signature
   !> dav_device_apply_fn of include/davidson_hip.h - it enqueues Y = Op(row0 : row0 + nloc, :) X on the stream it is handed (its own
   !> HIP kernels, hipBLAS, ...) - `ctx` is passed through to it, `diag` is the operator's diagonal (n entries).
+  !> which = 3: the preconditioner M (see engine_set_identity); its diagonal is not read, an array of any size will do.
   subroutine engine_set_device_operator(eng, which, fn, ctx, diag)
     type(davidson_engine), intent(inout) :: eng
     integer, intent(in) :: which
     type(c_funptr), intent(in) :: fn
     type(c_ptr), intent(in) :: ctx
     real(dp), intent(in) :: diag(:)
-    if (size(diag) /= eng%n) then
+    if (size(diag) /= eng%n .and. which /= 3) then
        print *, "engine_set_device_operator: diag must have n entries"
        error stop
     end if

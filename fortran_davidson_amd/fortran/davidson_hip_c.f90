@@ -7,6 +7,7 @@ module davidson_hip_c
   public
 
   integer(c_int), parameter :: DAV_OP_A = 0, DAV_OP_B = 1
+  integer(c_int), parameter :: DAV_OP_M = 2   ! the caller's preconditioner (the engine_* routines number the slots from 1: which = 3)
   integer(c_int), parameter :: DAV_PANEL_V = 0, DAV_PANEL_W = 1, DAV_PANEL_BV = 2, DAV_PANEL_X = 3, &
        DAV_PANEL_R = 4, DAV_PANEL_S = 5
   !> dav_panel_unit_column: "the engine keeps no such entry of the start order" (not an error)

@@ -65,7 +65,7 @@ module davidson_sparse
 
 contains
 
-  !> Sticky switch of operator A (which = 1) or B (which = 2): with on = .true. the NEXT engine_set_sparse / engine_set_sparse_device /
+  !> Sticky switch of operator A (which = 1), B (which = 2) or the preconditioner M (which = 3): with on = .true. the NEXT engine_set_sparse / engine_set_sparse_device /
   !> engine_set_block_sparse_device call for that operator also keeps where every stored value came from (8 bytes per entry or block of
   !> this rank, 16 per row or block row of the matrix), so that engine_update_sparse_values can move new numbers into the kept pattern.
   !> It has no effect on an operator that is already set.
@@ -76,7 +76,7 @@ contains
     call check_dav(dav_keep_value_map(eng%h, int(which - 1, c_int), merge(1_c_int, 0_c_int, on)), "dav_keep_value_map")
   end subroutine engine_keep_value_map
 
-  !> New values of operator A (which = 1) or B (which = 2), a sparse operator set after engine_keep_value_map: values has the length and
+  !> New values of operator A (which = 1), B (which = 2) or the preconditioner M (which = 3), a sparse operator set after engine_keep_value_map: values has the length and
   !> order of the values of the set call (for a BSR operator its blocks one after the other, each as the set call had them).  The
   !> pattern is not touched; values, diagonal, applies and solves equal bit for bit what a fresh engine_set_sparse with these values
   !> gives.  The array is free again when the call returns.
@@ -147,7 +147,7 @@ contains
     if (present(diagonals)) a%diagonals = diagonals
   end function new_csr_matrix
 
-  !> Operator A (which = 1) or B (which = 2) of the engine from a csr_matrix: the engine keeps the rows of its slab in HBM and applies
+  !> Operator A (which = 1), B (which = 2) or the preconditioner M (which = 3) of the engine from a csr_matrix: the engine keeps the rows of its slab in HBM and applies
   !> them with its own CSR kernel.  The matrix is not referenced after the call.
   subroutine engine_set_sparse_csr(eng, which, a)
     type(davidson_engine), intent(inout) :: eng
@@ -173,7 +173,7 @@ contains
     if (which == 1) eng%free_semantics = .false.
   end subroutine engine_set_sparse_csr
 
-  !> Operator A (which = 1) or B (which = 2) of the engine from a CSR matrix of order n whose arrays are DEVICE memory of the engine's
+  !> Operator A (which = 1), B (which = 2) or the preconditioner M (which = 3) of the engine from a CSR matrix of order n whose arrays are DEVICE memory of the engine's
   !> device (hipfort, OpenMP offload, a GPU assembly stage): dav_set_operator_csr_dev builds the operator on the GPU, bit for bit as
   !> engine_set_sparse builds it from a csr_matrix holding the same arrays.  base: 1 (default, Fortran numbering) or 0; lower: only the
   !> entries with column <= row are given; row_ptr_bits / col_bits: 64 (default for row_ptr) or 32 (default for col_idx).  The arrays
@@ -256,7 +256,7 @@ contains
     if (present(lower)) a%lower = lower
   end function new_bsr_matrix
 
-  !> Operator A (which = 1) or B (which = 2) of the engine from a bsr_matrix: the engine keeps the block rows of its slab in HBM and
+  !> Operator A (which = 1), B (which = 2) or the preconditioner M (which = 3) of the engine from a bsr_matrix: the engine keeps the block rows of its slab in HBM and
   !> applies them with its own matrix-core BSR kernel.  The matrix is not referenced after the call.
   subroutine engine_set_sparse_bsr(eng, which, a)
     type(davidson_engine), intent(inout) :: eng
@@ -278,7 +278,7 @@ contains
     if (which == 1) eng%free_semantics = .false.
   end subroutine engine_set_sparse_bsr
 
-  !> Operator A (which = 1) or B (which = 2) of the engine from a BSR matrix of order n with square blocks of size block_size whose
+  !> Operator A (which = 1), B (which = 2) or the preconditioner M (which = 3) of the engine from a BSR matrix of order n with square blocks of size block_size whose
   !> arrays are DEVICE memory of the engine's device: dav_set_operator_bsr_dev builds the operator on the GPU, bit for bit as
   !> engine_set_sparse builds it from a bsr_matrix holding the same arrays.  base: 1 (default, Fortran numbering of block rows and
   !> columns) or 0; lower: only the blocks with block column <= block row are given; row_major: the b * b values of a block are in C

@@ -20,6 +20,13 @@ from .engine_c import (CEngine, DavidsonHipError, _device_bsr_tensors, _device_c
                        csr_flag_word, device_bsr_tensors, device_csr_tensors, guess_array, is_torch_bsr, is_torch_csr, torch_bsr_parts, torch_csr_parts,
                        update_values_array)
 
+# The operator slots of DavidsonEngine, numbered as the Fortran routines number them.  OP_M is the caller's preconditioner - an
+# approximation of (A - sigma B)^-1, symmetric, for "GJD" positive definite - which "DPR" (T = M R) and "GJD" (its MINRES) apply in place
+# of the diagonal; "BDPR", "CHEB" and "LCHEB" do not read it.  It is set by set_sparse, set_block_sparse, set_device_operator and
+# set_identity, refreshed by update_values, replaced by setting it again and never unset.  The one-shot functions of this module
+# (generalized_eigensolver_sparse, generalized_eigensolver_bsr and the others) take no preconditioner: their doors have fixed argument lists.
+OP_A, OP_B, OP_M = 1, 2, 3
+
 _METHOD = {"DPR": 0, "GJD": 1, "BDPR": 3}
 _DEGREE_METHOD = {"CHEB": 4, "LCHEB": 5}        # "<name>" (default degree) or "<name><d>" with 1 <= d <= 64: the degree rides in bits 8..15
 
@@ -342,7 +349,15 @@ class DavidsonEngine:
     def comm_init(self, unique_id: bytes):
         self.lib.fd_engine_comm_init(self.p, C.create_string_buffer(unique_id, 128))
 
+    @staticmethod
+    def _not_the_preconditioner(which, entry):
+        """the entries that serve A and B only: refused here, because the Fortran doors stop the process on the engine's refusal"""
+        if which == OP_M:
+            raise ValueError(f"DavidsonEngine.{entry}: the preconditioner (which = 3, DAV_OP_M) is set with set_sparse, set_block_sparse, "
+                             "set_device_operator or set_identity only")
+
     def set_dense(self, which, matrix):
+        self._not_the_preconditioner(which, "set_dense")
         a = _f(matrix)
         assert a.shape == (self.n, self.n)
         self._note_blocks(which, None)
@@ -351,9 +366,9 @@ class DavidsonEngine:
     def _note_blocks(self, which, b, sparse=False):
         """the block size of operator `which` while it is a BSR operator, None otherwise: what solve("BDPR") checks before the engine is
         called; sparse: it is a CSR or BSR operator, what solve("CHEB") checks"""
-        self._blocks = getattr(self, "_blocks", [None, None])
+        self._blocks = getattr(self, "_blocks", [None, None, None])
         self._blocks[which - 1] = b
-        self._sparse = getattr(self, "_sparse", [False, False])
+        self._sparse = getattr(self, "_sparse", [False, False, False])
         self._sparse[which - 1] = bool(sparse) or b is not None
 
     def _keep_map(self, which, keep_map):
@@ -364,7 +379,7 @@ class DavidsonEngine:
         self.lib.fd_engine_keep_value_map(self.p, which, int(keep_map))
 
     def set_sparse(self, which, indptr, indices=None, data=None, lower=False, keep_map=False, diagonals=False):
-        """Operator A (which=1) or B (which=2) as a symmetric matrix in CSR form, 0-based (Fortran: engine_set_sparse): three arrays,
+        """Operator A, B or the preconditioner M (which=1, 2, 3) as a symmetric matrix in CSR form, 0-based (Fortran: engine_set_sparse): three arrays,
         or `indptr` an object with .tocsr(), or a torch.sparse_csr_tensor - one on the engine's GPU is built there (Fortran:
         engine_set_sparse_device; a refused matrix raises DavidsonHipError and leaves the operator unset).  lower=True: only the
         entries with column <= row are given.  keep_map=True: the operator also keeps where its values came from (Fortran:
@@ -395,7 +410,7 @@ class DavidsonEngine:
             self._kept[which] = {"count": nnz, "b": 1, "fortran_blocks": False}
 
     def set_block_sparse(self, which, indptr, indices=None, data=None, lower=False, keep_map=False):
-        """Operator A (which=1) or B (which=2) as a symmetric matrix in BSR form, 0-based (Fortran: engine_set_sparse with a bsr_matrix):
+        """Operator A, B or the preconditioner M (which=1, 2, 3) as a symmetric matrix in BSR form, 0-based (Fortran: engine_set_sparse with a bsr_matrix):
         three arrays - data (nnzb, b, b), row-major blocks - or `indptr` an object with .blocksize (a scipy bsr_matrix), or a
         torch.sparse_bsr_tensor - one on the engine's GPU is built there (Fortran: engine_set_block_sparse_device; a refused matrix
         raises DavidsonHipError and leaves the operator unset).  lower=True: only the blocks with block column <= block row are given.
@@ -424,7 +439,7 @@ class DavidsonEngine:
             self._kept[which] = {"count": nnzb * b * b, "b": b, "fortran_blocks": False}
 
     def update_values(self, which, data):
-        """New values of operator A (which=1) or B (which=2) on its kept pattern (Fortran: engine_update_sparse_values /
+        """New values of operator A (which=1), B (which=2) or M (which=3) on its kept pattern (Fortran: engine_update_sparse_values /
         engine_update_sparse_values_device): the operator was set by set_sparse / set_block_sparse with keep_map=True, and `data` is the
         data of that call with new numbers - for BSR (nnzb, b, b) row-major blocks, or the same flat.  A numpy array (or a CPU tensor)
         goes through the host entry, a torch tensor on the engine's GPU through the device entry; either works whichever way the
@@ -468,6 +483,7 @@ class DavidsonEngine:
     def read_matrix(self, which, path, fmt="text"):
         """Operator from a file, streamed to HBM (Fortran: engine_read_matrix): "text" = the reference's
         write_matrix/read_matrix dump format, "f64" = raw row-major float64."""
+        self._not_the_preconditioner(which, "read_matrix")
         self._note_blocks(which, None)
         self.c.set_dense_file(which - 1, path, fmt)
 
@@ -477,19 +493,24 @@ class DavidsonEngine:
 
     def generate_diagonal_dominant(self, which, sparsity, diag_val=None, seed=1):
         """generate_diagonal_dominant(n, sparsity[, diag_val]) built directly in HBM."""
+        self._not_the_preconditioner(which, "generate_diagonal_dominant")
         self._set_op(which, 0, seed, sparsity, diag_val)
 
     def set_hashed_operator(self, which, sparsity, diag_val=None, seed=1):
+        self._not_the_preconditioner(which, "set_hashed_operator")
         self._set_op(which, 1, seed, sparsity, diag_val)
 
     def set_harness_operator(self, which):
+        self._not_the_preconditioner(which, "set_harness_operator")
         self._set_op(which, 2, 0, 0.0, None)
 
     def set_identity(self, which):
+        """B = I (which = 2), or the preconditioner M = I (which = 3: "DPR" then corrects with T = R)."""
         self._set_op(which, 3, 0, 0.0, None)
 
-    def set_device_operator(self, which, fn, ctx, diag):
-        """The caller's own operator as a block apply on device memory (engine_set_device_operator; which = 1 / 2)."""
+    def set_device_operator(self, which, fn, ctx, diag=None):
+        """The caller's own operator as a block apply on device memory (engine_set_device_operator; which = 1 / 2 / 3).  diag: the
+        operator's diagonal; the preconditioner's (which = 3) is not read and may be None."""
         self._note_blocks(which, None)
         self.c.set_operator_device(which - 1, fn, ctx, diag)
 
@@ -527,8 +548,9 @@ class DavidsonEngine:
         a Lanczos bound, for a standard problem whose A is anything the engine applies on the device - set_dense, set_device_operator,
         set_hashed_operator, set_sparse, set_block_sparse ... (a generalized problem: ValueError before the engine is called)."""
         if _parse_method(method)[0] > 2:         # DPR, GJD and names that are none ask nothing of what the engine holds
-            _check_method(method, a_sparse=getattr(self, "_sparse", [False, False])[0], blocks=getattr(self, "_blocks", [None, None]),
-                          gev=self.gev, n=self.n, nranks=self.nranks, where="DavidsonEngine.solve")
+            # (BDPR's checks read A and B only: the preconditioner's blocks are no concern of a method that does not apply it)
+            _check_method(method, a_sparse=getattr(self, "_sparse", [False, False, False])[0],
+                          blocks=getattr(self, "_blocks", [None, None, None])[:2], gev=self.gev, n=self.n, nranks=self.nranks, where="DavidsonEngine.solve")
         if reuse_vectors is not None:
             self.keep_result_as_guess(bool(reuse_vectors))
         if initial_vectors is not None:

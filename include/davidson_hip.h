@@ -31,8 +31,24 @@ extern "C" {
 
 typedef struct dav_engine* dav_handle_t;
 
-/* which operator */
-enum { DAV_OP_A = 0, DAV_OP_B = 1 };
+/* which operator.  DAV_OP_M (additive within ABI 109) is the caller's PRECONDITIONER: an approximation of (A - sigma B)^-1 for a shift sigma
+ * the caller chose, handed over as an operator the engine applies to blocks.  It must be symmetric, and for GJD positive definite: that is
+ * the caller's promise, like the symmetry of A.  Which entries take it:
+ *   set:     dav_set_operator_csr(_dev) (DAV_CSR_DIAGONALS included), dav_set_operator_bsr(_dev), dav_set_operator_device (diag may be
+ *            NULL and is not read), dav_set_operator_identity; several ranks: set like A, global arrays on every rank, the apply is collective
+ *   refresh: dav_keep_value_map, dav_update_operator_values(_dev), dav_get_diagonal (sparse M only)
+ *   apply:   dav_apply, dav_apply_inner
+ *   refused, with a message that names DAV_OP_M and the engine left usable: every dense entry (host, device, rows, file, generated),
+ *            dav_set_operator_hashed, dav_set_operator_harness, dav_set_operator_host.
+ * Setting M again replaces it; there is no unset (dav_set_operator_identity gives T = R).  Which corrections read it:
+ *   DAV_METHOD_DPR   the Ritz phase writes R into DAV_PANEL_R and T = M R into V[:, m:m+ncorr] - bit for bit what
+ *                    dav_apply(h, DAV_OP_M, DAV_PANEL_R, 0, ncorr, DAV_PANEL_V, m) gives on that R - in place of T = R / (dA - theta dB);
+ *                    all entries of that phase follow (dav_ritz_residual_correction(_n, _g), dav_rr_ritz)
+ *   DAV_METHOD_GJD   MINRES is preconditioned by  y = M r - (x^T M r / x^T M x) M x  in place of the Jacobi diagonal; the call fails with a
+ *                    message naming M if at its first step a column has x^T M x <= 0 or r^T y < 0 (nothing else about M is checked)
+ *   DAV_METHOD_BDPR, DAV_METHOD_CHEB, DAV_METHOD_LCHEB do not read the slot: their corrections keep their bits.
+ * An engine on which the slot was never set computes what it computed before the slot existed. */
+enum { DAV_OP_A = 0, DAV_OP_B = 1, DAV_OP_M = 2 };
 /* device panels (N-long, column-major, resident in HBM) */
 enum { DAV_PANEL_V = 0,   /* search-space basis V (and, in its tail columns, the correction block T) */
        DAV_PANEL_W = 1,   /* A*V            (src/davidson.f90:131,223 inner DGEMM)                 */
@@ -246,7 +262,8 @@ int dav_set_operator_host(dav_handle_t h, int which, const double* diag);
  * that leaves  Y[0:nloc, 0:k] = Op[row0 : row0 + nloc, 0:n] * X[0:n, 0:k]  in y_dev (column-major, leading dimension ldy) - x_dev
  * holds ALL n rows of the block (column-major, ldx; several ranks: the engine has all-gathered it), rows [row0, row0 + nloc) are this
  * rank's slab (dav_local_rows) - and return 0; it must not synchronise the device.  diag: the operator's diagonal, n doubles on the
- * host (the DPR preconditioner and the start vectors need it - src/davidson.f90:490-523 probes it with N unit vectors).  Since ABI 106. */
+ * host (the DPR preconditioner and the start vectors need it - src/davidson.f90:490-523 probes it with N unit vectors); which = DAV_OP_M: may be NULL, is not read.
+ * Since ABI 106. */
 typedef int (*dav_device_apply_fn)(void* ctx, void* hip_stream, int64_t n, int64_t row0, int64_t nloc, int k, const double* x_dev, int64_t ldx,
                                    double* y_dev, int64_t ldy);
 int dav_set_operator_device(dav_handle_t h, int which, dav_device_apply_fn fn, void* ctx, const double* diag);
