@@ -35,7 +35,7 @@ module davidson_engine_setup
      real(dp) :: phase_seconds(8) = 0.0_dp
   end type davidson_engine
 
-  !> Correction policies of the outer loop (see davidson_device_loop)
+  !> Correction policies of the outer loop (module davidson_loop: reference_policy_loop runs the first two, davidson_locking_loop the third)
   integer, parameter, public :: POLICY_ALL = 0, POLICY_UNCONVERGED = 1, POLICY_LOCKING = 2
 
 contains
@@ -124,7 +124,7 @@ contains
   !> the pairs that need them.  "locking" (opt-in; standard problems; the deflation the reference's header cites and never
   !> implements, src/davidson.f90:7-8): a wanted pair whose residual is below the tolerance is locked - its Ritz vector leaves the
   !> active basis, which is kept orthogonal to it, its value is final - and the Rayleigh-Ritz problem, the corrections and the
-  !> restarts only concern the pairs still wanted (locking_loop in davidson_device_loop; oracle:
+  !> restarts only concern the pairs still wanted (davidson_locking_loop in module davidson_loop; oracle:
   !> generalized_eigensolver_dense_locking).
   subroutine engine_set_correction_policy(eng, policy)
     type(davidson_engine), intent(inout) :: eng

@@ -7,9 +7,18 @@ module davidson_knobs
   implicit none
   private
   public :: env_device, env_storage, env_storage_symmetric, symmetry_probe, basis_capacity, gjd_tol_unwanted, gjd_tol_wanted, &
-       gjd_adaptive_factor, restart_refresh_interval, ascending_order, tick, trace_iterations, verbose
+       gjd_adaptive_factor, restart_refresh_interval, ascending_order, tick, trace_iterations, verbose, default_max_dim
 
 contains
+
+  !> max_dim_sub of the front ends where the caller leaves it out: 10 * lowest (src/davidson.f90:115-119)
+  pure function default_max_dim(lowest, max_dim_sub) result(max_dim)
+    integer, intent(in) :: lowest
+    integer, intent(in), optional :: max_dim_sub
+    integer :: max_dim
+    max_dim = 10 * lowest
+    if (present(max_dim_sub)) max_dim = max_dim_sub
+  end function default_max_dim
 
   !> Device index from the environment (DAVIDSON_DEVICE, default 0): an engine knob that does not
   !> touch the reference's argument lists (dense and matrix-free front ends alike).

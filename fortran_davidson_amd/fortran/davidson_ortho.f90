@@ -66,7 +66,7 @@ contains
   !> pair) is replaced by a deterministic pseudo-random vector, as Householder QR would complete the
   !> basis with an arbitrary direction.
   !> only_first = .true.: return after the first pass that applied a transform (its number in last_pass) - the driver then
-  !> sweeps the block and runs the last pass together with the projection (project_with_last_pass); first_pass: number of
+  !> sweeps the block and runs the last pass together with the projection (davidson_loop: grow_basis, project_with_last_pass); first_pass: number of
   !> the first pass made here (a continuation).
   subroutine block_orthonormalise(be, n, m, kt, c_first, g_first, only_first, last_pass, first_pass, replaced)
     class(ortho_backend), intent(inout) :: be
