@@ -148,6 +148,17 @@ FD = {
     "fd_norm": (None, (i32, ptr, ptr)),
 }
 
+# include/davidson_hip_ext.h: the extension entries (prefix davx_) next to ABI 109, and their doors (prefix fdx_) of davidson_c_api.f90;
+# tests/test_coo_cpu.py compares both with the header and the Fortran sources, as tests/test_abi_cpu.py does for the tables above
+EXT = {
+    "davx_set_operator_coo": (i32, (ptr, i32, i64, ptr, ptr, ptr, i32, i32)),
+    "davx_set_operator_coo_dev": (i32, (ptr, i32, i64, ptr, i32, ptr, i32, ptr, i32, i32)),
+}
+EXT_FD = {
+    "fdx_engine_set_coo": (None, (ptr, i32, i32, i64, ptr, ptr, ptr, i32, i32)),
+    "fdx_engine_set_coo_device": (i32, (ptr, i32, i32, i64, ptr, i32, ptr, i32, ptr, i32, i32)),
+}
+
 
 def apply(lib, table, optional=()):
     """Set restype and argtypes of every entry of `table` on `lib`.  An entry of `optional` that the library lacks is skipped; any

@@ -46,6 +46,7 @@ def hip_lib() -> C.CDLL:
             pass
         lib = C.CDLL(HIP_LIB, mode=C.RTLD_LOCAL)
         _abi.apply(lib, _abi.DAV, optional=_abi.TEST_BUILD_ONLY)       # raises before the library can be used without prototypes
+        _abi.apply(lib, _abi.EXT)
         _hip = lib
         runtimes = hip_runtimes_mapped()
         if len(runtimes) > 1:
@@ -79,5 +80,6 @@ def fortran_lib() -> C.CDLL:
             raise NativeLibraryMissing(f"{FORTRAN_LIB} not built: run `make -C fortran_davidson_amd`")
         lib = C.CDLL(FORTRAN_LIB, mode=C.RTLD_GLOBAL)  # MKL dlopens its kernels and needs libmkl_core global
         _abi.apply(lib, _abi.FD)
+        _abi.apply(lib, _abi.EXT_FD)
         _fortran = lib
     return _fortran

@@ -1,5 +1,6 @@
 // Engine, sparse operators: a symmetric matrix in CSR or BSR form, given in host arrays (dav_set_operator_csr, dav_set_operator_bsr) or in
-// device arrays and built on the GPU (dav_set_operator_csr_dev, dav_set_operator_bsr_dev; kernels in k_csr_build.hip, k_bsr_build.hip).
+// device arrays and built on the GPU (dav_set_operator_csr_dev, dav_set_operator_bsr_dev; kernels in k_csr_build.hip, k_bsr_build.hip);
+// a CSR matrix also as unordered COO triples (davx_set_operator_coo, davx_set_operator_coo_dev; k_coo_build.hip).
 // All four entries follow one structure: the PATTERN - row_ptr and col_idx over rows or block rows - is validated; the
 // canonical order of this rank's rows is built with a PAYLOAD per column index (CSR: the value of the entry; BSR: the source of the block,
 // input position << 1 | mirrored); BSR gathers the VALUES from the sources; the DIAGONAL is summed per kind; one COMMIT step builds the
@@ -12,6 +13,8 @@
 // stay for the refresh, which fills the diagonals again (device memory: that of the CSR operator with its map plus 8 nd nloc bytes).
 #include "engine_internal.h"
 #include "dia_rule.h"
+#include "coo_host.h"
+#include "davidson_hip_ext.h"
 
 void sparse_release(E* e, OpDesc& o) {
   SparseStore& s = o.sp;
@@ -58,6 +61,7 @@ void sparse_build_items(const std::vector<int64_t>& rp, int max_rows, int64_t ch
 // ---- messages: every text exists once, composed from the nouns of the kind ---------------------------------------------------------------
 struct SparseWords { const char *rp, *ci, *row, *rows, *col, *item, *items; };
 const SparseWords CSR_WORDS{"row_ptr", "col_idx", "row", "rows", "column index", "entry", "entries"};
+const SparseWords COO_WORDS{"row_idx", "col_idx", "row", "rows", "column index", "entry", "entries"};      // triples: rp names the row indices
 const SparseWords BSR_WORDS{"block_row_ptr", "block_col_idx", "block row", "block rows", "block column", "block", "blocks"};
 
 // one call of one of the four entries
@@ -113,6 +117,17 @@ std::string msg_bad_entry(const SparseWords& w, int64_t n, int base, int64_t p, 
     return std::string(w.col) + " " + std::to_string(c) + " out of range at " + w.item + " " + std::to_string(p + base) + " (" + w.row + " " +
            std::to_string(i + base) + ")";
   return std::string(w.item) + " (" + std::to_string(i + base) + ", " + std::to_string(c) + ") lies above the diagonal of a DAV_CSR_LOWER matrix";
+}
+// triple p (from 0) carries the caller's row r and column c: the row outside the matrix, or what msg_bad_entry says of the column
+std::string msg_bad_triple(const SparseWords& w, int64_t n, int base, int64_t p, int64_t r, int64_t c) {
+  if (r - base < 0 || r - base >= n)
+    return std::string(w.row) + " index " + std::to_string(r) + " out of range at " + w.item + " " + std::to_string(p + base);
+  return msg_bad_entry(w, n, base, p, r - base, c);
+}
+// the scalar arguments of a COO entry ("" = fine; coo_host.h); bits = {row_bits, col_bits} of the device entry, nullptr for the host entry
+std::string bad_triples(int64_t n, int64_t nnz, int index_base, int triangle, const int* bits, const void* row_idx, const void* col_idx,
+                        const void* vals) {
+  return coo_bad_arguments(n, nnz, index_base, triangle, DAV_CSR_LOWER | DAV_CSR_DIAGONALS, bits, row_idx, col_idx, vals);
 }
 std::string no_memory(const std::string& what) { return "device memory for " + what + " could not be allocated"; }
 // (the estimates of the entries differ: 12 lnnz + 8 nloc bytes for CSR, 8 b^2 + 4 per block from host arrays, 8 b^2 + 12 from device arrays)
@@ -313,10 +328,13 @@ int dia_commit(const Entry& en, const std::vector<int32_t>& offs) {
 }
 }  // namespace
 
-extern "C" int dav_set_operator_csr(dav_handle_t e, int which, const int64_t* row_ptr, const int32_t* col_idx, const double* vals,
-                                    int index_base, int triangle) {
-  CHK(entry_begin(e, which, "dav_set_operator_csr"));
-  const Entry en{e, which, "dav_set_operator_csr", CSR_WORDS};
+namespace {
+// The host CSR path behind dav_set_operator_csr and davx_set_operator_coo.  perm (COO: the row form is a permutation of the caller's
+// triples) = the caller's position of every entry of vals; the value map and the diagonal sources then name the caller's positions.
+int set_csr_host(const Entry& en, const int64_t* row_ptr, const int32_t* col_idx, const double* vals, int index_base, int triangle,
+                 const int64_t* perm) {
+  E* e = en.e;
+  const int which = en.which;
   const int64_t n = e->n;
   std::string why = bad_arguments(en.w, n, false, 0, index_base, triangle, 0, nullptr, row_ptr);
   if (!why.empty()) return en.refuse(why);
@@ -354,8 +372,38 @@ extern "C" int dav_set_operator_csr(dav_handle_t e, int which, const int64_t* ro
       }
     if (keep_map) map.doff[(size_t)i + 1] = (int64_t)map.dpos.size();
   }
+  if (keep_map && perm) {
+    for (uint64_t& q : map.src) q = (uint64_t)perm[q >> 1] << 1 | (q & 1);
+    for (int64_t& p : map.dpos) p = perm[p];
+  }
   CHK(commit_host(en, DAV_KIND_CSR, 1, 0, rp, lcol, lval, diag, 12 * rp.back() + 8 * e->nloc, keep_map ? &map : nullptr));
   return (triangle & DAV_CSR_DIAGONALS) ? dia_commit(en, dia_offsets) : 0;
+}
+}  // namespace
+
+extern "C" int dav_set_operator_csr(dav_handle_t e, int which, const int64_t* row_ptr, const int32_t* col_idx, const double* vals,
+                                    int index_base, int triangle) {
+  CHK(entry_begin(e, which, "dav_set_operator_csr"));
+  return set_csr_host(Entry{e, which, "dav_set_operator_csr", CSR_WORDS}, row_ptr, col_idx, vals, index_base, triangle, nullptr);
+}
+
+// COO triples in host memory: validated in the order of the triples (the first offending p is named), brought into their row form by a
+// stable counting sort on the row, and from there the host CSR path - with the positions of the triples in the value map.
+extern "C" int davx_set_operator_coo(dav_handle_t e, int which, int64_t nnz, const int32_t* row_idx, const int32_t* col_idx, const double* vals,
+                                    int index_base, int triangle) {
+  CHK(entry_begin(e, which, "davx_set_operator_coo"));
+  const Entry en{e, which, "davx_set_operator_coo", COO_WORDS};
+  const int64_t n = e->n;
+  const std::string why = bad_triples(n, nnz, index_base, triangle, nullptr, row_idx, col_idx, vals);
+  if (!why.empty()) return en.refuse(why);
+  const int64_t bad = coo_first_bad(n, nnz, row_idx, col_idx, index_base, (triangle & DAV_CSR_LOWER) != 0);
+  if (bad >= 0) return en.refuse(msg_bad_triple(en.w, n, index_base, bad, row_idx[bad], col_idx[bad]));
+  CooRowForm f;
+  coo_row_form(n, nnz, row_idx, col_idx, vals, index_base, f);
+  const int32_t none_i = 0;
+  const double none_v = 0.0;
+  return set_csr_host(en, f.row_ptr.data(), nnz > 0 ? f.col.data() : &none_i, nnz > 0 ? f.val.data() : &none_v, index_base, triangle,
+                      f.perm.data());
 }
 
 extern "C" int dav_set_operator_bsr(dav_handle_t e, int which, int block_size, const int64_t* block_row_ptr, const int32_t* block_col_idx,
@@ -535,6 +583,10 @@ void pattern_scatter(hipStream_t st, const DevPattern& P, int64_t p_lo, int64_t 
                            osrc, tie);
 }
 
+template <class V>
+int pattern_sort_dev(E* e, BuildScratch& sc, const SparseWords& w, const int64_t* lrp, const std::vector<int64_t>& rp, int32_t* ocol, V* oval,
+                     const uint32_t* tie, uint8_t* flag, std::string* why);
+
 // the canonical order: columns to ocol and payloads (values / block sources) to oval, every local row in the order of pattern_order
 template <class V>
 int pattern_order_dev(E* e, BuildScratch& sc, const DevPattern& P, const SparseWords& w, const int64_t* lrp, const std::vector<int64_t>& rp,
@@ -560,8 +612,19 @@ int pattern_order_dev(E* e, BuildScratch& sc, const DevPattern& P, const SparseW
     p_hi = ends[1] - P.base;
   }
   HIPCHK(hipMemsetAsync(P.mcount, 0, sizeof(int32_t) * std::max<int64_t>(nloc, 1), st));
-  HIPCHK(hipMemsetAsync(flag, 0, std::max<int64_t>(nloc, 1), st));
   if (nloc > 0) pattern_scatter(st, P, p_lo, p_hi, lrp, ocol, oval, tie);
+  return pattern_sort_dev(e, sc, w, lrp, rp, ocol, oval, tie, flag, why);
+}
+
+// Rows lrp[0..nloc] (rp: the same offsets on the host) of columns ocol with payloads oval, each row into the order of its keys (column,
+// tie; tie == nullptr: the position is the tie): rows out of order are flagged, those of at most one LDS tile sorted by one workgroup each,
+// longer ones by tiles and merge passes.  flag: nloc bytes of scratch.
+template <class V>
+int pattern_sort_dev(E* e, BuildScratch& sc, const SparseWords& w, const int64_t* lrp, const std::vector<int64_t>& rp, int32_t* ocol, V* oval,
+                     const uint32_t* tie, uint8_t* flag, std::string* why) {
+  hipStream_t st = e->stream;
+  const int64_t nloc = (int64_t)rp.size() - 1, lnnz = rp[(size_t)nloc];
+  HIPCHK(hipMemsetAsync(flag, 0, std::max<int64_t>(nloc, 1), st));
   launch_csr_build_flag(st, lrp, nloc, lnnz, ocol, tie, flag);
   launch_csr_build_sort_rows(st, lrp, nloc, flag, ocol, oval, tie);
   // rows longer than one LDS tile that are out of order: tiles sorted, then merged (one row at a time)
@@ -672,6 +735,119 @@ extern "C" int dav_set_operator_csr_dev(dav_handle_t e, int which, const void* r
   launch_csr_build_diag(e->stream, row_ptr, P.rp64, col_idx, P.ci64, vals, e->n, index_base, P.dcount, P.dfirst, diag);
   if (keep_map)
     if (int rc = keep_diag_sources(en, sc, P, triangle & DAV_CSR_LOWER, 0, &why)) return en.step(rc, why);
+  std::vector<double> hdiag;
+  CHK(sparse_commit(en, DAV_KIND_CSR, 1, 0, rp, hdiag, diag, no_memory(work_list(en.w, lnnz))));
+  return (triangle & DAV_CSR_DIAGONALS) ? dia_commit(en, dia_offsets) : 0;
+}
+
+// COO triples in device memory (kernels in k_coo_build.hip).  Everything is validated in scratch before the previous
+// operator goes and anything is allocated for the new one.  Scratch (BuildScratch, released before return): 8 (nloc + 1) + 8 nloc bytes
+// for the counts and slot cursors of this rank's rows, 16 (n + 1) + 8 n for those of the diagonal pattern and the diagonal, 4 bytes per
+// canonical entry of this rank (the tie) and 16 per diagonal entry of the matrix (12 when the value map keeps their positions), nloc + n
+// bytes of row flags where a row is longer than 64 entries, 2 n - 1 bytes of marks with DAV_CSR_DIAGONALS, and 32 bytes per entry of the
+// longest row above 2048 entries.
+extern "C" int davx_set_operator_coo_dev(dav_handle_t e, int which, int64_t nnz, const void* row_idx, int row_bits, const void* col_idx,
+                                        int col_bits, const double* vals, int index_base, int triangle) {
+  CHK(entry_begin(e, which, "davx_set_operator_coo_dev"));
+  const Entry en{e, which, "davx_set_operator_coo_dev", COO_WORDS};
+  const int bits[2] = {row_bits, col_bits};
+  const int64_t n = e->n, nloc = e->nloc, r0 = e->row0;
+  std::string why = bad_triples(n, nnz, index_base, triangle, bits, row_idx, col_idx, vals);
+  if (!why.empty()) return en.refuse(why);
+  const int ri64 = row_bits == 64, ci64 = col_bits == 64, lower = (triangle & DAV_CSR_LOWER) ? 1 : 0;
+  if (nnz > 0 && (!device_array(e, row_idx, en.w.rp, (ri64 ? 8 : 4) * (size_t)nnz, &why) ||
+                  !device_array(e, col_idx, en.w.ci, (ci64 ? 8 : 4) * (size_t)nnz, &why) || !device_array(e, vals, "vals", 8 * (size_t)nnz, &why)))
+    return en.refuse(why);
+  hipStream_t st = e->stream;
+  BuildScratch sc(st);
+  // check / count: the first offending triple; the lengths of this rank's canonical rows and of the rows of the diagonal pattern
+  unsigned long long *info = nullptr, *lcount = nullptr, *dcount = nullptr;
+  int64_t *locate = nullptr, *tile_sums = nullptr;
+  sc.take(&info, 1); sc.take(&locate, 2); sc.take(&lcount, (size_t)nloc + 1); sc.take(&dcount, (size_t)n + 1);
+  sc.take(&tile_sums, (size_t)csr_build_scan_tiles(n));
+  if (sc.oom) return en.refuse(no_memory("the validation of " + std::to_string(n) + " " + en.w.rows));
+  HIPCHK(hipMemsetAsync(info, 0xff, sizeof(unsigned long long), st));
+  HIPCHK(hipMemsetAsync(lcount, 0, sizeof(unsigned long long) * ((size_t)nloc + 1), st));
+  HIPCHK(hipMemsetAsync(dcount, 0, sizeof(unsigned long long) * ((size_t)n + 1), st));
+  launch_coo_build_check(st, row_idx, ri64, col_idx, ci64, n, nnz, index_base, lower, r0, nloc, info, lcount + 1, dcount + 1);
+  unsigned long long first_bad = 0;
+  CHK(readback(st, &first_bad, info, sizeof(first_bad)));
+  if (first_bad != ~0ull) {
+    launch_coo_build_locate(st, row_idx, ri64, col_idx, ci64, (int64_t)first_bad, locate);
+    int64_t loc[2];
+    CHK(readback(st, loc, locate, sizeof(loc)));
+    return en.refuse(msg_bad_triple(en.w, n, index_base, (int64_t)first_bad, loc[0], loc[1]));
+  }
+  std::vector<int32_t> dia_offsets;
+  if (triangle & DAV_CSR_DIAGONALS) {          // the marks of the validated triples, read back: the list and the decision of the host entry
+    const size_t nmarks = (size_t)(2 * n - 1);
+    uint8_t* marks = nullptr;
+    unsigned long long* ndiag = nullptr;
+    sc.take(&marks, nmarks); sc.take(&ndiag, 1);
+    if (sc.oom) return en.refuse(no_memory("the marks of " + std::to_string(nmarks) + " offsets"));
+    HIPCHK(hipMemsetAsync(marks, 0, nmarks, st));
+    HIPCHK(hipMemsetAsync(ndiag, 0, sizeof(unsigned long long), st));
+    launch_coo_mark(st, row_idx, ri64, col_idx, ci64, n, nnz, index_base, lower, marks, ndiag);
+    std::vector<uint8_t> hmarks(nmarks);
+    unsigned long long hdiag = 0;
+    CHK(readback(st, hmarks.data(), marks, nmarks));
+    CHK(readback(st, &hdiag, ndiag, sizeof(hdiag)));
+    if (!dia_decide(hmarks.data(), n, nnz, (int64_t)hdiag, lower != 0, dia_offsets, &why)) return en.refuse(why);
+  }
+  // offsets: the two count arrays scanned in place (a leading 0 each); those of this rank's rows stay with the operator
+  CHK(operator_goes(e, which, true));
+  SparseStore& s = e->op[which].sp;
+  int64_t* lrp = (int64_t*)lcount;
+  int64_t* doff = (int64_t*)dcount;
+  launch_csr_build_scan(st, lrp + 1, nloc, tile_sums);
+  launch_csr_build_scan(st, doff + 1, n, tile_sums);
+  std::vector<int64_t> rp((size_t)nloc + 1), hdoff((size_t)n + 1);
+  CHK(readback(st, rp.data(), lrp, sizeof(int64_t) * rp.size()));
+  CHK(readback(st, hdoff.data(), doff, sizeof(int64_t) * hdoff.size()));
+  const int64_t lnnz = rp.back(), ndiag = hdoff.back();
+  const bool keep_map = e->keep_map[which] != 0;
+  if (!keep(&s.rp, (size_t)nloc + 1) || !keep(&s.col, (size_t)lnnz) || !keep(&s.val, (size_t)lnnz))
+    return en.refuse(no_memory(stored(en.w, lnnz, 12 * lnnz + 8 * nloc)));
+  if (keep_map && (!keep(&s.src, (size_t)lnnz) || !keep(&s.doff, (size_t)n + 1) || !keep(&s.dpos, (size_t)ndiag))) return en.refuse(map_memory(en.w));
+  HIPCHK(hipMemcpyAsync(s.rp, lrp, sizeof(int64_t) * ((size_t)nloc + 1), hipMemcpyDeviceToDevice, st));
+  // scatter: atomic slots (the cursors start at the offsets), then the sorts remove the slot order
+  unsigned long long *cursor = nullptr, *dcursor = nullptr;
+  uint32_t *tie = nullptr, *dtie = nullptr;
+  int32_t* dcol = nullptr;
+  uint64_t* dpos = (uint64_t*)s.dpos;
+  double* diag = nullptr;
+  sc.take(&cursor, (size_t)nloc); sc.take(&dcursor, (size_t)n); sc.take(&tie, (size_t)lnnz); sc.take(&dtie, (size_t)ndiag);
+  sc.take(&dcol, (size_t)ndiag); sc.take(&diag, (size_t)n);
+  if (!keep_map) sc.take(&dpos, (size_t)ndiag);
+  if (sc.oom) return en.refuse(no_memory("sorting " + std::to_string(lnnz) + " " + en.w.items));
+  if (nloc > 0) HIPCHK(hipMemcpyAsync(cursor, lrp, sizeof(int64_t) * (size_t)nloc, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(dcursor, doff, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemsetAsync(dcol, 0, sizeof(int32_t) * std::max<size_t>((size_t)ndiag, 1), st));
+  if (keep_map) launch_coo_build_scatter(st, row_idx, ri64, col_idx, ci64, vals, nnz, index_base, lower, r0, nloc, cursor, s.col, s.src, tie, dcursor, dtie, dpos);
+  else launch_coo_build_scatter(st, row_idx, ri64, col_idx, ci64, vals, nnz, index_base, lower, r0, nloc, cursor, s.col, s.val, tie, dcursor, dtie, dpos);
+  // sort: rows of at most 64 entries in registers; only where longer rows exist, the flag pass and the LDS / tile-and-merge sorts
+  auto order = [&](const int64_t* offs, const std::vector<int64_t>& hoffs, int32_t* ocol, auto* oval, uint32_t* t) -> int {
+    const int64_t nrows = (int64_t)hoffs.size() - 1;
+    launch_coo_sort_small(st, offs, nrows, ocol, oval, t);
+    bool longer = false;
+    for (int64_t i = 0; i < nrows && !longer; ++i) longer = hoffs[(size_t)i + 1] - hoffs[(size_t)i] > coo_sort_small_rows();
+    if (!longer) return 0;
+    uint8_t* flag = nullptr;
+    sc.take(&flag, (size_t)nrows);
+    if (sc.oom) { why = no_memory("sorting " + std::to_string(hoffs.back()) + " " + en.w.items); return 1; }
+    return pattern_sort_dev(e, sc, en.w, offs, hoffs, ocol, oval, t, flag, &why);
+  };
+  if (int rc = keep_map ? order(s.rp, rp, s.col, s.src, tie) : order(s.rp, rp, s.col, s.val, tie)) return en.step(rc, why);
+  if (int rc = order(doff, hdoff, dcol, dpos, dtie)) return en.step(rc, why);
+  if (keep_map) {          // the values follow their sources; the sorted diagonal pattern is the diagonal sources
+    launch_sparse_refresh_csr(st, s.src, lnnz, vals, s.val);
+    HIPCHK(hipMemcpyAsync(s.doff, doff, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToDevice, st));
+    s.gcount = nnz;
+    s.triangle = triangle & DAV_CSR_LOWER;
+    s.rowmaj = 0;
+  }
+  // the diagonal of the whole matrix: per row from +0.0 in ascending p
+  launch_sparse_refresh_diag(st, 1, doff, (const int64_t*)dpos, vals, n, diag);
   std::vector<double> hdiag;
   CHK(sparse_commit(en, DAV_KIND_CSR, 1, 0, rp, hdiag, diag, no_memory(work_list(en.w, lnnz))));
   return (triangle & DAV_CSR_DIAGONALS) ? dia_commit(en, dia_offsets) : 0;

@@ -267,6 +267,30 @@ void launch_csr_build_sort_long(hipStream_t st, int64_t a, int64_t m, int32_t* o
 void launch_csr_build_diag(hipStream_t st, const void* rp, int rp64, const void* col, int ci64, const double* vals, int64_t n, int base,
                            const uint32_t* dcount, const unsigned long long* dfirst, double* diag);
 
+// ---- K1c'': device build of a CSR operator from COO triples (k_coo_build.hip; davx_set_operator_coo_dev) ---------------------------------
+// The caller's global triples: row and col of 32 (ri64 / ci64 = 0) or 64 bits, numbered from `base`, nnz < 2^32.
+// first_bad (~0 first) = the first triple with a row or column out of range or (lower) above the diagonal; lcount[i] (zero first) += the
+// entries of local row i, own and (lower) mirrored; dcount[i] (zero first) += the diagonal entries of row i of the whole matrix
+void launch_coo_build_check(hipStream_t st, const void* row, int ri64, const void* col, int ci64, int64_t n, int64_t nnz, int base, int lower,
+                            int64_t r0, int64_t nloc, unsigned long long* first_bad, unsigned long long* lcount, unsigned long long* dcount);
+// out[0] = row_idx[p], out[1] = col_idx[p]
+void launch_coo_build_locate(hipStream_t st, const void* row, int ri64, const void* col, int ci64, int64_t p, int64_t* out);
+// validated triples to atomic slots of their canonical rows: cursor[i] (the row's offset first) counts the slots taken; column, payload
+// (V: the value, or the source p << 1 | mirrored) and tie = p per slot.  The diagonal entries also go to slots of the diagonal pattern
+// (dcursor: its offsets first): dtie = p, dpos = p
+template <class V>
+void launch_coo_build_scatter(hipStream_t st, const void* row, int ri64, const void* col, int ci64, const double* vals, int64_t nnz, int base,
+                              int lower, int64_t r0, int64_t nloc, unsigned long long* cursor, int32_t* ocol, V* oval, uint32_t* tie,
+                              unsigned long long* dcursor, uint32_t* dtie, uint64_t* dpos);
+// every row of 2 .. coo_sort_small_rows() entries sorted in place by key (column, tie), in registers - columns, payloads and ties alike,
+// so that a later flag pass finds these rows in key order; other rows are left alone
+template <class V>
+void launch_coo_sort_small(hipStream_t st, const int64_t* lrp, int64_t nrows, int32_t* ocol, V* oval, uint32_t* tie);
+int64_t coo_sort_small_rows();
+// launch_dia_mark over triples
+void launch_coo_mark(hipStream_t st, const void* row, int ri64, const void* col, int ci64, int64_t n, int64_t nnz, int base, int lower,
+                     uint8_t* marks, unsigned long long* ndiag);
+
 // ---- K1d': device build of a BSR operator (k_bsr_build.hip; dav_set_operator_bsr_dev) -----------------------------------------------
 // The index level is the CSR build above over the n / b block rows with the block source as payload.  Then the values move once:
 // val[q b^2 + k b + m] = entry (tr ? k : m, tr ? m : k) of input block p, for canonical block q with src[q] = p << 1 | tr; rowmaj: the

@@ -170,6 +170,107 @@ def check_csr(indptr, indices, data, n, base=0, lower=False):
     return rp, ci, vv
 
 
+def is_torch_coo(t):
+    """True for a torch tensor in the sparse COO layout (torch itself is imported only when the object comes from it)"""
+    if not type(t).__module__.startswith("torch"):
+        return False
+    import torch
+    return isinstance(t, torch.Tensor) and t.layout == torch.sparse_coo
+
+
+def torch_coo_parts(t):
+    """(rows, cols, values) of a torch sparse COO tensor AS THEY STAND - _indices() and _values(), coalesced or not, duplicates
+    included; on the CPU as numpy arrays"""
+    if t.dim() != 2 or t.shape[0] != t.shape[1] or t.dense_dim() != 0:
+        raise ValueError(f"COO input: a square matrix of scalars is needed, the tensor has shape {tuple(t.shape)}")
+    idx, vals = t._indices(), t._values()
+    parts = (idx[0].contiguous(), idx[1].contiguous(), vals.contiguous())
+    if t.device.type == "cpu":
+        return tuple(x.numpy() for x in parts)
+    return parts
+
+
+def coo_triples(rows, cols=None, vals=None):
+    """(rows, cols, vals) of COO input as it stands: three arrays, or one object with .row, .col and .data (a scipy coo_matrix - read
+    without sum_duplicates() and without tocsr(); scipy itself is never imported here), or a torch.sparse_coo_tensor.  Torch tensors
+    on the CPU - the parts of a COO tensor, or three tensors given one by one - come back as numpy arrays (the host path); tensors on a
+    GPU stay tensors (the device path)."""
+    def host(a):
+        if type(a).__module__.startswith("torch") and hasattr(a, "device") and a.device.type == "cpu":
+            return a.detach().contiguous().numpy()
+        return a
+    if cols is None and vals is None:
+        if is_torch_coo(rows):
+            return torch_coo_parts(rows)
+        if all(hasattr(rows, name) for name in ("row", "col", "data")):
+            return rows.row, rows.col, rows.data
+    if cols is None or vals is None:
+        raise DavidsonHipError("COO input: rows, cols and vals are all needed (or one object with .row, .col and .data, or a "
+                               "torch.sparse_coo_tensor)")
+    return host(rows), host(cols), host(vals)
+
+
+def coo_arrays(rows, cols=None, vals=None):
+    """(rows int32, cols int32, vals float64) of COO input in host memory (coo_triples says what is accepted), the triples in their
+    order.  Checks only what keeps the C call inside the arrays: three one-dimensional arrays of one length.  An index that does not
+    fit int32 becomes -2^31 or 2^31 - 1, which the engine refuses as out of range at that triple."""
+    rows, cols, vals = coo_triples(rows, cols, vals)
+    out = []
+    for a in (rows, cols):
+        a = np.ascontiguousarray(a)
+        if a.dtype.kind not in "iu":
+            raise DavidsonHipError(f"COO input: indices must be integers, not {a.dtype}")
+        if a.dtype != np.int32:
+            a = np.clip(a, -2**31 if a.dtype.kind == "i" else 0, 2**31 - 1).astype(np.int32)
+        out.append(a)
+    vv = np.ascontiguousarray(vals, dtype=np.float64)
+    if any(a.ndim != 1 for a in (*out, vv)) or not out[0].size == out[1].size == vv.size:
+        raise DavidsonHipError(f"COO input: rows / cols / vals hold {out[0].size} / {out[1].size} / {vv.size} values: three "
+                               "one-dimensional arrays of one length are needed")
+    return out[0], out[1], vv
+
+
+def check_coo(rows, cols, vals, n, base=0, lower=False):
+    """Everything davx_set_operator_coo validates, checked in Python (ValueError) - for the Fortran doors, which stop the process on an
+    engine error.  Returns the arrays as coo_arrays does."""
+    try:
+        ri, ci, vv = coo_arrays(rows, cols, vals)
+    except DavidsonHipError as exc:
+        raise ValueError(str(exc)) from None
+    if base not in (0, 1):
+        raise ValueError("COO input: index base must be 0 or 1")
+    if vv.size >= 2**32:
+        raise ValueError("COO input: fewer than 2^32 triples are needed")
+    i, j = ri.astype(np.int64) - base, ci.astype(np.int64) - base
+    bad = (i < 0) | (i >= n) | (j < 0) | (j >= n) | ((j > i) if lower else False)
+    if bad.any():
+        p = int(np.argmax(bad))
+        what = "lies above the diagonal with lower=True" if 0 <= i[p] < n and 0 <= j[p] < n else f"is out of range [{base}, {n + base})"
+        raise ValueError(f"COO input: triple {p + base} at ({ri[p]}, {ci[p]}) {what}")
+    return ri, ci, vv
+
+
+def _device_coo_tensors(rows, cols, vals, device):
+    """The checks of COO triples in device tensors before any library call: int32 / int64 indices and float64 values (TypeError, never
+    converted), contiguous one-dimensional tensors of one length on cuda:`device` (ValueError).  Returns (row_bits, col_bits, nnz)."""
+    import torch
+    args = (("rows", rows, (torch.int32, torch.int64)), ("cols", cols, (torch.int32, torch.int64)), ("vals", vals, (torch.float64,)))
+    for name, t, kinds in args:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"device COO input: {name} must be a torch tensor, not {type(t).__name__}")
+        if t.dtype not in kinds:
+            raise TypeError(f"device COO input: {name} has dtype {t.dtype}, expected " + " or ".join(str(k) for k in kinds))
+    for name, t, _ in args:
+        if t.layout != torch.strided or not t.is_contiguous() or t.dim() != 1:
+            raise ValueError(f"device COO input: {name} must be a contiguous one-dimensional tensor")
+    for name, t, _ in args:
+        if t.device.type != "cuda" or t.device.index != device:
+            raise ValueError(f"device COO input: {name} lies on {t.device}, the engine on cuda:{device}")
+    if not rows.numel() == cols.numel() == vals.numel():
+        raise ValueError(f"device COO input: rows / cols / vals hold {rows.numel()} / {cols.numel()} / {vals.numel()} values")
+    return (64 if rows.dtype == torch.int64 else 32), (64 if cols.dtype == torch.int64 else 32), vals.numel()
+
+
 BSR_ROW_MAJOR, BSR_COL_MAJOR = 0, 1
 
 
@@ -528,6 +629,38 @@ class CEngine:
         torch.cuda.current_stream(row_ptr.device).synchronize()
         self._saw_values(which, None)
         self._chk(self.lib.dav_set_operator_csr_dev(self.h, which, row_ptr.data_ptr(), rpb, col_idx.data_ptr() or None, cib,
+                                                    vals.data_ptr() or None, base, csr_flag_word(lower, diagonals)))
+        self._saw_values(which, nnz)
+
+    def set_operator_coo(self, which, rows, cols=None, vals=None, base=0, lower=False, diagonals=False):
+        """davx_set_operator_coo: the symmetric matrix of set_operator_csr as COO triples (rows[p], cols[p], vals[p]) in any order,
+        duplicates included and kept as separate terms in the order of p - the operator is, bit for bit, that of the CSR matrix a
+        stable sort of the triples by row gives.  Three numpy arrays, or a scipy coo_matrix (its .row, .col and .data as they stand:
+        no sum_duplicates, no tocsr), or a torch.sparse_coo_tensor (its _indices() and _values() as they stand, coalesced or not; one
+        on the GPU goes to set_operator_coo_dev).  The engine validates the input (DavidsonHipError names the first offending
+        triple) and leaves the operator unset when it refuses it.  After keep_value_map, update_operator_values takes the values in
+        the order of the triples.  lower, diagonals: as for set_operator_csr."""
+        rows, cols, vals = coo_triples(rows, cols, vals)
+        if type(vals).__module__.startswith("torch"):
+            return self.set_operator_coo_dev(which, rows, cols, vals, base=base, lower=lower, diagonals=diagonals)
+        ri, ci, vv = coo_arrays(rows, cols, vals)
+        i32p = C.POINTER(C.c_int32)
+        self._saw_values(which, None)
+        self._chk(self.lib.davx_set_operator_coo(self.h, which, vv.size, ri.ctypes.data_as(i32p) if vv.size else None,
+                                                ci.ctypes.data_as(i32p) if vv.size else None, _dp(vv) if vv.size else None, base,
+                                                csr_flag_word(lower, diagonals)))
+        self._saw_values(which, int(vv.size))
+
+    def set_operator_coo_dev(self, which, rows, cols, vals, base=0, lower=False, diagonals=False):
+        """davx_set_operator_coo_dev: the triples of set_operator_coo as torch tensors on the engine's device, bucketed by row and
+        sorted on the GPU - rows and cols int32 or int64, vals float64, all contiguous and of one length.  Other dtypes are a TypeError
+        (never converted).  Torch's current stream on the device is synchronised first.  The engine's refusal is a DavidsonHipError;
+        the operator is then unset."""
+        rb, cb, nnz = _device_coo_tensors(rows, cols, vals, self.device)
+        import torch
+        torch.cuda.current_stream(vals.device).synchronize()
+        self._saw_values(which, None)
+        self._chk(self.lib.davx_set_operator_coo_dev(self.h, which, nnz, rows.data_ptr() or None, rb, cols.data_ptr() or None, cb,
                                                     vals.data_ptr() or None, base, csr_flag_word(lower, diagonals)))
         self._saw_values(which, nnz)
 

@@ -405,6 +405,8 @@ module davidson_csr
   public :: generalized_eigensolver_sparse, generalized_eigensolver_bsr, generalized_eigensolver_sparse_guess, generalized_eigensolver_bsr_guess
   public :: generalized_eigensolver_sparse_precond_csr, generalized_eigensolver_sparse_precond_bsr, generalized_eigensolver_bsr_precond_csr, &
        generalized_eigensolver_bsr_precond_bsr
+  public :: generalized_eigensolver_coo, generalized_eigensolver_coo_precond_coo, generalized_eigensolver_coo_precond_csr, &
+       generalized_eigensolver_coo_precond_bsr
 
 contains
 
@@ -628,6 +630,115 @@ contains
          max_dim_sub, second_matrix, initial_vectors, precond_bsr=preconditioner)
   end subroutine generalized_eigensolver_bsr_precond_bsr
 
+  !> COO front-end: the argument list of the sparse specific with coo_matrix operators (module davidson_sparse) - unordered triples,
+  !> duplicates kept as separate terms.  The operators built are those of the csr_matrix a stable sort by row gives, bit for bit.
+  subroutine coo_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix, initial_vectors, precond_coo, precond_csr, precond_bsr)
+    integer, intent(in) :: lowest
+    real(dp), dimension(:, :), intent(in), optional :: initial_vectors
+    type(coo_matrix), intent(in) :: matrix
+    type(coo_matrix), intent(in), optional :: second_matrix
+    type(coo_matrix), intent(in), optional :: precond_coo      !< preconditioner= of the front ends: slot 3 of the engine
+    type(csr_matrix), intent(in), optional :: precond_csr
+    type(bsr_matrix), intent(in), optional :: precond_bsr
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    real(dp), dimension(:, :), intent(out) :: eigenvectors
+    integer, intent(in) :: max_iterations
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), intent(in) :: tolerance
+    character(len=*), intent(in) :: method
+    integer, intent(out) :: iters
+
+    type(davidson_engine) :: eng
+    integer :: max_dim
+
+    max_dim = default_max_dim(lowest, max_dim_sub)
+    call engine_create(eng, matrix%n, lowest, max_dim, present(second_matrix), env_device())
+    call engine_set_sparse(eng, 1, matrix)
+    if (present(second_matrix)) call engine_set_sparse(eng, 2, second_matrix)
+    if (present(precond_coo)) call engine_set_sparse(eng, 3, precond_coo)
+    if (present(precond_csr)) call engine_set_sparse(eng, 3, precond_csr)
+    if (present(precond_bsr)) call engine_set_sparse(eng, 3, precond_bsr)
+    call device_solve_impl(eng, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+         tolerance, iters, max_dim, initial_vectors)
+    call engine_destroy(eng)
+  end subroutine coo_solve_impl
+
+  !> The specific of the generic for a coo_matrix, with initial_vectors= (keyword)
+  subroutine generalized_eigensolver_coo(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix, initial_vectors)
+    integer, intent(in) :: lowest
+    type(coo_matrix), intent(in) :: matrix
+    type(coo_matrix), intent(in), optional :: second_matrix
+    real(dp), dimension(:, :), intent(out) :: eigenvectors
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    real(dp), dimension(:, :), intent(in), optional :: initial_vectors
+    call coo_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub, second_matrix, initial_vectors)
+  end subroutine generalized_eigensolver_coo
+
+  !> The same with preconditioner=, a coo_matrix (slot 3 of the engine); initial_vectors= may accompany it.
+  subroutine generalized_eigensolver_coo_precond_coo(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix, preconditioner, initial_vectors)
+    integer, intent(in) :: lowest
+    type(coo_matrix), intent(in) :: matrix
+    type(coo_matrix), intent(in), optional :: second_matrix
+    real(dp), dimension(:, :), intent(out) :: eigenvectors
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    type(coo_matrix), intent(in) :: preconditioner
+    real(dp), dimension(:, :), intent(in), optional :: initial_vectors
+    call coo_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub, second_matrix, initial_vectors, precond_coo=preconditioner)
+  end subroutine generalized_eigensolver_coo_precond_coo
+
+  !> The same with preconditioner=, a csr_matrix (slot 3 of the engine); initial_vectors= may accompany it.
+  subroutine generalized_eigensolver_coo_precond_csr(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix, preconditioner, initial_vectors)
+    integer, intent(in) :: lowest
+    type(coo_matrix), intent(in) :: matrix
+    type(coo_matrix), intent(in), optional :: second_matrix
+    real(dp), dimension(:, :), intent(out) :: eigenvectors
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    type(csr_matrix), intent(in) :: preconditioner
+    real(dp), dimension(:, :), intent(in), optional :: initial_vectors
+    call coo_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub, second_matrix, initial_vectors, precond_csr=preconditioner)
+  end subroutine generalized_eigensolver_coo_precond_csr
+
+  !> The same with preconditioner=, a bsr_matrix (slot 3 of the engine); initial_vectors= may accompany it.
+  subroutine generalized_eigensolver_coo_precond_bsr(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix, preconditioner, initial_vectors)
+    integer, intent(in) :: lowest
+    type(coo_matrix), intent(in) :: matrix
+    type(coo_matrix), intent(in), optional :: second_matrix
+    real(dp), dimension(:, :), intent(out) :: eigenvectors
+    integer, intent(in), optional :: max_dim_sub
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    type(bsr_matrix), intent(in) :: preconditioner
+    real(dp), dimension(:, :), intent(in), optional :: initial_vectors
+    call coo_solve_impl(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters, &
+         max_dim_sub, second_matrix, initial_vectors, precond_bsr=preconditioner)
+  end subroutine generalized_eigensolver_coo_precond_bsr
+
 end module davidson_csr
 
 
@@ -637,17 +748,19 @@ module davidson
   use davidson_free, only: generalized_eigensolver_free, generalized_eigensolver_free_guess
   use davidson_device, only: generalized_eigensolver_device, generalized_eigensolver_device_guess, davidson_free_buffers, engine_set_initial_vectors, &
        engine_set_initial_vectors_device, engine_keep_result_as_guess
-  use davidson_sparse, only: csr_matrix, bsr_matrix
+  use davidson_sparse, only: csr_matrix, bsr_matrix, coo_matrix
+  use davidson_csr, only: generalized_eigensolver_coo, generalized_eigensolver_coo_precond_coo, generalized_eigensolver_coo_precond_csr, &
+       generalized_eigensolver_coo_precond_bsr
   use davidson_csr, only: generalized_eigensolver_sparse, generalized_eigensolver_bsr, generalized_eigensolver_sparse_guess, &
        generalized_eigensolver_bsr_guess, generalized_eigensolver_sparse_precond_csr, generalized_eigensolver_sparse_precond_bsr, &
        generalized_eigensolver_bsr_precond_csr, generalized_eigensolver_bsr_precond_bsr
   implicit none
   private
-  public :: generalized_eigensolver, davidson_free_buffers, csr_matrix, bsr_matrix, engine_set_initial_vectors, &
+  public :: generalized_eigensolver, davidson_free_buffers, csr_matrix, bsr_matrix, coo_matrix, engine_set_initial_vectors, &
        engine_set_initial_vectors_device, engine_keep_result_as_guess
 
   !> Generic of the reference (src/davidson.f90:601-625), resolved by the first argument: a matrix,
-  !> a block-apply procedure, (new) a device-resident `davidson_engine`, or (new) a sparse `csr_matrix` / `bsr_matrix`.
+  !> a block-apply procedure, (new) a device-resident `davidson_engine`, or (new) a sparse `csr_matrix` / `bsr_matrix` / `coo_matrix`.
   interface generalized_eigensolver
      procedure generalized_eigensolver_dense
      procedure generalized_eigensolver_free
@@ -662,6 +775,10 @@ module davidson
      procedure generalized_eigensolver_sparse_precond_csr
      procedure generalized_eigensolver_sparse_precond_bsr
      procedure generalized_eigensolver_bsr_precond_csr
+     procedure generalized_eigensolver_coo
+     procedure generalized_eigensolver_coo_precond_coo
+     procedure generalized_eigensolver_coo_precond_csr
+     procedure generalized_eigensolver_coo_precond_bsr
      procedure generalized_eigensolver_bsr_precond_bsr
   end interface generalized_eigensolver
 

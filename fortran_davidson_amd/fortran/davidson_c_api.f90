@@ -9,7 +9,7 @@ module davidson_c_api
   use davidson_device
   use davidson_free, only: free_matmul
   use davidson_sparse, only: csr_matrix, bsr_matrix, engine_set_sparse, engine_set_sparse_device, engine_set_block_sparse_device, &
-       engine_keep_value_map, engine_update_sparse_values, engine_update_sparse_values_device
+       coo_matrix, engine_set_coo_device, engine_keep_value_map, engine_update_sparse_values, engine_update_sparse_values_device
   use davidson_hip_c, only: DAV_CSR_LOWER, DAV_CSR_DIAGONALS, DAV_BSR_ROW_MAJOR, DAV_BSR_COL_MAJOR, dav_set_operator_bsr_dev
   use lapack_wrapper
   use array_utils
@@ -347,6 +347,42 @@ contains
          row_ptr_bits=int(rp_bits), col_bits=int(col_bits), stat=st, diagonals=iand(lower, DAV_CSR_DIAGONALS) /= 0)
     stat = int(st, c_int)
   end function fd_engine_set_sparse_device
+
+  !> engine_set_sparse(eng, which, a) with a coo_matrix from C arrays of nnz triples numbered from `base`: renumbered from 1
+  subroutine fdx_engine_set_coo(p, which, n, nnz, row, col, vals, base, lower) bind(C, name="fdx_engine_set_coo")
+    type(c_ptr), value :: p
+    integer(c_int), value :: which, n, base, lower
+    integer(c_int64_t), value :: nnz
+    integer(c_int32_t), intent(in) :: row(*), col(*)
+    real(c_double), intent(in) :: vals(*)
+    type(davidson_engine), pointer :: eng
+    type(coo_matrix) :: a
+    call c_f_pointer(p, eng)
+    a%n = int(n)
+    a%row_idx = row(1:nnz) + (1_c_int32_t - base)
+    a%col_idx = col(1:nnz) + (1_c_int32_t - base)
+    a%values = vals(1:nnz)
+    a%lower = iand(lower, DAV_CSR_LOWER) /= 0
+    a%diagonals = iand(lower, DAV_CSR_DIAGONALS) /= 0
+    call engine_set_sparse(eng, int(which), a)
+  end subroutine fdx_engine_set_coo
+
+  !> engine_set_coo_device(eng, which, n, nnz, ...) with device arrays of COO triples: returns the engine's status, as
+  !> fd_engine_set_sparse_device does; `lower` is the same flag word
+  function fdx_engine_set_coo_device(p, which, n, nnz, row, row_bits, col, col_bits, vals, base, lower) result(stat) &
+       bind(C, name="fdx_engine_set_coo_device")
+    type(c_ptr), value :: p
+    integer(c_int), value :: which, n, row_bits, col_bits, base, lower
+    integer(c_int64_t), value :: nnz
+    type(c_ptr), value :: row, col, vals
+    integer(c_int) :: stat
+    type(davidson_engine), pointer :: eng
+    integer :: st
+    call c_f_pointer(p, eng)
+    call engine_set_coo_device(eng, int(which), int(n), nnz, row, col, vals, base=int(base), lower=iand(lower, DAV_CSR_LOWER) /= 0, &
+         row_bits=int(row_bits), col_bits=int(col_bits), stat=st, diagonals=iand(lower, DAV_CSR_DIAGONALS) /= 0)
+    stat = int(st, c_int)
+  end function fdx_engine_set_coo_device
 
   !> engine_set_sparse(eng, which, a) with a bsr_matrix from C arrays numbered from `base` (values in Fortran order, as bsr_from_c)
   subroutine fd_engine_set_block_sparse(p, which, n, b, rp, col, vals, base, lower) bind(C, name="fd_engine_set_block_sparse")

@@ -187,6 +187,34 @@ module davidson_hip_c
        integer(c_int), value :: index_base, triangle
        integer(c_int) :: ierr
      end function
+     !> the same matrix as COO triples in any order, duplicates kept as separate terms: global host arrays
+     function davx_set_operator_coo(h, which, nnz, row_idx, col_idx, vals, index_base, triangle) bind(C, name="davx_set_operator_coo") &
+          result(ierr)
+       import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+       type(c_ptr), value :: h
+       integer(c_int), value :: which
+       integer(c_int64_t), value :: nnz
+       integer(c_int32_t), intent(in) :: row_idx(*)
+       integer(c_int32_t), intent(in) :: col_idx(*)
+       real(c_double), intent(in) :: vals(*)
+       integer(c_int), value :: index_base, triangle
+       integer(c_int) :: ierr
+     end function
+     !> the triples from device arrays of the engine's device, bucketed and sorted on the GPU (row_bits / col_bits: 32 or 64)
+     function davx_set_operator_coo_dev(h, which, nnz, row_idx, row_bits, col_idx, col_bits, vals, index_base, triangle) &
+          bind(C, name="davx_set_operator_coo_dev") result(ierr)
+       import :: c_ptr, c_int, c_int64_t
+       type(c_ptr), value :: h
+       integer(c_int), value :: which
+       integer(c_int64_t), value :: nnz
+       type(c_ptr), value :: row_idx
+       integer(c_int), value :: row_bits
+       type(c_ptr), value :: col_idx
+       integer(c_int), value :: col_bits
+       type(c_ptr), value :: vals
+       integer(c_int), value :: index_base, triangle
+       integer(c_int) :: ierr
+     end function
      !> a BSR matrix from device arrays of the engine's device, built on the GPU (row_ptr_bits / col_bits: 32 or 64)
      function dav_set_operator_bsr_dev(h, which, block_size, block_row_ptr, row_ptr_bits, block_col_idx, col_bits, vals, index_base, &
           triangle, block_layout) bind(C, name="dav_set_operator_bsr_dev") result(ierr)

@@ -1,7 +1,8 @@
 !> Sparse operators: a symmetric real matrix in CSR (compressed sparse row) or BSR (block sparse row) form, 1-based as Fortran numbers
 !> rows and columns, and engine_set_sparse, which hands either to a device-resident problem (dav_set_operator_csr / dav_set_operator_bsr,
 !> include/davidson_hip.h); engine_set_sparse_device / engine_set_block_sparse_device take the same matrices from device arrays.  The solves of a csr_matrix / bsr_matrix are the specifics generalized_eigensolver_sparse /
-!> generalized_eigensolver_bsr of the generic generalized_eigensolver (module davidson).
+!> generalized_eigensolver_bsr of the generic generalized_eigensolver (module davidson).  A coo_matrix holds the same matrix as unordered
+!> (row, column, value) triples, duplicates included (davx_set_operator_coo); engine_set_coo_device takes the triples from device arrays.
 module davidson_sparse
   use, intrinsic :: iso_c_binding
   use numeric_kinds, only: dp
@@ -10,6 +11,7 @@ module davidson_sparse
   implicit none
   private
   public :: csr_matrix, bsr_matrix, engine_set_sparse, engine_set_sparse_device, engine_set_block_sparse_device
+  public :: coo_matrix, engine_set_coo_device
   public :: engine_keep_value_map, engine_update_sparse_values, engine_update_sparse_values_device
 
   !> A symmetric real matrix of order n in CSR form, 1-based: the entries of row i are col_idx / values(row_ptr(i) : row_ptr(i+1) - 1).
@@ -31,6 +33,23 @@ module davidson_sparse
      module procedure new_csr_matrix
   end interface csr_matrix
 
+  !> A symmetric real matrix of order n as COO triples, 1-based: entry p is values(p) at (row_idx(p), col_idx(p)).  The triples may come
+  !> in any order and may repeat a position: duplicates stay separate terms, in the order of p.  The operator built is, bit for bit,
+  !> that of the csr_matrix obtained by a stable sort of the triples by row.  lower and diagonals: as for csr_matrix.
+  type :: coo_matrix
+     integer :: n = 0
+     integer(c_int32_t), allocatable :: row_idx(:)
+     integer(c_int32_t), allocatable :: col_idx(:)
+     real(dp), allocatable :: values(:)
+     logical :: lower = .false.
+     logical :: diagonals = .false.
+  end type coo_matrix
+
+  !> coo_matrix(n, row_idx, col_idx, values [, lower] [, diagonals]) from default-kind integer arrays, 1-based
+  interface coo_matrix
+     module procedure new_coo_matrix
+  end interface coo_matrix
+
   !> A symmetric real matrix of order n in BSR form with square blocks of a uniform size block_size = b (1..16, n a multiple of b),
   !> 1-based: the blocks of block row I are col_idx / values(:, :, row_ptr(I) : row_ptr(I+1) - 1), values(m, k, p) the entry (m, k) of
   !> block p.  lower = .true.: only the blocks with block column <= block row are given (a diagonal block in full; the engine mirrors
@@ -49,10 +68,11 @@ module davidson_sparse
      module procedure new_bsr_matrix
   end interface bsr_matrix
 
-  !> engine_set_sparse(eng, which, a) with a csr_matrix or a bsr_matrix
+  !> engine_set_sparse(eng, which, a) with a csr_matrix, a bsr_matrix or a coo_matrix
   interface engine_set_sparse
      module procedure engine_set_sparse_csr
      module procedure engine_set_sparse_bsr
+     module procedure engine_set_sparse_coo
   end interface engine_set_sparse
 
   !> engine_update_sparse_values(eng, which, values): new values on the kept pattern of a sparse operator set after
@@ -218,6 +238,97 @@ contains
     end if
     if (ierr == 0 .and. which == 1) eng%free_semantics = .false.
   end subroutine engine_set_sparse_device
+
+  function new_coo_matrix(n, row_idx, col_idx, values, lower, diagonals) result(a)
+    integer, intent(in) :: n
+    integer, intent(in) :: row_idx(:), col_idx(:)
+    real(dp), intent(in) :: values(:)
+    logical, intent(in), optional :: lower, diagonals
+    type(coo_matrix) :: a
+    if (size(row_idx) /= size(values) .or. size(col_idx) /= size(values)) then
+       print *, "coo_matrix: row_idx / col_idx / values hold ", size(row_idx), " / ", size(col_idx), " / ", size(values), &
+            " triples: the three must be of one length"
+       error stop
+    end if
+    a%n = n
+    a%row_idx = int(row_idx, c_int32_t)
+    a%col_idx = int(col_idx, c_int32_t)
+    a%values = values
+    if (present(lower)) a%lower = lower
+    if (present(diagonals)) a%diagonals = diagonals
+  end function new_coo_matrix
+
+  !> Operator A (which = 1), B (which = 2) or the preconditioner M (which = 3) of the engine from a coo_matrix: the operator of the
+  !> csr_matrix that a stable sort of the triples by row gives, bit for bit.  After engine_keep_value_map,
+  !> engine_update_sparse_values takes the values in the order of the triples.  The matrix is not referenced after the call.
+  subroutine engine_set_sparse_coo(eng, which, a)
+    type(davidson_engine), intent(inout) :: eng
+    integer, intent(in) :: which
+    type(coo_matrix), intent(in) :: a
+    real(dp) :: nothing(1)
+    integer(c_int) :: tri
+    tri = merge(DAV_CSR_LOWER, DAV_CSR_FULL, a%lower)
+    if (a%diagonals) tri = ior(tri, DAV_CSR_DIAGONALS)
+    if (a%n /= eng%n .or. .not. allocated(a%values)) then
+       print *, "engine_set_sparse: the matrix must be of order ", eng%n
+       error stop
+    end if
+    if (size(a%values) > 0) then
+       call check_dav(davx_set_operator_coo(eng%h, int(which - 1, c_int), int(size(a%values), c_int64_t), a%row_idx, a%col_idx, &
+            a%values, 1_c_int, tri), "davx_set_operator_coo")
+    else
+       nothing = 0.0_dp
+       call check_dav(davx_set_operator_coo(eng%h, int(which - 1, c_int), 0_c_int64_t, [0_c_int32_t], [0_c_int32_t], nothing, 1_c_int, &
+            tri), "davx_set_operator_coo")
+    end if
+    if (which == 1) eng%free_semantics = .false.
+  end subroutine engine_set_sparse_coo
+
+  !> Operator A (which = 1), B (which = 2) or the preconditioner M (which = 3) of the engine from nnz COO triples of a matrix of order
+  !> n whose arrays are DEVICE memory of the engine's device: davx_set_operator_coo_dev builds the operator on the GPU, bit for bit as
+  !> engine_set_sparse builds it from a coo_matrix holding the same triples.  base: 1 (default) or 0; lower: only entries with column
+  !> <= row are given; row_bits / col_bits: 32 (default) or 64.  The arrays must be complete when the call is made and are free again
+  !> when it returns.  stat present: a refused matrix returns its non-zero status here (dav_last_error says why; the operator is left
+  !> unset), otherwise the program stops.  diagonals = .true.: the matrix is stored by its diagonals.
+  subroutine engine_set_coo_device(eng, which, n, nnz, row_idx, col_idx, vals, base, lower, row_bits, col_bits, stat, diagonals)
+    type(davidson_engine), intent(inout) :: eng
+    integer, intent(in) :: which, n
+    integer(c_int64_t), intent(in) :: nnz
+    type(c_ptr), intent(in) :: row_idx, col_idx, vals
+    integer, intent(in), optional :: base, row_bits, col_bits
+    logical, intent(in), optional :: lower
+    integer, intent(out), optional :: stat
+    logical, intent(in), optional :: diagonals
+    integer(c_int) :: ib, rb, cb, tri, ierr
+    if (n /= eng%n) then
+       if (present(stat)) then
+          stat = -1
+          return
+       end if
+       print *, "engine_set_coo_device: the matrix must be of order ", eng%n
+       error stop
+    end if
+    ib = 1_c_int
+    rb = 32_c_int
+    cb = 32_c_int
+    tri = DAV_CSR_FULL
+    if (present(base)) ib = int(base, c_int)
+    if (present(row_bits)) rb = int(row_bits, c_int)
+    if (present(col_bits)) cb = int(col_bits, c_int)
+    if (present(lower)) then
+       if (lower) tri = DAV_CSR_LOWER
+    end if
+    if (present(diagonals)) then
+       if (diagonals) tri = ior(tri, DAV_CSR_DIAGONALS)
+    end if
+    ierr = davx_set_operator_coo_dev(eng%h, int(which - 1, c_int), nnz, row_idx, rb, col_idx, cb, vals, ib, tri)
+    if (present(stat)) then
+       stat = int(ierr)
+    else
+       call check_dav(ierr, "davx_set_operator_coo_dev")
+    end if
+    if (ierr == 0 .and. which == 1) eng%free_semantics = .false.
+  end subroutine engine_set_coo_device
 
   function new_bsr_matrix(n, b, row_ptr, col_idx, values, lower) result(a)
     integer, intent(in) :: n, b

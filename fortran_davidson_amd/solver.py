@@ -16,9 +16,9 @@ import ctypes as C
 import numpy as np
 
 from ._lib import fortran_lib, hip_lib
-from .engine_c import (CEngine, DavidsonHipError, _device_bsr_tensors, _device_csr_tensors, _dp, _f, _optional, check_bsr, check_csr,
-                       csr_flag_word, device_bsr_tensors, device_csr_tensors, guess_array, is_torch_bsr, is_torch_csr, torch_bsr_parts, torch_csr_parts,
-                       update_values_array)
+from .engine_c import (CEngine, DavidsonHipError, _device_bsr_tensors, _device_coo_tensors, _device_csr_tensors, _dp, _f, _optional, check_bsr,
+                       check_coo, check_csr, coo_triples, csr_flag_word, device_bsr_tensors, device_csr_tensors, guess_array, is_torch_bsr,
+                       is_torch_coo, is_torch_csr, torch_bsr_parts, torch_csr_parts, update_values_array)
 
 # The operator slots of DavidsonEngine, numbered as the Fortran routines number them.  OP_M is the caller's preconditioner - an
 # approximation of (A - sigma B)^-1, symmetric, for "GJD" positive definite - which "DPR" (T = M R) and "GJD" (its MINRES) apply in place
@@ -189,6 +189,16 @@ def generalized_eigensolver_sparse(indptr, indices, data, lowest, method, max_it
     matrix that does not suit the storage is refused).  Returns (eigenvalues, eigenvectors, iters)."""
     _check_method(method, a_sparse=True, blocks=(None, None), gev=second is not None, where="generalized_eigensolver_sparse")
     a = indptr if indices is None and data is None else (indptr, indices, data)
+    if is_torch_coo(a) or is_torch_coo(second):
+        # a torch.sparse_coo_tensor goes to the COO path as it stands (set_sparse routes each operator by its layout)
+        first = a if is_torch_coo(a) else second
+        n = a.shape[0] if hasattr(a, "shape") else len(a[0]) - 1
+        with DavidsonEngine(n, lowest, max_dim_sub, gev=second is not None,
+                            device=first.device.index if first.device.type != "cpu" else 0) as eng:
+            eng.set_sparse(1, a, lower=lower, diagonals=diagonals)
+            if second is not None:
+                eng.set_sparse(2, second, lower=lower, diagonals=diagonals)
+            return eng.solve(method, max_iterations, tolerance, initial_vectors=initial_vectors)
     if _is_device_csr(a) or _is_device_csr(second):
         # a matrix in device memory: an engine of its own, built on the GPU (DavidsonEngine.set_sparse)
         n = a.shape[0] if hasattr(a, "shape") else len(a[0]) - 1
@@ -217,6 +227,29 @@ def generalized_eigensolver_sparse(indptr, indices, data, lowest, method, max_it
                                   csr_flag_word(lower, diagonals), lowest, _method_code(method), max_iterations, tolerance, -1 if max_dim_sub is None else max_dim_sub,
                                   _dp(evals), _dp(evecs), C.byref(iters))
     return evals, evecs, iters.value
+
+
+def generalized_eigensolver_coo(rows, cols, vals, n, lowest, method, max_iterations, tolerance, max_dim_sub=None, second=None,
+                                lower=False, initial_vectors=None, diagonals=False):
+    """`call generalized_eigensolver(a_coo, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters [, max_dim_sub]
+    [, b_coo])` (the coo_matrix specific of module davidson) with A as COO triples, 0-based, in any order, duplicates kept as separate
+    terms: three arrays, or `rows` a scipy coo_matrix or a torch.sparse_coo_tensor and cols = vals = None (DavidsonEngine.set_coo
+    says how each is read).  n: the order of the matrix; None when the first argument carries a shape.  `second`: B the same way - a
+    tuple (rows, cols, vals) or one such object.  Triples in tensors on the GPU are built there.  lower, initial_vectors,
+    diagonals: as for generalized_eigensolver_sparse.  Returns (eigenvalues, eigenvectors, iters)."""
+    _check_method(method, a_sparse=True, blocks=(None, None), gev=second is not None, where="generalized_eigensolver_coo")
+    a = rows if cols is None and vals is None else (rows, cols, vals)
+    if n is None:
+        if not hasattr(a, "shape"):
+            raise ValueError("generalized_eigensolver_coo: n is needed when the triples come as three arrays")
+        n = int(a.shape[0])
+    on_gpu = [t for m in (a, second) if m is not None for t in (m if isinstance(m, tuple) else (m,))
+              if type(t).__module__.startswith("torch") and t.device.type != "cpu"]
+    with DavidsonEngine(n, lowest, max_dim_sub, gev=second is not None, device=on_gpu[0].device.index if on_gpu else 0) as eng:
+        eng.set_coo(1, *(a if isinstance(a, tuple) else (a,)), lower=lower, diagonals=diagonals)
+        if second is not None:
+            eng.set_coo(2, *(second if isinstance(second, tuple) else (second,)), lower=lower, diagonals=diagonals)
+        return eng.solve(method, max_iterations, tolerance, initial_vectors=initial_vectors)
 
 
 def _bsr_input(a, n, lower=False):
@@ -387,6 +420,8 @@ class DavidsonEngine:
         its diagonals (csr_matrix(..., diagonals=.true.)) - for stencils and banded matrices, also a scipy dia_matrix, for which the
         keyword stays explicit; a matrix with too many diagonals for its entries is refused (DavidsonHipError), never stored as CSR."""
         a = indptr if indices is None and data is None else (indptr, indices, data)
+        if is_torch_coo(a):         # the triples as they stand: the COO path (set_coo)
+            return self.set_coo(which, a, lower=lower, keep_map=keep_map, diagonals=diagonals)
         if _is_device_csr(a):
             return self._set_sparse_device(which, *torch_csr_parts(a), lower=lower, keep_map=keep_map, diagonals=diagonals)
         _, rp, ci, vv = _sparse_input(a, self.n, lower)
@@ -405,6 +440,34 @@ class DavidsonEngine:
                                                   vals.data_ptr() or None, 0, csr_flag_word(lower, diagonals))
         if st != 0:
             raise DavidsonHipError(hip_lib().dav_last_error().decode())
+        self._note_blocks(which, None, sparse=True)
+        if keep_map:
+            self._kept[which] = {"count": nnz, "b": 1, "fortran_blocks": False}
+
+    def set_coo(self, which, rows, cols=None, vals=None, lower=False, keep_map=False, diagonals=False):
+        """Operator A, B or the preconditioner M (which=1, 2, 3) as COO triples (rows[p], cols[p], vals[p]), 0-based, in any order and
+        with duplicates, which stay separate terms in the order of p (Fortran: engine_set_sparse with a coo_matrix): three arrays, or a
+        scipy coo_matrix (its .row, .col and .data as they stand - no sum_duplicates, no tocsr), or a torch.sparse_coo_tensor (its
+        _indices() and _values() as they stand, coalesced or not).  Tensors on the engine's GPU are bucketed and sorted there (Fortran:
+        engine_set_coo_device; a refused matrix raises DavidsonHipError and leaves the operator unset).  The operator equals, bit for
+        bit, that of set_sparse on the CSR matrix a stable sort of the triples by row gives.  lower, diagonals: as for set_sparse.
+        keep_map=True: update_values then takes the values in the order of the triples."""
+        rows, cols, vals = coo_triples(rows, cols, vals)
+        if type(vals).__module__.startswith("torch"):
+            rb, cb, nnz = _device_coo_tensors(rows, cols, vals, self.device)
+            self._keep_map(which, keep_map)
+            import torch
+            torch.cuda.current_stream(vals.device).synchronize()
+            st = self.lib.fdx_engine_set_coo_device(self.p, which, self.n, nnz, rows.data_ptr() or None, rb, cols.data_ptr() or None, cb,
+                                                   vals.data_ptr() or None, 0, csr_flag_word(lower, diagonals))
+            if st != 0:
+                raise DavidsonHipError(hip_lib().dav_last_error().decode())
+        else:
+            ri, ci, vv = check_coo(rows, cols, vals, self.n, 0, lower)
+            nnz = int(vv.size)
+            self._keep_map(which, keep_map)
+            self.lib.fdx_engine_set_coo(self.p, which, self.n, nnz, _i32(ri), _i32(ci), _dp(vv) if nnz else (C.c_double * 1)(), 0,
+                                       csr_flag_word(lower, diagonals))
         self._note_blocks(which, None, sparse=True)
         if keep_map:
             self._kept[which] = {"count": nnz, "b": 1, "fortran_blocks": False}
