@@ -13,7 +13,7 @@ the Fortran API through ctypes.  There is no CPU fallback anywhere: importing wo
 any compute call without one raises.
 """
 from .solver import (DavidsonEngine, generalized_eigensolver, generalized_eigensolver_bsr, generalized_eigensolver_sparse,  # noqa: F401
-                     generalized_eigensolver_coo, generate_diagonal_dominant,
+                     generalized_eigensolver_coo, generalized_eigensolver_hermitian, hermitian_eigenpairs, generate_diagonal_dominant,
                      lapack_generalized_eigensolver, lapack_qr, lapack_sort, generate_preconditioner,
                      lapack_matmul, lapack_solver, norm)
 from .engine_c import CEngine, DavidsonHipError, free_buffers  # noqa: F401

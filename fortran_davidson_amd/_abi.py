@@ -159,6 +159,17 @@ EXT_FD = {
     "fdx_engine_set_coo_device": (i32, (ptr, i32, i32, i64, ptr, i32, ptr, i32, ptr, i32, i32)),
 }
 
+# include/davidson_hip_herm.h: complex Hermitian CSR operators through their real form (prefix davh_) and their doors (prefix fdh_);
+# tests/test_herm_cpu.py compares both with the header and the Fortran sources
+HERM = {
+    "davh_set_operator_csr": (i32, (ptr, i32, ptr, ptr, ptr, i32, i32)),
+    "davh_set_operator_csr_dev": (i32, (ptr, i32, ptr, i32, ptr, i32, ptr, i32, i32)),
+}
+HERM_FD = {
+    "fdh_engine_set_hermitian": (None, (ptr, i32, i32, ptr, ptr, ptr, i32, i32)),
+    "fdh_engine_set_hermitian_device": (i32, (ptr, i32, i32, ptr, i32, ptr, i32, ptr, i32, i32)),
+}
+
 
 def apply(lib, table, optional=()):
     """Set restype and argtypes of every entry of `table` on `lib`.  An entry of `optional` that the library lacks is skipped; any

@@ -47,6 +47,7 @@ def hip_lib() -> C.CDLL:
         lib = C.CDLL(HIP_LIB, mode=C.RTLD_LOCAL)
         _abi.apply(lib, _abi.DAV, optional=_abi.TEST_BUILD_ONLY)       # raises before the library can be used without prototypes
         _abi.apply(lib, _abi.EXT)
+        _abi.apply(lib, _abi.HERM)
         _hip = lib
         runtimes = hip_runtimes_mapped()
         if len(runtimes) > 1:
@@ -81,5 +82,6 @@ def fortran_lib() -> C.CDLL:
         lib = C.CDLL(FORTRAN_LIB, mode=C.RTLD_GLOBAL)  # MKL dlopens its kernels and needs libmkl_core global
         _abi.apply(lib, _abi.FD)
         _abi.apply(lib, _abi.EXT_FD)
+        _abi.apply(lib, _abi.HERM_FD)
         _fortran = lib
     return _fortran

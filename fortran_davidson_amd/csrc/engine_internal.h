@@ -149,6 +149,8 @@ struct SparseStore {
   int64_t* dpos = nullptr;          // device: positions of the diagonal entries (blocks) in the caller's vals, row by row in input order
   int64_t gcount = 0;               // entries (blocks) of the caller's vals
   int triangle = 0, rowmaj = 0;     // of the set call: DAV_CSR_FULL / DAV_CSR_LOWER; BSR: the caller's blocks are row-major
+  int pairs = 0;                    // the value source of the set call: 0 = b * b doubles per block; 1 (davh_*, b = 2) = one (re, im) pair
+  int pairs_base = 0;               // pairs: the index base of the set call (a refused refresh names entry and row in it)
   // BSR, built at the first DAV_METHOD_BDPR correction (engine_bdpr.hip): the diagonal blocks of the local block rows, b x b column-major
   // each, duplicates summed in stored order; new values (dav_update_operator_values) make them stale, a set call releases them
   double* bdiag = nullptr;

@@ -1,6 +1,8 @@
 // Engine, sparse operators: a symmetric matrix in CSR or BSR form, given in host arrays (dav_set_operator_csr, dav_set_operator_bsr) or in
 // device arrays and built on the GPU (dav_set_operator_csr_dev, dav_set_operator_bsr_dev; kernels in k_csr_build.hip, k_bsr_build.hip);
 // a CSR matrix also as unordered COO triples (davx_set_operator_coo, davx_set_operator_coo_dev; k_coo_build.hip).
+// A complex Hermitian CSR matrix goes in as the BSR matrix of its 2 x 2 real blocks, its (re, im) values read where they lie
+// (davh_set_operator_csr, davh_set_operator_csr_dev; the pair kernels of k_bsr_build.hip).
 // All four entries follow one structure: the PATTERN - row_ptr and col_idx over rows or block rows - is validated; the
 // canonical order of this rank's rows is built with a PAYLOAD per column index (CSR: the value of the entry; BSR: the source of the block,
 // input position << 1 | mirrored); BSR gathers the VALUES from the sources; the DIAGONAL is summed per kind; one COMMIT step builds the
@@ -15,6 +17,7 @@
 #include "dia_rule.h"
 #include "coo_host.h"
 #include "davidson_hip_ext.h"
+#include "davidson_hip_herm.h"
 
 void sparse_release(E* e, OpDesc& o) {
   SparseStore& s = o.sp;
@@ -269,7 +272,7 @@ struct HostMap {
   std::vector<uint64_t> src;
   std::vector<int64_t> doff, dpos;
   int64_t gcount = 0;
-  int triangle = 0, rowmaj = 0;
+  int triangle = 0, rowmaj = 0, pairs = 0, base = 0;
 };
 std::string map_memory(const SparseWords& w) { return no_memory(std::string("the value map of the ") + w.items + " of this rank"); }
 
@@ -282,7 +285,7 @@ int commit_host(const Entry& en, int kind, int b, int64_t grow0, const std::vect
   if (!upload(&s.rp, rp) || !upload(&s.col, lcol) || !upload(&s.val, lval)) return en.refuse(oom);
   if (map) {
     if (!upload(&s.src, map->src) || !upload(&s.doff, map->doff) || !upload(&s.dpos, map->dpos)) return en.refuse(map_memory(en.w));
-    s.gcount = map->gcount; s.triangle = map->triangle; s.rowmaj = map->rowmaj;
+    s.gcount = map->gcount; s.triangle = map->triangle; s.rowmaj = map->rowmaj; s.pairs = map->pairs; s.pairs_base = map->base;
   }
   return sparse_commit(en, kind, b, grow0, rp, diag, nullptr, oom);
 }
@@ -406,26 +409,53 @@ extern "C" int davx_set_operator_coo(dav_handle_t e, int which, int64_t nnz, con
                       f.perm.data());
 }
 
-extern "C" int dav_set_operator_bsr(dav_handle_t e, int which, int block_size, const int64_t* block_row_ptr, const int32_t* block_col_idx,
-                                    const double* vals, int index_base, int triangle, int block_layout) {
-  CHK(entry_begin(e, which, "dav_set_operator_bsr"));
-  const Entry en{e, which, "dav_set_operator_bsr", BSR_WORDS};
+namespace {
+// ---- the (re, im) value source: a complex Hermitian CSR matrix as the BSR matrix of its 2 x 2 blocks (davh_*) ----------
+// the scalar arguments of a davh_ entry ("" = fine): the real order even, then what a CSR entry asks of the order n / 2
+std::string bad_arguments_herm(const SparseWords& w, int64_t n, int index_base, int triangle, const int* bits, const void* row_ptr) {
+  if (n % 2 != 0)
+    return "n = " + std::to_string(n) + " is odd: a Hermitian operator of order n / 2 needs an engine of the even real order n (re, im interleaved)";
+  const std::string why = bad_arguments(w, n / 2, false, 0, index_base, triangle, 0, bits, row_ptr);
+  if (!why.empty()) return why;
+  if (triangle & DAV_CSR_DIAGONALS) return "DAV_CSR_DIAGONALS serves the real CSR entries only: a Hermitian operator is stored by blocks";
+  return "";
+}
+// diagonal entry p of row i (both from 0) carries the imaginary part im: the real form would not be symmetric
+std::string msg_imag_diagonal(const SparseWords& w, int base, int64_t p, int64_t i, double im) {
+  char num[40];
+  snprintf(num, sizeof num, "%.17g", im);
+  return std::string("diagonal ") + w.item + " " + std::to_string(p + base) + " (" + w.row + " " + std::to_string(i + base) +
+         ") has the imaginary part " + num + ": the diagonal of a Hermitian matrix is real";
+}
+
+// The host BSR path behind dav_set_operator_bsr and davh_set_operator_csr.  pairs: vals holds one (re, im) pair (a, b) per block, b = 2,
+// standing for the row-major block [[a, -b], [b, a]]; the words and the scalar checks are the entry's own.
+int set_bsr_host(const Entry& en, int b, const int64_t* block_row_ptr, const int32_t* block_col_idx, const double* vals, int index_base,
+                 int triangle, int block_layout, bool pairs) {
+  E* e = en.e;
+  const int which = en.which;
   const int64_t n = e->n;
-  const int b = block_size;
-  std::string why = bad_arguments(en.w, n, true, b, index_base, triangle, block_layout, nullptr, block_row_ptr);
-  if (!why.empty()) return en.refuse(why);
+  std::string why;
   const int64_t nb = n / b, bb = (int64_t)b * b;
   int64_t ib0, nbl;
   local_block_rows(e, b, &ib0, &nbl);
   const HostPattern P{block_row_ptr, block_col_idx, nb, ib0, nbl, index_base, triangle == DAV_CSR_LOWER};
   if (!pattern_validate(P, vals, en.w, &why)) return en.refuse(why);
+  if (pairs)
+    for (int64_t I = 0; I < nb; ++I)
+      for (int64_t p = block_row_ptr[I] - index_base; p < block_row_ptr[I + 1] - index_base; ++p)
+        if ((int64_t)block_col_idx[p] - index_base == I && !(vals[2 * p + 1] == 0.0))
+          return en.refuse(msg_imag_diagonal(en.w, index_base, p, I, vals[2 * p + 1]));
   std::vector<int64_t> rp;
   std::vector<int32_t> lcol;
   std::vector<uint64_t> src;        // source of each canonical block: input block p << 1 | mirrored
   pattern_order(P, [](int64_t p, bool mirrored) { return (uint64_t)p << 1 | (uint64_t)mirrored; }, rp, lcol, src);
   // entry (m, k) of input block p in the caller's layout
   const bool rowmaj = block_layout == DAV_BSR_ROW_MAJOR;
-  auto entry = [&](int64_t p, int m, int k) { return vals[p * bb + (rowmaj ? (int64_t)m * b + k : (int64_t)k * b + m)]; };
+  auto entry = [&](int64_t p, int m, int k) {
+    if (pairs) return m == k ? vals[2 * p] : m > k ? vals[2 * p + 1] : -vals[2 * p + 1];          // -b: a sign flip
+    return vals[p * bb + (rowmaj ? (int64_t)m * b + k : (int64_t)k * b + m)];
+  };
   // values column-major per block: lval[q * b * b + k * b + m] = A_q[m][k] (a mirrored block is the transpose of its source)
   std::vector<double> lval(src.size() * (size_t)bb);
   for (size_t q = 0; q < src.size(); ++q) {
@@ -444,6 +474,8 @@ extern "C" int dav_set_operator_bsr(dav_handle_t e, int which, int block_size, c
     map.gcount = block_row_ptr[nb] - index_base;
     map.triangle = triangle;
     map.rowmaj = rowmaj ? 1 : 0;
+    map.pairs = pairs ? 1 : 0;
+    map.base = index_base;
   }
   for (int64_t I = 0; I < nb; ++I) {
     for (int64_t p = block_row_ptr[I] - index_base; p < block_row_ptr[I + 1] - index_base; ++p)
@@ -455,6 +487,26 @@ extern "C" int dav_set_operator_bsr(dav_handle_t e, int which, int block_size, c
   }
   if (keep_map) map.src.swap(src);          // the sources of the canonical blocks, as the order step left them
   return commit_host(en, DAV_KIND_BSR, b, ib0 * b - e->row0, rp, lcol, lval, diag, rp.back() * (8 * bb + 4), keep_map ? &map : nullptr);
+}
+}  // namespace
+
+extern "C" int dav_set_operator_bsr(dav_handle_t e, int which, int block_size, const int64_t* block_row_ptr, const int32_t* block_col_idx,
+                                    const double* vals, int index_base, int triangle, int block_layout) {
+  CHK(entry_begin(e, which, "dav_set_operator_bsr"));
+  const Entry en{e, which, "dav_set_operator_bsr", BSR_WORDS};
+  const std::string why = bad_arguments(en.w, e->n, true, block_size, index_base, triangle, block_layout, nullptr, block_row_ptr);
+  if (!why.empty()) return en.refuse(why);
+  return set_bsr_host(en, block_size, block_row_ptr, block_col_idx, vals, index_base, triangle, block_layout, false);
+}
+
+// A complex Hermitian CSR matrix of order n / 2 in host arrays: the host BSR path with b = 2 over the caller's pattern, reading pairs.
+extern "C" int davh_set_operator_csr(dav_handle_t e, int which, const int64_t* row_ptr, const int32_t* col_idx, const double* vals,
+                                     int index_base, int triangle) {
+  CHK(entry_begin(e, which, "davh_set_operator_csr"));
+  const Entry en{e, which, "davh_set_operator_csr", CSR_WORDS};
+  const std::string why = bad_arguments_herm(en.w, e->n, index_base, triangle, nullptr, row_ptr);
+  if (!why.empty()) return en.refuse(why);
+  return set_bsr_host(en, 2, row_ptr, col_idx, vals, index_base, triangle, DAV_BSR_ROW_MAJOR, true);
 }
 
 // ---- device arrays: the same steps on the GPU --------------------------------------------------------------------------------------------
@@ -856,23 +908,51 @@ extern "C" int davx_set_operator_coo_dev(dav_handle_t e, int which, int64_t nnz,
 // The index level is the CSR device build over the n / b block rows, local block rows = those that touch the slab, with the SOURCE of a
 // block (input position, mirrored or not) as payload; the values then move once (launch_bsr_build_gather).  Validation, canonical block
 // rows, values, diagonal and work list equal those of dav_set_operator_bsr bit for bit.
-extern "C" int dav_set_operator_bsr_dev(dav_handle_t e, int which, int block_size, const void* block_row_ptr, int row_ptr_bits,
-                                        const void* block_col_idx, int col_bits, const double* vals, int index_base, int triangle,
-                                        int block_layout) {
-  CHK(entry_begin(e, which, "dav_set_operator_bsr_dev"));
-  const Entry en{e, which, "dav_set_operator_bsr_dev", BSR_WORDS};
+// pairs (davh_set_operator_csr_dev): vals holds one (re, im) pair per block, b = 2; the 16 bytes of an entry are read where they lie -
+// by the diagonal pass, which runs right after the pattern is validated, before anything is allocated for the new operator (a refusal
+// releases the previous operator, as every refusal of a set entry does), and by the gather.
+namespace {
+int set_bsr_dev(const Entry& en, int b, const void* block_row_ptr, int row_ptr_bits, const void* block_col_idx, int col_bits, const double* vals,
+                int index_base, int triangle, int block_layout, bool pairs) {
+  E* e = en.e;
+  const int which = en.which;
   const int64_t n = e->n;
-  const int b = block_size, bits[2] = {row_ptr_bits, col_bits};
-  std::string why = bad_arguments(en.w, n, true, b, index_base, triangle, block_layout, bits, block_row_ptr);
-  if (!why.empty()) return en.refuse(why);
+  std::string why;
   const int64_t nb = n / b, bb = (int64_t)b * b;
   int64_t ib0, nbl;
   local_block_rows(e, b, &ib0, &nbl);
   BuildScratch sc(e->stream);
-  DevPattern P{block_row_ptr, row_ptr_bits == 64, block_col_idx, col_bits == 64, vals, 8 * (size_t)bb, nb, ib0, nbl, index_base,
+  DevPattern P{block_row_ptr, row_ptr_bits == 64, block_col_idx, col_bits == 64, vals, pairs ? 16 : 8 * (size_t)bb, nb, ib0, nbl, index_base,
                triangle == DAV_CSR_LOWER};
   std::vector<int64_t> rp;
-  if (int rc = pattern_begin_dev(en, sc, P, rp, &why)) return en.step(rc, why);
+  double* diag = nullptr;
+  if (pairs) {
+    if (((uintptr_t)vals & 15) != 0) return en.refuse("vals is not aligned to 16 bytes (one complex value)");
+    if (int rc = pattern_validate_dev(e, sc, P, en.w, &why)) return en.step(rc, why);
+    unsigned long long* bad = nullptr;
+    sc.take(&bad, 1);
+    diag = diag_scratch(sc, n, &why);
+    if (!diag) return en.refuse(why);
+    HIPCHK(hipMemsetAsync(bad, 0xff, sizeof(unsigned long long), e->stream));
+    launch_bsr_build_diag_pairs(e->stream, block_row_ptr, P.rp64, block_col_idx, P.ci64, vals, nb, index_base, P.dcount, P.dfirst, diag, bad);
+    unsigned long long first_bad = 0;
+    CHK(readback(e->stream, &first_bad, bad, sizeof(first_bad)));
+    if (first_bad != ~0ull) {          // the diagonal entry p lies in row col_idx[p]
+      int64_t* locate = nullptr;
+      sc.take(&locate, 2);
+      if (sc.oom) return en.refuse(no_memory("the validation"));
+      launch_csr_build_locate(e->stream, P.row_ptr, P.rp64, P.col_idx, P.ci64, nb, P.base, (int64_t)first_bad, locate);
+      int64_t loc[2];
+      double im = 0.0;
+      CHK(readback(e->stream, loc, locate, sizeof(loc)));
+      CHK(readback(e->stream, &im, vals + 2 * (int64_t)first_bad + 1, sizeof(im)));
+      return en.refuse(msg_imag_diagonal(en.w, index_base, (int64_t)first_bad, loc[0], im));
+    }
+    CHK(operator_goes(e, which, true));
+    if (int rc = pattern_offsets_dev(e, sc, P, en.w, &e->op[which].sp.rp, rp, &why)) return en.step(rc, why);
+  } else if (int rc = pattern_begin_dev(en, sc, P, rp, &why)) {
+    return en.step(rc, why);
+  }
   SparseStore& s = e->op[which].sp;
   const int64_t lnnzb = rp.back();
   const bool keep_map = e->keep_map[which] != 0;
@@ -883,14 +963,45 @@ extern "C" int dav_set_operator_bsr_dev(dav_handle_t e, int which, int block_siz
     return en.refuse(no_memory(stored(en.w, lnnzb, lnnzb * (8 * bb + 12))));
   if (int rc = pattern_order_dev(e, sc, P, en.w, s.rp, rp, s.col, src, &why)) return en.step(rc, why);
   // the values: column-major per block, a mirrored block the transpose of its source
-  launch_bsr_build_gather(e->stream, b, src, lnnzb, vals, block_layout == DAV_BSR_ROW_MAJOR ? 1 : 0, s.val);
-  double* diag = diag_scratch(sc, n, &why);
-  if (!diag) return en.refuse(why);
-  launch_bsr_build_diag(e->stream, b, block_row_ptr, P.rp64, block_col_idx, P.ci64, vals, nb, index_base, P.dcount, P.dfirst, diag);
-  if (keep_map)
+  if (pairs) {
+    launch_bsr_build_gather_pairs(e->stream, src, lnnzb, vals, s.val);
+  } else {
+    launch_bsr_build_gather(e->stream, b, src, lnnzb, vals, block_layout == DAV_BSR_ROW_MAJOR ? 1 : 0, s.val);
+    diag = diag_scratch(sc, n, &why);
+    if (!diag) return en.refuse(why);
+    launch_bsr_build_diag(e->stream, b, block_row_ptr, P.rp64, block_col_idx, P.ci64, vals, nb, index_base, P.dcount, P.dfirst, diag);
+  }
+  if (keep_map) {
     if (int rc = keep_diag_sources(en, sc, P, triangle, block_layout == DAV_BSR_ROW_MAJOR ? 1 : 0, &why)) return en.step(rc, why);
+    s.pairs = pairs ? 1 : 0;
+    s.pairs_base = index_base;
+  }
   std::vector<double> hdiag;
   return sparse_commit(en, DAV_KIND_BSR, b, ib0 * b - e->row0, rp, hdiag, diag, no_memory(work_list(en.w, lnnzb)));
+}
+}  // namespace
+
+extern "C" int dav_set_operator_bsr_dev(dav_handle_t e, int which, int block_size, const void* block_row_ptr, int row_ptr_bits,
+                                        const void* block_col_idx, int col_bits, const double* vals, int index_base, int triangle,
+                                        int block_layout) {
+  CHK(entry_begin(e, which, "dav_set_operator_bsr_dev"));
+  const Entry en{e, which, "dav_set_operator_bsr_dev", BSR_WORDS};
+  const int bits[2] = {row_ptr_bits, col_bits};
+  const std::string why = bad_arguments(en.w, e->n, true, block_size, index_base, triangle, block_layout, bits, block_row_ptr);
+  if (!why.empty()) return en.refuse(why);
+  return set_bsr_dev(en, block_size, block_row_ptr, row_ptr_bits, block_col_idx, col_bits, vals, index_base, triangle, block_layout, false);
+}
+
+// A complex Hermitian CSR matrix of order n / 2 in device arrays: the device BSR build with b = 2 over the caller's pattern, reading pairs.
+// No scratch holds expanded values.
+extern "C" int davh_set_operator_csr_dev(dav_handle_t e, int which, const void* row_ptr, int row_ptr_bits, const void* col_idx, int col_bits,
+                                         const double* vals, int index_base, int triangle) {
+  CHK(entry_begin(e, which, "davh_set_operator_csr_dev"));
+  const Entry en{e, which, "davh_set_operator_csr_dev", CSR_WORDS};
+  const int bits[2] = {row_ptr_bits, col_bits};
+  const std::string why = bad_arguments_herm(en.w, e->n, index_base, triangle, bits, row_ptr);
+  if (!why.empty()) return en.refuse(why);
+  return set_bsr_dev(en, 2, row_ptr, row_ptr_bits, col_idx, col_bits, vals, index_base, triangle, DAV_BSR_ROW_MAJOR, true);
 }
 
 // ---- new values on the kept pattern ------------------------------------------------------------------------------------------------------
@@ -925,13 +1036,34 @@ int update_from_device(E* e, int which, const char* name, BuildScratch& sc, cons
   double* diag = nullptr;          // the diagonal of the whole matrix (o.diag holds the local rows)
   sc.take(&diag, (size_t)e->n);
   if (sc.oom) return update_refuse(name, no_memory("the diagonal"));
-  if (o.kind == DAV_KIND_BSR) launch_bsr_build_gather(st, s.b, s.src, s.nnz, vals, s.rowmaj, s.val);
+  if (s.pairs) {          // (re, im) pairs: the diagonal first - an imaginary diagonal is refused before a value moves
+    unsigned long long* bad = nullptr;
+    sc.take(&bad, 1);
+    if (sc.oom) return update_refuse(name, no_memory("the diagonal"));
+    HIPCHK(hipMemsetAsync(bad, 0xff, sizeof(unsigned long long), st));
+    launch_bsr_refresh_diag_pairs(st, s.doff, s.dpos, vals, e->n / 2, diag, bad);
+    unsigned long long first_bad = 0;
+    CHK(readback(st, &first_bad, bad, sizeof(first_bad)));
+    if (first_bad != ~0ull) {          // the text of the set entries: the row of entry p from the kept diagonal sources (ascending in p)
+      const int64_t nb = e->n / 2, p = (int64_t)first_bad;
+      std::vector<int64_t> doff((size_t)nb + 1);
+      CHK(readback(st, doff.data(), s.doff, sizeof(int64_t) * doff.size()));
+      std::vector<int64_t> dpos((size_t)doff.back());
+      CHK(readback(st, dpos.data(), s.dpos, sizeof(int64_t) * dpos.size()));
+      const int64_t t = std::lower_bound(dpos.begin(), dpos.end(), p) - dpos.begin();
+      const int64_t row = std::upper_bound(doff.begin(), doff.end(), t) - doff.begin() - 1;
+      double im = 0.0;
+      CHK(readback(st, &im, vals + 2 * p + 1, sizeof(im)));
+      return update_refuse(name, msg_imag_diagonal(CSR_WORDS, s.pairs_base, p, row, im));
+    }
+    launch_bsr_build_gather_pairs(st, s.src, s.nnz, vals, s.val);
+  } else if (o.kind == DAV_KIND_BSR) launch_bsr_build_gather(st, s.b, s.src, s.nnz, vals, s.rowmaj, s.val);
   else launch_sparse_refresh_csr(st, s.src, s.nnz, vals, s.val);
   if (o.kind == DAV_KIND_DIA) dia_fill(e, s);        // the slots follow the values, as the set call filled them
   o.sp.bdiag_valid = false;          // the diagonal blocks of a BDPR correction follow the values: rebuilt at the next one
   o.sp.rbound_valid = false;         // ... and the row-sum bound of a CHEB correction
   o.lbound_valid = false;            // ... and the Lanczos bound of an LCHEB correction
-  launch_sparse_refresh_diag(st, s.b, s.doff, s.dpos, vals, e->n, diag);
+  if (!s.pairs) launch_sparse_refresh_diag(st, s.b, s.doff, s.dpos, vals, e->n, diag);
   if (e->nloc > 0) HIPCHK(hipMemcpyAsync(o.diag, diag + e->row0, sizeof(double) * e->nloc, hipMemcpyDeviceToDevice, st));
   // what depends on the numbers: the diagonal on the host and the start-vector order of A
   if (which == DAV_OP_A) e->basis_order.clear();
@@ -946,7 +1078,7 @@ extern "C" int dav_update_operator_values(dav_handle_t e, int which, const doubl
   const std::string why = not_updatable(e->op[which]);
   if (!why.empty()) return update_refuse(name, why);
   const SparseStore& s = e->op[which].sp;
-  const size_t count = (size_t)s.gcount * (size_t)s.b * (size_t)s.b;
+  const size_t count = (size_t)s.gcount * (s.pairs ? 2 : (size_t)s.b * (size_t)s.b);
   if (count > 0 && !vals) return update_refuse(name, "null vals");
   BuildScratch sc(e->stream);
   double* dvals = nullptr;
@@ -962,10 +1094,11 @@ extern "C" int dav_update_operator_values_dev(dav_handle_t e, int which, const d
   std::string why = not_updatable(e->op[which]);
   if (!why.empty()) return update_refuse(name, why);
   const SparseStore& s = e->op[which].sp;
-  const size_t count = (size_t)s.gcount * (size_t)s.b * (size_t)s.b;
+  const size_t count = (size_t)s.gcount * (s.pairs ? 2 : (size_t)s.b * (size_t)s.b);
   if (count > 0) {
     if (!vals_dev) return update_refuse(name, "null vals");
     if (!device_array(e, vals_dev, "vals", sizeof(double) * count, &why)) return update_refuse(name, why);
+    if (s.pairs && ((uintptr_t)vals_dev & 15) != 0) return update_refuse(name, "vals is not aligned to 16 bytes (one complex value)");
   }
   BuildScratch sc(e->stream);
   return update_from_device(e, which, name, sc, vals_dev);

@@ -13,6 +13,7 @@
 //         contiguous run of NB b^2 doubles: whole 128-byte segments on the output side for every b.  All loads of a thread are issued
 //         before its first LDS store.  b is a template parameter (1..16): every division of the element index is by a constant.
 // diag    one thread per row of the matrix: the diagonal blocks of its block row in input order from the first one the check pass found.
+// The same two steps for a complex Hermitian CSR matrix, whose values are (re, im) pairs (davh_set_operator_csr_dev): further down.
 #include "kernels.h"
 
 namespace {
@@ -92,6 +93,91 @@ __global__ __launch_bounds__(BG_THREADS) void bsr_build_diag_kernel(int b, const
   }
 }
 
+// ---- the (re, im) value source (davh_set_operator_csr(_dev)) ------------------------------------------------------------
+// Entry p of a complex Hermitian CSR matrix lies in the caller's vals as the pair (a, b) = vals[2 p], vals[2 p + 1] and stands for the
+// 2 x 2 block [[a, -b], [b, a]]; a mirrored block is its transpose, the block of conj(h).  The store is that of b = 2: column-major blocks.
+//
+// gather_pairs  two lanes per canonical block q, lane half h = one column (16 bytes) of the block: val[4 q + 2 h .. + 1] =
+//               h == 0 ? (a, tr ? -b : b) : (tr ? b : -b, a).  A wave stores 64 consecutive 16-byte columns (1 KiB, whole 128-byte
+//               segments) and reads 32 consecutive sources (256 bytes) and their pairs - consecutive for sorted FULL input, scattered for
+//               mirrored entries; the two lanes of a block read the same 16 bytes (one request).  -b is a sign flip: values are moved.
+//               All loads of a thread are issued before its first store.  40 bytes per block of this rank besides its 32 stored.
+// diag_pairs    one thread per block row I: s = +0.0 + the real parts of its diagonal entries in input order, diag[2 I] = diag[2 I + 1] = s
+//               (one 16-byte store).  A diagonal entry whose imaginary part is not +-0.0 (NaN included) is no Hermitian diagonal: the
+//               smallest such p goes to *bad by an integer atomicMin (the first per thread is its smallest).
+constexpr int BP_EPT = 4;                   // 16-byte columns per thread of gather_pairs
+constexpr int BP_TILE = BG_THREADS * BP_EPT;
+
+__global__ __launch_bounds__(BG_THREADS) void bsr_build_gather_pairs_kernel(const uint64_t* __restrict__ src, int64_t lnnzb,
+                                                                            const double2* __restrict__ pairs, double2* __restrict__ val) {
+  const int64_t t0 = (int64_t)blockIdx.x * BP_TILE + threadIdx.x, total = 2 * lnnzb;
+  uint64_t s[BP_EPT];
+  double2 z[BP_EPT];
+#pragma unroll
+  for (int u = 0; u < BP_EPT; ++u) {
+    const int64_t t = t0 + (int64_t)u * BG_THREADS;
+    s[u] = t < total ? src[t >> 1] : 0;
+  }
+#pragma unroll
+  for (int u = 0; u < BP_EPT; ++u) {
+    const int64_t t = t0 + (int64_t)u * BG_THREADS;
+    z[u] = t < total ? pairs[s[u] >> 1] : make_double2(0.0, 0.0);
+  }
+#pragma unroll
+  for (int u = 0; u < BP_EPT; ++u) {
+    const int64_t t = t0 + (int64_t)u * BG_THREADS;
+    if (t >= total) continue;
+    const bool tr = (s[u] & 1) != 0, second = (t & 1) != 0;
+    const double a = z[u].x, b = z[u].y;
+    val[t] = second ? make_double2(tr ? b : -b, a) : make_double2(a, tr ? -b : b);
+  }
+}
+
+template <class RP, class CI>
+__global__ __launch_bounds__(BG_THREADS) void bsr_build_diag_pairs_kernel(const RP* __restrict__ rp, const CI* __restrict__ col,
+                                                                          const double2* __restrict__ pairs, int64_t nb, int base,
+                                                                          const uint32_t* __restrict__ dcount,
+                                                                          const unsigned long long* __restrict__ dfirst,
+                                                                          double2* __restrict__ diag, unsigned long long* __restrict__ bad) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; I < nb; I += stride) {
+    const uint32_t cnt = dcount[I];
+    double s = 0.0;
+    if (cnt > 0) {
+      const int64_t p0 = (int64_t)dfirst[I], p1 = (int64_t)rp[I + 1] - base;
+      uint32_t seen = 0;
+      bool clean = true;
+      for (int64_t p = p0; p < p1 && seen < cnt; ++p)
+        if ((int64_t)col[p] - base == I) {
+          const double2 z = pairs[p];
+          s += z.x;
+          ++seen;
+          if (clean && !(z.y == 0.0)) { atomicMin(bad, (unsigned long long)p); clean = false; }
+        }
+    }
+    diag[I] = make_double2(s, s);
+  }
+}
+
+// the refresh: the same sums and the same check over the kept diagonal sources
+__global__ __launch_bounds__(BG_THREADS) void bsr_refresh_diag_pairs_kernel(const int64_t* __restrict__ doff, const int64_t* __restrict__ dpos,
+                                                                            const double2* __restrict__ pairs, int64_t nb,
+                                                                            double2* __restrict__ diag, unsigned long long* __restrict__ bad) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; I < nb; I += stride) {
+    const int64_t t1 = doff[I + 1];
+    double s = 0.0;
+    bool clean = true;
+    for (int64_t t = doff[I]; t < t1; ++t) {
+      const int64_t p = dpos[t];
+      const double2 z = pairs[p];
+      s += z.x;
+      if (clean && !(z.y == 0.0)) { atomicMin(bad, (unsigned long long)p); clean = false; }
+    }
+    diag[I] = make_double2(s, s);
+  }
+}
+
 template <int B>
 void bg_launch(hipStream_t st, const uint64_t* src, int64_t lnnzb, const double* vals, int rowmaj, double* val) {
   constexpr int NB = BgShape<B>::NB;
@@ -108,6 +194,27 @@ void launch_bsr_build_gather(hipStream_t st, int bs, const uint64_t* src, int64_
 #undef BG_CASE
     default: break;                          // the engine has refused any other block size
   }
+}
+
+void launch_bsr_build_gather_pairs(hipStream_t st, const uint64_t* src, int64_t lnnzb, const double* pairs, double* val) {
+  if (lnnzb <= 0) return;
+  hipLaunchKernelGGL(bsr_build_gather_pairs_kernel, dim3((unsigned)((2 * lnnzb + BP_TILE - 1) / BP_TILE)), dim3(BG_THREADS), 0, st, src, lnnzb,
+                     (const double2*)pairs, (double2*)val);
+}
+
+void launch_bsr_build_diag_pairs(hipStream_t st, const void* rp, int rp64, const void* col, int ci64, const double* pairs, int64_t nb, int base,
+                                 const uint32_t* dcount, const unsigned long long* dfirst, double* diag, unsigned long long* bad) {
+  if (nb <= 0) return;
+  const unsigned grid = (unsigned)std::min<int64_t>(8192, (nb + BG_THREADS - 1) / BG_THREADS);
+  cb_dispatch(rp64, ci64, [&](auto r_, auto c_) { using RP = decltype(r_); using CI = decltype(c_); hipLaunchKernelGGL((bsr_build_diag_pairs_kernel<RP, CI>), dim3(grid), dim3(BG_THREADS), 0, st, (const RP*)rp, (const CI*)col,
+                             (const double2*)pairs, nb, base, dcount, dfirst, (double2*)diag, bad); });
+}
+
+void launch_bsr_refresh_diag_pairs(hipStream_t st, const int64_t* doff, const int64_t* dpos, const double* pairs, int64_t nb, double* diag,
+                                   unsigned long long* bad) {
+  if (nb <= 0) return;
+  const unsigned grid = (unsigned)std::min<int64_t>(8192, (nb + BG_THREADS - 1) / BG_THREADS);
+  hipLaunchKernelGGL(bsr_refresh_diag_pairs_kernel, dim3(grid), dim3(BG_THREADS), 0, st, doff, dpos, (const double2*)pairs, nb, (double2*)diag, bad);
 }
 
 void launch_bsr_build_diag(hipStream_t st, int bs, const void* rp, int rp64, const void* col, int ci64, const double* vals, int64_t nb,

@@ -300,6 +300,15 @@ void launch_bsr_build_gather(hipStream_t st, int bs, const uint64_t* src, int64_
 // +0.0 (dcount / dfirst of the check pass over the block rows; entry (m, m) sits at m b + m in either layout)
 void launch_bsr_build_diag(hipStream_t st, int bs, const void* rp, int rp64, const void* col, int ci64, const double* vals, int64_t nb,
                            int base, const uint32_t* dcount, const unsigned long long* dfirst, double* diag);
+// The (re, im) value source of a complex Hermitian CSR matrix (davh_set_operator_csr(_dev), b = 2): pairs[2 p], pairs[2 p + 1] = (a, b) of
+// entry p stand for the block [[a, -b], [b, a]], 16-byte aligned.  val[4 q ..] = tr ? {a, -b, b, a} : {a, b, -b, a} (column-major).
+void launch_bsr_build_gather_pairs(hipStream_t st, const uint64_t* src, int64_t lnnzb, const double* pairs, double* val);
+// diag[2 I] = diag[2 I + 1] = +0.0 + the real parts of the diagonal entries of row I in input order, I < nb; *bad (~0 first) = the smallest
+// position of a diagonal entry whose imaginary part is not +-0.0.  The second form reads the kept diagonal sources (the refresh).
+void launch_bsr_build_diag_pairs(hipStream_t st, const void* rp, int rp64, const void* col, int ci64, const double* pairs, int64_t nb, int base,
+                                 const uint32_t* dcount, const unsigned long long* dfirst, double* diag, unsigned long long* bad);
+void launch_bsr_refresh_diag_pairs(hipStream_t st, const int64_t* doff, const int64_t* dpos, const double* pairs, int64_t nb, double* diag,
+                                   unsigned long long* bad);
 
 // ---- K1e: new values on the kept pattern of a sparse operator (k_sparse_refresh.hip; dav_update_operator_values) --------------------
 // The value map src[q] = p << 1 | mirrored of every canonical local entry (block) q, p the position in the caller's vals, and the

@@ -170,6 +170,90 @@ def check_csr(indptr, indices, data, n, base=0, lower=False):
     return rp, ci, vv
 
 
+def hermitian_arrays(indptr, indices=None, data=None, n=None):
+    """(indptr int64, indices int32, data complex128) of a complex Hermitian CSR matrix of order n given as three arrays, as one object
+    with .indptr, .indices and .data (a scipy csr_matrix of complex dtype, read as it stands; scipy itself is never imported here) or
+    as a complex torch.sparse_csr_tensor on the CPU.  complex128 values are handed over as they lie - no copy, no expansion into real
+    blocks: the engine reads the (re, im) pairs of the array itself.  Other dtypes are a TypeError (never converted).  Checks only
+    what keeps the C call inside the arrays."""
+    if is_torch_csr(indptr):
+        indptr, indices, data = torch_csr_parts(indptr)
+    elif indices is None and data is None and all(hasattr(indptr, name) for name in ("indptr", "indices", "data")):
+        indptr, indices, data = indptr.indptr, indptr.indices, indptr.data
+    if indices is None or data is None:
+        raise DavidsonHipError("Hermitian CSR input: indptr, indices and data are all needed (or one object with .indptr, .indices and .data)")
+    vv = np.asarray(data)
+    if vv.dtype != np.complex128:
+        raise TypeError(f"Hermitian CSR input: data has dtype {vv.dtype}, expected complex128")
+    vv = np.ascontiguousarray(vv)
+    rp = np.ascontiguousarray(indptr, dtype=np.int64)
+    ci = np.ascontiguousarray(indices)
+    if ci.size and (ci.min() < -2**31 or ci.max() >= 2**31):
+        raise DavidsonHipError("Hermitian CSR input: column indices do not fit int32")
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    if rp.ndim != 1 or (n is not None and rp.size != n + 1) or rp.size < 2:
+        raise DavidsonHipError(f"Hermitian CSR input: indptr must hold n + 1 = {'?' if n is None else n + 1} offsets, it holds {rp.size}")
+    nnz = int(rp[-1] - rp[0])
+    if nnz < 0 or ci.size < nnz or vv.size < nnz or vv.ndim != 1:
+        raise DavidsonHipError(f"Hermitian CSR input: indptr says {nnz} entries, indices / data hold {ci.size} / {vv.size}")
+    return rp, ci, vv
+
+
+def check_hermitian(indptr, indices, data, n, base=0, lower=False):
+    """Everything davh_set_operator_csr validates, checked in Python (ValueError) - for the Fortran doors, which stop the process on an
+    engine error.  Returns the arrays as hermitian_arrays does."""
+    try:
+        rp, ci, vv = hermitian_arrays(indptr, indices, data, n)
+    except DavidsonHipError as exc:
+        raise ValueError(str(exc)) from None
+    if base not in (0, 1):
+        raise ValueError("Hermitian CSR input: index base must be 0 or 1")
+    if rp[0] != base:
+        raise ValueError(f"Hermitian CSR input: indptr[0] = {rp[0]} must equal the index base {base}")
+    if np.any(np.diff(rp) < 0):
+        raise ValueError(f"Hermitian CSR input: indptr decreases at row {int(np.argmax(np.diff(rp) < 0)) + base}")
+    nnz = int(rp[-1] - base)
+    cols = ci[:nnz].astype(np.int64) - base
+    if nnz and (cols.min() < 0 or cols.max() >= n):
+        raise ValueError(f"Hermitian CSR input: column index out of range [{base}, {n + base})")
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(rp))
+    if lower and np.any(cols > rows):
+        p = int(np.argmax(cols > rows))
+        raise ValueError(f"Hermitian CSR input: entry ({rows[p] + base}, {cols[p] + base}) lies above the diagonal with lower=True")
+    bad = (cols == rows) & ~(vv[:nnz].imag == 0.0)
+    if bad.any():
+        p = int(np.argmax(bad))
+        raise ValueError(f"Hermitian CSR input: diagonal entry {p + base} (row {rows[p] + base}) has the imaginary part "
+                         f"{float(vv[p].imag)!r}: the diagonal of a Hermitian matrix is real")
+    return rp, ci, vv
+
+
+def _device_hermitian_tensors(row_ptr, col_idx, vals, n, device):
+    """The checks of a complex CSR matrix of order n in device tensors before any library call: int32 / int64 indices and complex128
+    values (TypeError, never converted), contiguous tensors on cuda:`device`, n + 1 offsets (ValueError).  Returns (row_ptr_bits,
+    col_bits, nnz)."""
+    import torch
+    args = (("row_ptr", row_ptr, (torch.int32, torch.int64)), ("col_idx", col_idx, (torch.int32, torch.int64)),
+            ("vals", vals, (torch.complex128,)))
+    for name, t, kinds in args:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"device Hermitian CSR input: {name} must be a torch tensor, not {type(t).__name__}")
+        if t.dtype not in kinds:
+            raise TypeError(f"device Hermitian CSR input: {name} has dtype {t.dtype}, expected " + " or ".join(str(k) for k in kinds))
+    for name, t, _ in args:
+        if t.layout != torch.strided or not t.is_contiguous() or t.dim() != 1:
+            raise ValueError(f"device Hermitian CSR input: {name} must be a contiguous one-dimensional tensor")
+    for name, t, _ in args:
+        if t.device.type != "cuda" or t.device.index != device:
+            raise ValueError(f"device Hermitian CSR input: {name} lies on {t.device}, the engine on cuda:{device}")
+    if row_ptr.numel() != n + 1:
+        raise ValueError(f"device Hermitian CSR input: row_ptr must hold n + 1 = {n + 1} offsets, it holds {row_ptr.numel()}")
+    nnz = int(row_ptr[-1]) - int(row_ptr[0])          # two values read back: the kernels must not read past the tensors
+    if col_idx.numel() < nnz or vals.numel() < nnz:
+        raise ValueError(f"device Hermitian CSR input: row_ptr says {nnz} entries, col_idx / vals hold {col_idx.numel()} / {vals.numel()}")
+    return (64 if row_ptr.dtype == torch.int64 else 32), (64 if col_idx.dtype == torch.int64 else 32), nnz
+
+
 def is_torch_coo(t):
     """True for a torch tensor in the sparse COO layout (torch itself is imported only when the object comes from it)"""
     if not type(t).__module__.startswith("torch"):
@@ -390,14 +474,16 @@ def _device_bsr_tensors(row_ptr, col_idx, vals, n, device):
     return b, (64 if row_ptr.dtype == torch.int64 else 32), (64 if col_idx.dtype == torch.int64 else 32), nnzb
 
 
-def update_values_array(vals, count, device=None, what="update_operator_values"):
+def update_values_array(vals, count, device=None, what="update_operator_values", pairs=False):
     """The checks of new values for a kept pattern before any library call: float64 (TypeError, never converted), contiguous, and - where
-    `count` (the values the set call saw) is known - exactly that many (ValueError); BSR blocks as (nnzb, b, b) or flat.  Returns
-    (flat numpy array, None) for host data (numpy, or a torch tensor on the CPU) or (None, torch tensor) for a tensor on cuda:`device`."""
+    `count` (the values the set call saw) is known - exactly that many (ValueError); BSR blocks as (nnzb, b, b) or flat.  pairs: the
+    operator is a Hermitian one (set_operator_csr_hermitian): complex128 instead, one value per entry; a real operator takes no
+    complex values and a Hermitian one no real ones (TypeError).  Returns (flat numpy array, None) for host data (numpy, or a torch
+    tensor on the CPU) or (None, torch tensor) for a tensor on cuda:`device`."""
     if type(vals).__module__.startswith("torch"):
         import torch
-        if vals.dtype != torch.float64:
-            raise TypeError(f"{what}: vals has dtype {vals.dtype}, expected torch.float64")
+        if vals.dtype != (torch.complex128 if pairs else torch.float64):
+            raise TypeError(f"{what}: vals has dtype {vals.dtype}, expected " + ("torch.complex128" if pairs else "torch.float64"))
         if vals.layout != torch.strided or not vals.is_contiguous():
             raise ValueError(f"{what}: vals must be a contiguous tensor")
         if count is not None and vals.numel() != count:
@@ -408,8 +494,8 @@ def update_values_array(vals, count, device=None, what="update_operator_values")
             raise ValueError(f"{what}: vals lies on {vals.device}, the engine on cuda:{device}")
         return None, vals
     a = np.asarray(vals)
-    if a.dtype != np.float64:
-        raise TypeError(f"{what}: vals has dtype {a.dtype}, expected float64")
+    if a.dtype != (np.complex128 if pairs else np.float64):
+        raise TypeError(f"{what}: vals has dtype {a.dtype}, expected " + ("complex128" if pairs else "float64"))
     if count is not None and a.size != count:
         raise ValueError(f"{what}: the set call saw {count} values, vals holds {a.size}")
     return np.ascontiguousarray(a).reshape(-1), None
@@ -696,10 +782,47 @@ class CEngine:
                                                     vals.data_ptr() or None, base, CSR_LOWER if lower else CSR_FULL, layout))
         self._saw_values(which, nnzb * b * b)
 
-    def _saw_values(self, which, count):
-        """the number of values the sparse set call of operator `which` saw (None: unknown - a refused call, or one not made here)"""
+    def set_operator_csr_hermitian(self, which, indptr, indices=None, data=None, base=0, lower=False):
+        """davh_set_operator_csr: a complex Hermitian matrix of order n / 2 in CSR form on this engine of the real order n, through its
+        real form - every entry a + ib the block [[a, -b], [b, a]] of a BSR operator with block size 2 (include/davidson_hip_herm.h).
+        Three arrays with data complex128, a scipy csr_matrix of complex dtype or a complex torch.sparse_csr_tensor (one on the GPU goes
+        to set_operator_csr_hermitian_dev); the complex values are read where they lie.  lower=True: only the entries with column <= row
+        are given; the strict lower ones are mirrored as conjugates.  The engine validates the input (DavidsonHipError; a diagonal entry
+        with an imaginary part is refused) and leaves the operator unset when it refuses it.  After keep_value_map,
+        update_operator_values takes complex128 values in the order of this call."""
+        if is_torch_csr(indptr) and indptr.device.type != "cpu":
+            return self.set_operator_csr_hermitian_dev(which, *torch_csr_parts(indptr), base=base, lower=lower)
+        rp, ci, vv = hermitian_arrays(indptr, indices, data, self.n // 2 if self.n % 2 == 0 else None)
+        ci_p = ci.ctypes.data_as(C.POINTER(C.c_int32)) if ci.size else (C.c_int32 * 1)()
+        vv_p = vv.ctypes.data_as(C.c_void_p) if vv.size else (C.c_double * 2)()
+        self._saw_values(which, None)
+        self._chk(self.lib.davh_set_operator_csr(self.h, which, rp.ctypes.data_as(C.POINTER(C.c_int64)), ci_p, vv_p, base,
+                                                 CSR_LOWER if lower else CSR_FULL))
+        self._saw_values(which, int(rp[-1] - rp[0]), pairs=True)
+
+    def set_operator_csr_hermitian_dev(self, which, row_ptr, col_idx, vals, base=0, lower=False):
+        """davh_set_operator_csr_dev: the matrix of set_operator_csr_hermitian as torch tensors on the engine's device, built on the
+        GPU - row_ptr (n / 2 + 1) and col_idx int32 or int64, vals complex128, all contiguous.  Other dtypes are a TypeError (never
+        converted).  Torch's current stream on the device is synchronised first.  The engine's refusal is a DavidsonHipError; the
+        operator is then unset."""
+        if self.n % 2:
+            raise DavidsonHipError(f"set_operator_csr_hermitian_dev: the engine's order {self.n} is odd; a Hermitian operator of order "
+                                   "n / 2 needs an engine of the even real order n")
+        rpb, cib, nnz = _device_hermitian_tensors(row_ptr, col_idx, vals, self.n // 2, self.device)
+        import torch
+        torch.cuda.current_stream(row_ptr.device).synchronize()
+        self._saw_values(which, None)
+        self._chk(self.lib.davh_set_operator_csr_dev(self.h, which, row_ptr.data_ptr(), rpb, col_idx.data_ptr() or None, cib,
+                                                     vals.data_ptr() or None, base, CSR_LOWER if lower else CSR_FULL))
+        self._saw_values(which, nnz, pairs=True)
+
+    def _saw_values(self, which, count, pairs=False):
+        """the number of values the sparse set call of operator `which` saw (None: unknown - a refused call, or one not made here);
+        pairs: they are complex (re, im) pairs (set_operator_csr_hermitian)"""
         self._value_counts = getattr(self, "_value_counts", {})
         self._value_counts[which] = count
+        self._value_pairs = getattr(self, "_value_pairs", {})
+        self._value_pairs[which] = pairs
 
     def keep_value_map(self, which, on=True):
         """dav_keep_value_map: a sticky switch per operator; the NEXT sparse set call of `which` also keeps where every stored value came
@@ -711,16 +834,18 @@ class CEngine:
         """dav_update_operator_values / dav_update_operator_values_dev: new values on the kept pattern of a CSR or BSR operator set after
         keep_value_map(which) - `vals` as long and in the order (BSR: block layout; (nnzb, b, b) or flat) of the vals of that set call.
         A numpy array (or a torch tensor on the CPU) goes through the host entry; a torch tensor on the engine's device through the
-        device entry, after torch's current stream on the device has been synchronised.  float64 only (TypeError, never converted); a
+        device entry, after torch's current stream on the device has been synchronised.  float64 only - complex128 only for an operator
+        set by set_operator_csr_hermitian, one value per entry - (TypeError, never converted); a
         length other than what the set call saw is a ValueError before the engine is called.  The engine's refusal - no value map, not
         a sparse operator - is a DavidsonHipError, and the operator keeps its old values."""
-        host, dev = update_values_array(vals, getattr(self, "_value_counts", {}).get(which), self.device)
+        host, dev = update_values_array(vals, getattr(self, "_value_counts", {}).get(which), self.device,
+                                        pairs=getattr(self, "_value_pairs", {}).get(which, False))
         if dev is not None:
             import torch
             torch.cuda.current_stream(dev.device).synchronize()
             self._chk(self.lib.dav_update_operator_values_dev(self.h, which, dev.data_ptr() or None))
         else:
-            self._chk(self.lib.dav_update_operator_values(self.h, which, _dp(host) if host.size else (C.c_double * 1)()))
+            self._chk(self.lib.dav_update_operator_values(self.h, which, host.ctypes.data_as(C.c_void_p) if host.size else (C.c_double * 2)()))
 
     def get_diagonal(self, which):
         d = np.zeros(self.n)

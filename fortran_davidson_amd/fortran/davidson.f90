@@ -742,6 +742,50 @@ contains
 end module davidson_csr
 
 
+module davidson_zcsr
+  use numeric_kinds, only: dp
+  use davidson_device
+  use davidson_hermitian
+  implicit none
+  private
+  public :: generalized_eigensolver_hermitian
+
+contains
+
+  !> Hermitian front-end: the argument list of the sparse specific with zcsr_matrix operators (module davidson_hermitian) and complex
+  !> eigenvectors (n, lowest).  The engine is created with the real order 2 n and solves for 2 * lowest real pairs - every eigenvalue of
+  !> the real form is double - from which hermitian_eigenpairs takes the complex ones.  max_dim_sub counts real columns (default: that
+  !> of 2 * lowest pairs); iters is the count of the real loop.
+  subroutine generalized_eigensolver_hermitian(matrix, eigenvalues, eigenvectors, lowest, method, max_iterations, &
+       tolerance, iters, max_dim_sub, second_matrix)
+    integer, intent(in) :: lowest
+    type(zcsr_matrix), intent(in) :: matrix
+    type(zcsr_matrix), intent(in), optional :: second_matrix
+    real(dp), dimension(lowest), intent(out) :: eigenvalues
+    complex(dp), dimension(:, :), intent(out) :: eigenvectors
+    character(len=*), intent(in) :: method
+    integer, intent(in) :: max_iterations
+    real(dp), intent(in) :: tolerance
+    integer, intent(out) :: iters
+    integer, intent(in), optional :: max_dim_sub
+
+    type(davidson_engine) :: eng
+    real(dp), allocatable :: theta(:), v(:, :)
+    integer :: max_dim
+
+    max_dim = default_max_dim(2 * lowest, max_dim_sub)
+    allocate(theta(2 * lowest), v(2 * matrix%n, 2 * lowest))
+    call engine_create(eng, 2 * matrix%n, 2 * lowest, max_dim, present(second_matrix), env_device())
+    call engine_set_hermitian(eng, 1, matrix)
+    if (present(second_matrix)) call engine_set_hermitian(eng, 2, second_matrix)
+    call device_solve_impl(eng, theta, v, 2 * lowest, method, max_iterations, tolerance, iters, max_dim)
+    call engine_destroy(eng)
+    call hermitian_eigenpairs(theta, v, lowest, eigenvalues, eigenvectors, second_matrix)
+  end subroutine generalized_eigensolver_hermitian
+
+end module davidson_zcsr
+
+
 module davidson
   use numeric_kinds, only: dp
   use davidson_dense, only: generalized_eigensolver_dense, generalized_eigensolver_dense_guess
@@ -749,6 +793,8 @@ module davidson
   use davidson_device, only: generalized_eigensolver_device, generalized_eigensolver_device_guess, davidson_free_buffers, engine_set_initial_vectors, &
        engine_set_initial_vectors_device, engine_keep_result_as_guess
   use davidson_sparse, only: csr_matrix, bsr_matrix, coo_matrix
+  use davidson_hermitian, only: zcsr_matrix
+  use davidson_zcsr, only: generalized_eigensolver_hermitian
   use davidson_csr, only: generalized_eigensolver_coo, generalized_eigensolver_coo_precond_coo, generalized_eigensolver_coo_precond_csr, &
        generalized_eigensolver_coo_precond_bsr
   use davidson_csr, only: generalized_eigensolver_sparse, generalized_eigensolver_bsr, generalized_eigensolver_sparse_guess, &
@@ -756,11 +802,12 @@ module davidson
        generalized_eigensolver_bsr_precond_csr, generalized_eigensolver_bsr_precond_bsr
   implicit none
   private
-  public :: generalized_eigensolver, davidson_free_buffers, csr_matrix, bsr_matrix, coo_matrix, engine_set_initial_vectors, &
+  public :: generalized_eigensolver, davidson_free_buffers, csr_matrix, bsr_matrix, coo_matrix, zcsr_matrix, engine_set_initial_vectors, &
        engine_set_initial_vectors_device, engine_keep_result_as_guess
 
   !> Generic of the reference (src/davidson.f90:601-625), resolved by the first argument: a matrix,
-  !> a block-apply procedure, (new) a device-resident `davidson_engine`, or (new) a sparse `csr_matrix` / `bsr_matrix` / `coo_matrix`.
+  !> a block-apply procedure, (new) a device-resident `davidson_engine`, or (new) a sparse `csr_matrix` / `bsr_matrix` / `coo_matrix`, or a complex Hermitian
+  !> `zcsr_matrix` (complex eigenvectors).
   interface generalized_eigensolver
      procedure generalized_eigensolver_dense
      procedure generalized_eigensolver_free
@@ -780,6 +827,7 @@ module davidson
      procedure generalized_eigensolver_coo_precond_csr
      procedure generalized_eigensolver_coo_precond_bsr
      procedure generalized_eigensolver_bsr_precond_bsr
+     procedure generalized_eigensolver_hermitian
   end interface generalized_eigensolver
 
 end module davidson

@@ -10,7 +10,8 @@ module davidson_c_api
   use davidson_free, only: free_matmul
   use davidson_sparse, only: csr_matrix, bsr_matrix, engine_set_sparse, engine_set_sparse_device, engine_set_block_sparse_device, &
        coo_matrix, engine_set_coo_device, engine_keep_value_map, engine_update_sparse_values, engine_update_sparse_values_device
-  use davidson_hip_c, only: DAV_CSR_LOWER, DAV_CSR_DIAGONALS, DAV_BSR_ROW_MAJOR, DAV_BSR_COL_MAJOR, dav_set_operator_bsr_dev
+  use davidson_hermitian, only: engine_set_hermitian_device
+  use davidson_hip_c, only: DAV_CSR_LOWER, DAV_CSR_DIAGONALS, DAV_BSR_ROW_MAJOR, DAV_BSR_COL_MAJOR, dav_set_operator_bsr_dev, davh_set_operator_csr, check_dav
   use lapack_wrapper
   use array_utils
   implicit none
@@ -383,6 +384,41 @@ contains
          row_bits=int(row_bits), col_bits=int(col_bits), stat=st, diagonals=iand(lower, DAV_CSR_DIAGONALS) /= 0)
     stat = int(st, c_int)
   end function fdx_engine_set_coo_device
+
+  !> engine_set_hermitian for C arrays of a complex CSR matrix of order n (the engine's is 2 n) numbered from `base`; vals: 2 nnz
+  !> doubles, (re, im) pairs.  The arrays go to davh_set_operator_csr as they are - no zcsr_matrix is built, the values are read where
+  !> they lie, and the engine's messages count entries and rows from `base`.
+  subroutine fdh_engine_set_hermitian(p, which, n, rp, col, vals, base, lower) bind(C, name="fdh_engine_set_hermitian")
+    type(c_ptr), value :: p
+    integer(c_int), value :: which, n, base, lower
+    integer(c_int64_t), intent(in) :: rp(n + 1)
+    integer(c_int32_t), intent(in) :: col(*)
+    real(c_double), intent(in) :: vals(*)
+    type(davidson_engine), pointer :: eng
+    call c_f_pointer(p, eng)
+    if (2 * n /= eng%n) then
+       print *, "fdh_engine_set_hermitian: the matrix must be of order ", eng%n / 2
+       error stop
+    end if
+    call check_dav(davh_set_operator_csr(eng%h, which - 1_c_int, rp, col, vals, base, iand(lower, DAV_CSR_LOWER)), &
+         "davh_set_operator_csr")
+    if (which == 1) eng%free_semantics = .false.
+  end subroutine fdh_engine_set_hermitian
+
+  !> engine_set_hermitian_device(eng, which, n, ...) with device arrays: returns the engine's status, as fd_engine_set_sparse_device does
+  function fdh_engine_set_hermitian_device(p, which, n, rp, rp_bits, col, col_bits, vals, base, lower) result(stat) &
+       bind(C, name="fdh_engine_set_hermitian_device")
+    type(c_ptr), value :: p
+    integer(c_int), value :: which, n, rp_bits, col_bits, base, lower
+    type(c_ptr), value :: rp, col, vals
+    integer(c_int) :: stat
+    type(davidson_engine), pointer :: eng
+    integer :: st
+    call c_f_pointer(p, eng)
+    call engine_set_hermitian_device(eng, int(which), int(n), rp, col, vals, base=int(base), lower=iand(lower, DAV_CSR_LOWER) /= 0, &
+         row_ptr_bits=int(rp_bits), col_bits=int(col_bits), stat=st)
+    stat = int(st, c_int)
+  end function fdh_engine_set_hermitian_device
 
   !> engine_set_sparse(eng, which, a) with a bsr_matrix from C arrays numbered from `base` (values in Fortran order, as bsr_from_c)
   subroutine fd_engine_set_block_sparse(p, which, n, b, rp, col, vals, base, lower) bind(C, name="fd_engine_set_block_sparse")

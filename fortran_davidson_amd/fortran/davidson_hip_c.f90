@@ -215,6 +215,32 @@ module davidson_hip_c
        integer(c_int), value :: index_base, triangle
        integer(c_int) :: ierr
      end function
+     !> a complex Hermitian CSR matrix of order n / 2 through its real form (include/davidson_hip_herm.h): vals as (re, im) pairs
+     function davh_set_operator_csr(h, which, row_ptr, col_idx, vals, index_base, triangle) bind(C, name="davh_set_operator_csr") &
+          result(ierr)
+       import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+       type(c_ptr), value :: h
+       integer(c_int), value :: which
+       integer(c_int64_t), intent(in) :: row_ptr(*)
+       integer(c_int32_t), intent(in) :: col_idx(*)
+       real(c_double), intent(in) :: vals(*)          ! 2 nnz doubles: the memory of a complex(c_double_complex) array
+       integer(c_int), value :: index_base, triangle
+       integer(c_int) :: ierr
+     end function
+     !> the same matrix from device arrays of the engine's device, built on the GPU (row_ptr_bits / col_bits: 32 or 64)
+     function davh_set_operator_csr_dev(h, which, row_ptr, row_ptr_bits, col_idx, col_bits, vals, index_base, triangle) &
+          bind(C, name="davh_set_operator_csr_dev") result(ierr)
+       import :: c_ptr, c_int
+       type(c_ptr), value :: h
+       integer(c_int), value :: which
+       type(c_ptr), value :: row_ptr
+       integer(c_int), value :: row_ptr_bits
+       type(c_ptr), value :: col_idx
+       integer(c_int), value :: col_bits
+       type(c_ptr), value :: vals
+       integer(c_int), value :: index_base, triangle
+       integer(c_int) :: ierr
+     end function
      !> a BSR matrix from device arrays of the engine's device, built on the GPU (row_ptr_bits / col_bits: 32 or 64)
      function dav_set_operator_bsr_dev(h, which, block_size, block_row_ptr, row_ptr_bits, block_col_idx, col_bits, vals, index_base, &
           triangle, block_layout) bind(C, name="dav_set_operator_bsr_dev") result(ierr)

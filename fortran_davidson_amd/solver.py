@@ -16,8 +16,8 @@ import ctypes as C
 import numpy as np
 
 from ._lib import fortran_lib, hip_lib
-from .engine_c import (CEngine, DavidsonHipError, _device_bsr_tensors, _device_coo_tensors, _device_csr_tensors, _dp, _f, _optional, check_bsr,
-                       check_coo, check_csr, coo_triples, csr_flag_word, device_bsr_tensors, device_csr_tensors, guess_array, is_torch_bsr,
+from .engine_c import (CEngine, DavidsonHipError, _device_bsr_tensors, _device_coo_tensors, _device_csr_tensors, _device_hermitian_tensors,
+                       _dp, _f, _optional, check_bsr, check_coo, check_csr, check_hermitian, coo_triples, csr_flag_word, device_bsr_tensors, device_csr_tensors, guess_array, is_torch_bsr,
                        is_torch_coo, is_torch_csr, torch_bsr_parts, torch_csr_parts, update_values_array)
 
 # The operator slots of DavidsonEngine, numbered as the Fortran routines number them.  OP_M is the caller's preconditioner - an
@@ -250,6 +250,93 @@ def generalized_eigensolver_coo(rows, cols, vals, n, lowest, method, max_iterati
         if second is not None:
             eng.set_coo(2, *(second if isinstance(second, tuple) else (second,)), lower=lower, diagonals=diagonals)
         return eng.solve(method, max_iterations, tolerance, initial_vectors=initial_vectors)
+
+
+def _hermitian_parts(a):
+    """the three parts of a complex CSR operator given as a tuple (indptr, indices, data), an object with .indptr / .indices / .data (a
+    scipy csr_matrix) or a torch.sparse_csr_tensor (on the CPU as numpy arrays, on a GPU as tensors), as they stand"""
+    if is_torch_csr(a):
+        return torch_csr_parts(a)
+    if not isinstance(a, tuple):
+        return a.indptr, a.indices, a.data
+    return a
+
+
+def hermitian_eigenpairs(theta, v, lowest, second=None, lower=False):
+    """The `lowest` complex eigenpairs of H x = lambda S x from the 2 * lowest real Ritz pairs of its real form (Fortran:
+    hermitian_eigenpairs): theta (2 * lowest,) ascending, v (2 n, 2 * lowest) real with real and imaginary parts interleaved,
+    S-orthonormal in the real form.  second: S as a complex CSR matrix - a tuple (indptr, indices, data) or a scipy csr_matrix, 0-based,
+    with lower=True only its entries with column <= row - or None for S = I.  Returns (eigenvalues (lowest,) ascending, eigenvectors
+    complex (n, lowest) with X^H S X = I).
+    The real form has every eigenvalue twice and the solver leaves an arbitrary rotation inside each pair, so Z = v[0::2] + i v[1::2]
+    has the complex rank `lowest` only.  G = Z^H S Z equals I + iK with K real antisymmetric, its eigenvalues come in pairs 1 +- s, and
+    the `lowest` largest are >= 1 even where the cut goes through a degenerate cluster: their vectors U and C = U diag(g^-1/2) give an
+    S-orthonormal basis Z C of the space.  T = C^H (G diag(theta)) C, hermitised, = W Lambda W^H; X = Z C W.  O(n lowest^2) on the host."""
+    theta = np.asarray(theta, dtype=np.float64)[:2 * lowest]
+    v = np.asarray(v, dtype=np.float64)[:, :2 * lowest]
+    if theta.size != 2 * lowest or v.ndim != 2 or v.shape[0] % 2 or v.shape[1] != 2 * lowest:
+        raise ValueError(f"hermitian_eigenpairs: theta (2 * lowest,) and v (2 n, 2 * lowest) are needed, not {theta.shape} and {v.shape}")
+    z = v[0::2] + 1j * v[1::2]
+    if second is None:
+        sz = z
+    else:
+        rp, ci, vv = check_hermitian(*_hermitian_parts(second), z.shape[0], 0, lower)
+        rows = np.repeat(np.arange(z.shape[0]), np.diff(rp))
+        sz = np.zeros_like(z)
+        np.add.at(sz, rows, vv[:, None] * z[ci])
+        if lower:
+            off = ci != rows
+            np.add.at(sz, ci[off], np.conj(vv[off])[:, None] * z[rows[off]])
+    g = z.conj().T @ sz
+    g = 0.5 * (g + g.conj().T)
+    gw, u = np.linalg.eigh(g)
+    c = u[:, lowest:] / np.sqrt(gw[lowest:])
+    t = c.conj().T @ ((g * theta[None, :]) @ c)
+    lam, w = np.linalg.eigh(0.5 * (t + t.conj().T))
+    return lam, z @ (c @ w)
+
+
+def _hermitian_guess(x, n, g_max):
+    """initial_vectors= of a Hermitian solve: complex (n, g) -> real (2 n, 2 g): the g interleaved columns and their J-partners (the
+    interleaved columns of i x) - one complex vector is two real ones"""
+    x = np.asarray(x.cpu().numpy() if type(x).__module__.startswith("torch") else x)
+    if x.ndim == 1:
+        x = x.reshape(-1, 1)
+    if x.dtype != np.complex128:
+        raise TypeError(f"initial_vectors: x has dtype {x.dtype}, expected complex128")
+    if x.ndim != 2 or x.shape[0] != n or x.shape[1] < 1:
+        raise ValueError(f"initial_vectors: x must have shape ({n}, ncols), it has {x.shape}")
+    x = x[:, :g_max]
+    out = np.zeros((2 * n, 2 * x.shape[1]), order="F")
+    out[0::2, :x.shape[1]], out[1::2, :x.shape[1]] = x.real, x.imag
+    out[0::2, x.shape[1]:], out[1::2, x.shape[1]:] = -x.imag, x.real
+    return out
+
+
+def generalized_eigensolver_hermitian(indptr, indices, data, lowest, method, max_iterations, tolerance, max_dim_sub=None, second=None,
+                                      lower=False, n=None, initial_vectors=None):
+    """`call generalized_eigensolver(a_zcsr, eigenvalues, eigenvectors, lowest, method, max_iterations, tolerance, iters [, max_dim_sub]
+    [, b_zcsr])` (the zcsr_matrix specific of module davidson): the lowest eigenpairs of a complex Hermitian matrix A in CSR form,
+    0-based - three arrays with data complex128, or `indptr` a scipy csr_matrix of complex dtype or a complex torch.sparse_csr_tensor
+    and indices = data = None.  `second`: S of a generalized problem the same way.  A tensor on the GPU is built there.  The solve runs
+    on the real form of order 2 n (DavidsonEngine.set_hermitian) for 2 * lowest real pairs, from which hermitian_eigenpairs takes the
+    complex ones; max_dim_sub counts real columns (default 10 * 2 * lowest), iters is the real loop's count.  lower=True: only the
+    entries with column <= row are given, for A and S.  initial_vectors: complex (n, g), staged as its g interleaved columns and their
+    J-partners.  Returns (eigenvalues (lowest,), eigenvectors complex (n, lowest), iters)."""
+    a = indptr if indices is None and data is None else (indptr, indices, data)
+    if n is None:
+        n = int(a.shape[0]) if hasattr(a, "shape") else len(a[0]) - 1
+    on_gpu = [m for m in (a, second) if is_torch_csr(m) and m.device.type != "cpu"]
+    with DavidsonEngine(2 * n, 2 * lowest, max_dim_sub, gev=second is not None, device=on_gpu[0].device.index if on_gpu else 0) as eng:
+        eng.set_hermitian(1, a, lower=lower)
+        if second is not None:
+            eng.set_hermitian(2, second, lower=lower)
+        guess = None if initial_vectors is None else _hermitian_guess(initial_vectors, n, lowest)
+        theta, v, iters = eng.solve(method, max_iterations, tolerance, initial_vectors=guess)
+    if second is not None and is_torch_csr(second) and second.device.type != "cpu":
+        second = second.cpu()
+    lam, x = hermitian_eigenpairs(theta, v, lowest, second, lower)
+    return lam, x, iters
 
 
 def _bsr_input(a, n, lower=False):
@@ -501,19 +588,58 @@ class DavidsonEngine:
         if keep_map:
             self._kept[which] = {"count": nnzb * b * b, "b": b, "fortran_blocks": False}
 
+    def set_hermitian(self, which, a, lower=False, keep_map=False):
+        """Operator A, B or the preconditioner M (which=1, 2, 3) of this engine of the real order 2 n as a complex Hermitian matrix of
+        order n in CSR form, 0-based, through its real form (Fortran: engine_set_hermitian): a tuple (indptr, indices, data) with data
+        complex128, a scipy csr_matrix of complex dtype or a complex torch.sparse_csr_tensor - one on the engine's GPU is built there
+        (Fortran: engine_set_hermitian_device; a refused matrix raises DavidsonHipError and leaves the operator unset).  The operator
+        is, bit for bit, the BSR operator of the blocks [[re, -im], [im, re]] with block size 2, and the methods see it as one.
+        lower=True: only the entries with column <= row are given and the strict lower ones are mirrored as conjugates.
+        keep_map=True: update_values then takes complex128 values in the order of this call."""
+        if self.n % 2:
+            raise ValueError(f"DavidsonEngine.set_hermitian: the engine's order {self.n} is odd; a Hermitian operator of order n needs an "
+                             "engine of the real order 2 n")
+        nc = self.n // 2
+        parts = _hermitian_parts(a)
+        if type(parts[2]).__module__.startswith("torch"):
+            rpb, cib, nnz = _device_hermitian_tensors(*parts, nc, self.device)
+            if keep_map:          # the positions of the diagonal entries, for the check update_values makes of host data
+                import torch
+                rows = torch.repeat_interleave(torch.arange(nc, device=parts[0].device), torch.diff(parts[0]).long())
+                diag_pos = torch.nonzero(rows == parts[1][:nnz].long() - int(parts[0][0])).reshape(-1).cpu().numpy()
+            self._keep_map(which, keep_map)
+            import torch
+            torch.cuda.current_stream(parts[0].device).synchronize()
+            st = self.lib.fdh_engine_set_hermitian_device(self.p, which, nc, parts[0].data_ptr(), rpb, parts[1].data_ptr() or None, cib,
+                                                          parts[2].data_ptr() or None, 0, int(lower))
+            if st != 0:
+                raise DavidsonHipError(hip_lib().dav_last_error().decode())
+        else:
+            rp, ci, vv = check_hermitian(*parts, nc, 0, lower)
+            nnz = int(rp[-1] - rp[0])
+            diag_pos = np.flatnonzero(ci[:nnz] == np.repeat(np.arange(nc), np.diff(rp)))
+            self._keep_map(which, keep_map)
+            self.lib.fdh_engine_set_hermitian(self.p, which, nc, _i64(rp), _i32(ci), vv.ctypes.data_as(C.c_void_p) if nnz else (C.c_double * 2)(),
+                                              0, int(lower))
+        self._note_blocks(which, 2, sparse=True)
+        if keep_map:
+            self._kept[which] = {"count": nnz, "b": 2, "fortran_blocks": False, "pairs": True, "diag_pos": diag_pos}
+
     def update_values(self, which, data):
         """New values of operator A (which=1), B (which=2) or M (which=3) on its kept pattern (Fortran: engine_update_sparse_values /
         engine_update_sparse_values_device): the operator was set by set_sparse / set_block_sparse with keep_map=True, and `data` is the
         data of that call with new numbers - for BSR (nnzb, b, b) row-major blocks, or the same flat.  A numpy array (or a CPU tensor)
         goes through the host entry, a torch tensor on the engine's GPU through the device entry; either works whichever way the
-        operator was set.  float64 only (TypeError); a wrong length is a ValueError, an operator set without keep_map=True a
+        operator was set.  float64 only - for an operator set by set_hermitian complex128 only, one value per entry, the diagonal entries
+        real (host data: ValueError; device data: the engine's DavidsonHipError; both count entries and rows from 0) - (TypeError); a wrong length is a ValueError, an operator set without keep_map=True a
         DavidsonHipError - all before the engine is called, and the operator keeps its values.  Diagonal, applies and solves then equal
         bit for bit those of a fresh set call with `data`."""
         kept = getattr(self, "_kept", {}).get(which)
         if kept is None:
             raise DavidsonHipError(f"update_values: operator {which} was not set with keep_map=True (dav_keep_value_map): it keeps no "
                                    "value map")
-        host, dev = update_values_array(data, kept["count"], self.device, "update_values")
+        pairs = kept.get("pairs", False)
+        host, dev = update_values_array(data, kept["count"], self.device, "update_values", pairs=pairs)
         b = kept["b"]
         if dev is not None:
             import torch
@@ -526,6 +652,14 @@ class DavidsonEngine:
             return
         if kept["fortran_blocks"] and b > 1:
             host = np.ascontiguousarray(host.reshape(-1, b, b).transpose(0, 2, 1)).reshape(-1)
+        if pairs:          # complex128 values: the (re, im) pairs as they lie, 2 doubles each
+            # the engine's one refusal of values, made here: the Fortran door of host data stops the process on it
+            bad = kept["diag_pos"][~(host[kept["diag_pos"]].imag == 0.0)]
+            if bad.size:
+                raise ValueError(f"update_values: diagonal entry {int(bad[0])} has the imaginary part {float(host[bad[0]].imag)!r}: the "
+                                 "diagonal of a Hermitian matrix is real")
+            self.lib.fd_engine_update_values(self.p, which, host.ctypes.data_as(C.c_void_p) if host.size else (C.c_double * 2)(), 2 * host.size)
+            return
         self.lib.fd_engine_update_values(self.p, which, _dp(host) if host.size else (C.c_double * 1)(), host.size)
 
     def set_correction_policy(self, policy):
