@@ -170,6 +170,18 @@ HERM_FD = {
     "fdh_engine_set_hermitian_device": (i32, (ptr, i32, i32, ptr, i32, ptr, i32, ptr, i32, i32)),
 }
 
+# include/davidson_hip_precond.h: the preconditioner the engine builds from the stored operators (prefix davp_) and its doors (prefix
+# fdp_); tests/test_fsai_cpu.py compares both with the header and the Fortran sources
+PRECOND = {
+    "davp_build_fsai": (i32, (ptr, f64, i32)),
+    "davp_fsai_info": (i32, (ptr, ptr, ptr, ptr)),
+    "davp_fsai_get_factor": (i32, (ptr, i32, ptr, ptr, ptr)),
+}
+PRECOND_FD = {
+    "fdp_engine_build_fsai": (i32, (ptr, f64, i32)),
+    "fdp_engine_fsai_info": (None, (ptr, ptr, ptr, ptr)),
+}
+
 
 def apply(lib, table, optional=()):
     """Set restype and argtypes of every entry of `table` on `lib`.  An entry of `optional` that the library lacks is skipped; any

@@ -48,6 +48,7 @@ def hip_lib() -> C.CDLL:
         _abi.apply(lib, _abi.DAV, optional=_abi.TEST_BUILD_ONLY)       # raises before the library can be used without prototypes
         _abi.apply(lib, _abi.EXT)
         _abi.apply(lib, _abi.HERM)
+        _abi.apply(lib, _abi.PRECOND)
         _hip = lib
         runtimes = hip_runtimes_mapped()
         if len(runtimes) > 1:
@@ -83,5 +84,6 @@ def fortran_lib() -> C.CDLL:
         _abi.apply(lib, _abi.FD)
         _abi.apply(lib, _abi.EXT_FD)
         _abi.apply(lib, _abi.HERM_FD)
+        _abi.apply(lib, _abi.PRECOND_FD)
         _fortran = lib
     return _fortran

@@ -431,14 +431,14 @@ int apply_sym_set(E* e, int which, OpDesc& o, const SymSet& set, bool partial, b
 
 // Byte and flop model of one product of a sparse operator with k columns (include/davidson_hip.h: dav_stats): values and columns of the
 // entries (blocks of b x b; CSR: b = 1), the offsets, the gathered operand read and this rank's rows written.
-static void sparse_traffic(const E* e, const OpDesc& o, int k, double* bytes, double* flops) {
-  const double bb = (double)o.sp.b * o.sp.b, nnz = (double)o.sp.nnz;
-  if (o.kind == DAV_KIND_DIA) {          // k_dia.hip: the slots, the offsets, the operand, the rows written; flops = the useful work
-    *bytes = 8.0 * (double)o.sp.dia_nd * (double)e->nloc + 4.0 * (double)o.sp.dia_nd + 8.0 * (double)e->n * k + 8.0 * (double)e->nloc * k;
+static void sparse_traffic(const E* e, int kind, const SparseStore& sp, int k, double* bytes, double* flops) {
+  const double bb = (double)sp.b * sp.b, nnz = (double)sp.nnz;
+  if (kind == DAV_KIND_DIA) {          // k_dia.hip: the slots, the offsets, the operand, the rows written; flops = the useful work
+    *bytes = 8.0 * (double)sp.dia_nd * (double)e->nloc + 4.0 * (double)sp.dia_nd + 8.0 * (double)e->n * k + 8.0 * (double)e->nloc * k;
     *flops = 2.0 * nnz * k;
     return;
   }
-  *bytes = 8.0 * bb * nnz + 4.0 * nnz + 8.0 * (double)(o.sp.nrows + 1) + 8.0 * (double)e->n * k + 8.0 * (double)e->nloc * k;
+  *bytes = 8.0 * bb * nnz + 4.0 * nnz + 8.0 * (double)(sp.nrows + 1) + 8.0 * (double)e->n * k + 8.0 * (double)e->nloc * k;
   *flops = 2.0 * bb * nnz * k;
 }
 
@@ -481,13 +481,14 @@ static int apply_device(E* e, int which, OpDesc& o, const double* src, int k, do
 // and the chunk sums of the long rows.  Always fp64 (inner sweeps too: there is no fp32 copy of a sparse operator).
 // A CSR matrix stored by diagonals (DAV_KIND_DIA, k_dia.hip) takes the same steps with one launch and no work list.
 // epi (CSR, DIA): the step of the Chebyshev correction in the product's epilogue (k_spmm.hip, k_dia.hip), its columns those of src / dst.
-static int apply_sparse(E* e, int which, OpDesc& o, const double* src, int k, double* dst, bool timed, const ChebEpi* epi = nullptr) {
-  const SparseStore& s = o.sp;
+// The store s of kind `kind` is the operator's own (OpDesc::sp) or one of the two of a DAV_KIND_FSAI operator (apply_fsai below).
+static int apply_sparse(E* e, int which, int kind, const SparseStore& s, const double* src, int k, double* dst, bool timed,
+                        const ChebEpi* epi = nullptr) {
   for (int c = 0; c < k; c += 64) {
     const int kk = std::min(64, k - c), groups = (kk + 15) / 16, gp = groups == 3 ? 4 : groups;
     int slot = -1, kslot = -1;
     double bytes, flops;
-    sparse_traffic(e, o, kk, &bytes, &flops);
+    sparse_traffic(e, kind, s, kk, &bytes, &flops);
     if (epi) bytes += 8.0 * (double)e->nloc * kk * (epi->zprev ? 3 : 2);      // the epilogue reads z, r (and z_{k-1}) at the rows it writes
     if (timed) CHK(timed_begin(e, which == DAV_OP_A ? 0 : 2, bytes, &slot));
     CHK(pack_operand(e, src + (int64_t)c * e->ldp, kk, has_comm(e)));
@@ -499,16 +500,16 @@ static int apply_sparse(E* e, int which, OpDesc& o, const double* src, int k, do
       ep.z += (int64_t)c * ep.ld; ep.r += (int64_t)c * ep.ld; ep.pi += c;
       if (ep.zprev) ep.zprev += (int64_t)c * ep.ld;
     }
-    if (o.kind == DAV_KIND_DIA) {
+    if (kind == DAV_KIND_DIA) {
       if (epi) {
         launch_spmm_dia_cheb(e->stream, s.dia_off, s.dia_nd, s.dia_val, s.dia_ld, e->nloc, e->row0, e->n, e->xt, e->xt_group_stride, gp, kk, out, e->ldp, ep);
       } else {
         launch_spmm_dia(e->stream, s.dia_off, s.dia_nd, s.dia_val, s.dia_ld, e->nloc, e->row0, e->n, e->xt, e->xt_group_stride, gp, kk, out, e->ldp);
       }
-    } else if (o.kind == DAV_KIND_CSR && epi) {
+    } else if (kind == DAV_KIND_CSR && epi) {
       launch_spmm_csr_cheb(e->stream, s.items, s.nitems, s.rp, s.col, s.val, e->xt, e->xt_group_stride, gp, kk, s.part, out, e->ldp, ep);
       launch_spmm_csr_finish_cheb(e->stream, s.longs, s.nlong, s.part, kk, out, e->ldp, ep);
-    } else if (o.kind == DAV_KIND_CSR) {
+    } else if (kind == DAV_KIND_CSR) {
       launch_spmm_csr(e->stream, s.items, s.nitems, s.rp, s.col, s.val, e->xt, e->xt_group_stride, gp, kk, s.part, out, e->ldp);
       launch_spmm_csr_finish(e->stream, s.longs, s.nlong, s.part, kk, out, e->ldp);
     } else {
@@ -521,6 +522,27 @@ static int apply_sparse(E* e, int which, OpDesc& o, const double* src, int k, do
     count_apply(e, which, kk);
   }
   HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// The built preconditioner M = G^T G (DAV_KIND_FSAI; engine_fsai.hip): 64 columns at a time, the rows of G applied into
+// the block between the products and the rows of G^T from there into dst - each product the CSR steps above (pack, product, chunk sums,
+// zeroed padding rows), so the result equals, bit for bit, two applies of the two stores set as CSR operators.  The block (ldp x 64) is
+// allocated here, at the first apply, and not cleared: the first product writes every row of the columns the second one reads, the
+// padding rows included.
+static int apply_fsai(E* e, int which, OpDesc& o, const double* src, int k, double* dst, bool timed) {
+  if (!o.fsai_ws) {
+    if (pool_malloc(&o.fsai_ws, sizeof(double) * (size_t)e->ldp * 64) != hipSuccess) {
+      (void)hipGetLastError();
+      o.fsai_ws = nullptr;
+      return fail("dav_apply: device memory for the intermediate block of the FSAI preconditioner could not be allocated");
+    }
+  }
+  for (int c = 0; c < k; c += 64) {
+    const int kk = std::min(64, k - c);
+    CHK(apply_sparse(e, which, DAV_KIND_CSR, o.sp, src + (int64_t)c * e->ldp, kk, o.fsai_ws, timed));
+    CHK(apply_sparse(e, which, DAV_KIND_CSR, o.sp2, o.fsai_ws, kk, dst + (int64_t)c * e->ldp, timed));
+  }
   return 0;
 }
 
@@ -575,7 +597,8 @@ int apply_ptr(E* e, int which, const double* src, int k, double* dst, bool timed
   if (o.kind == DAV_KIND_IDENTITY) return apply_identity(e, src, k, dst);
   CHK(need_comm(e));
   if (o.kind == DAV_KIND_DEVICE) return apply_device(e, which, o, src, k, dst, timed);
-  if (o.kind == DAV_KIND_CSR || o.kind == DAV_KIND_BSR || o.kind == DAV_KIND_DIA) return apply_sparse(e, which, o, src, k, dst, timed);
+  if (o.kind == DAV_KIND_CSR || o.kind == DAV_KIND_BSR || o.kind == DAV_KIND_DIA) return apply_sparse(e, which, o.kind, o.sp, src, k, dst, timed);
+  if (o.kind == DAV_KIND_FSAI) return apply_fsai(e, which, o, src, k, dst, timed);
   if ((o.kind == DAV_KIND_DENSE || o.kind == DAV_KIND_HASHED || o.kind == DAV_KIND_HARNESS) && o.storage == 1)
     return apply_symmetric(e, which, o, src, k, dst, timed, inner);
   return apply_full_rows(e, which, o, src, k, dst, timed);
@@ -585,7 +608,7 @@ int apply_csr_cheb(E* e, const double* src, int k, double* dst, const ChebEpi& e
   OpDesc& o = e->op[DAV_OP_A];
   if (o.kind != DAV_KIND_CSR && o.kind != DAV_KIND_DIA) return fail("apply_csr_cheb: operator A is not a CSR operator");
   CHK(need_comm(e));
-  return apply_sparse(e, DAV_OP_A, o, src, k, dst, true, &epi);
+  return apply_sparse(e, DAV_OP_A, o.kind, o.sp, src, k, dst, true, &epi);
 }
 
 // W0 = Op * V0 for the unit columns V0 = e_idx of dav_init_basis over SEVERAL ranks of dealt-out symmetric tiles, without a sweep:
@@ -669,7 +692,7 @@ extern "C" int dav_bench_apply2(dav_handle_t e, int which, int k, int reps, doub
   *avg_ms = total / reps;
   *kernel_ms = ktotal / reps;
   if (e->op[which].kind == DAV_KIND_CSR || e->op[which].kind == DAV_KIND_BSR || e->op[which].kind == DAV_KIND_DIA) {
-    sparse_traffic(e, e->op[which], k, bytes, flops);
+    sparse_traffic(e, e->op[which].kind, e->op[which].sp, k, bytes, flops);
     e->st = saved;
     return 0;
   }

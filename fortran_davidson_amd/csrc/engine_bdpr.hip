@@ -4,15 +4,6 @@
 
 namespace {
 const char* slot_name(int which) { return which == DAV_OP_A ? "operator A" : "operator B"; }
-const char* kind_name(int kind) {
-  switch (kind) {
-    case DAV_KIND_NONE: return "not set";
-    case DAV_KIND_DENSE: return "a dense matrix";
-    case DAV_KIND_CSR: return "a CSR matrix";
-    case DAV_KIND_DIA: return "a CSR matrix stored by diagonals";
-    default: return "not a BSR matrix";
-  }
-}
 int refuse(int which, const std::string& why) { return fail(std::string("BDPR correction: ") + slot_name(which) + " " + why); }
 }  // namespace
 
@@ -21,12 +12,12 @@ int refuse(int which, const std::string& why) { return fail(std::string("BDPR co
 int bdpr_prepare(E* e) {
   const OpDesc& A = e->op[DAV_OP_A];
   if (A.kind != DAV_KIND_BSR)
-    return refuse(DAV_OP_A, std::string("is ") + kind_name(A.kind) + ": the block solves need the diagonal blocks of a BSR operator (dav_set_operator_bsr)");
+    return refuse(DAV_OP_A, std::string("is ") + kind_words(A.kind) + ": the block solves need the diagonal blocks of a BSR operator (dav_set_operator_bsr)");
   const int b = A.sp.b;
   if (e->gev) {
     const OpDesc& B = e->op[DAV_OP_B];
     if (B.kind != DAV_KIND_BSR)
-      return refuse(DAV_OP_B, std::string("is ") + kind_name(B.kind) + ": a generalized problem needs a BSR operator B of the block size of A (" +
+      return refuse(DAV_OP_B, std::string("is ") + kind_words(B.kind) + ": a generalized problem needs a BSR operator B of the block size of A (" +
                                   std::to_string(b) + ")");
     if (B.sp.b != b)
       return refuse(DAV_OP_B, "has block size " + std::to_string(B.sp.b) + ", operator A has " + std::to_string(b) + ": the block sizes must be equal");

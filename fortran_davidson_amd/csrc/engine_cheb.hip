@@ -6,16 +6,6 @@
 #include "engine_internal.h"
 
 namespace {
-const char* kind_name(int kind) {
-  switch (kind) {
-    case DAV_KIND_NONE: return "not set";
-    case DAV_KIND_DENSE: return "a dense matrix";
-    case DAV_KIND_HOST: return "a host callback";
-    case DAV_KIND_DEVICE: return "a device callback";
-    case DAV_KIND_IDENTITY: return "the identity";
-    default: return "a generated operator";
-  }
-}
 // the refusals of both methods; the prefix says which
 int refuse(int method, const std::string& why) { return fail((method == DAV_METHOD_LCHEB ? "LCHEB correction: " : "CHEB correction: ") + why); }
 int ws_cols(const E* e) { return e->cols_alloc / 2 + 8; }     // the width of a block of the GJD workspace
@@ -147,7 +137,7 @@ int cheb_prepare(E* e, const MethodSpec& method) {
   OpDesc& A = e->op[DAV_OP_A];
   if (kind == DAV_METHOD_CHEB) {
     if (A.kind != DAV_KIND_CSR && A.kind != DAV_KIND_BSR && A.kind != DAV_KIND_DIA)
-      return refuse(kind, std::string("operator A is ") + kind_name(A.kind) +
+      return refuse(kind, std::string("operator A is ") + kind_words(A.kind) +
                           ": the spectral bound is taken from the stored entries of a CSR or BSR operator (dav_set_operator_csr / dav_set_operator_bsr)");
   } else {
     if (A.kind == DAV_KIND_NONE) return refuse(kind, "operator A is not set");

@@ -200,7 +200,12 @@ struct OpDesc {
   // streamed rows of a dense one; released with the engine
   double* lbound = nullptr;
   bool lbound_valid = false;
-  SparseStore sp;            // DAV_KIND_CSR / DAV_KIND_BSR / DAV_KIND_DIA
+  SparseStore sp;            // DAV_KIND_CSR / DAV_KIND_BSR / DAV_KIND_DIA; DAV_KIND_FSAI: the rows of G
+  // DAV_KIND_FSAI (engine_fsai.hip): the rows of G^T as a second canonical CSR store, the block between the two products
+  // (ldp x 64, allocated at the first apply) and what davp_fsai_info reports; all released with the operator
+  SparseStore sp2;
+  double* fsai_ws = nullptr;
+  int64_t fsai_longest_row = 0, fsai_longest_col = 0;
 };
 
 struct SmallBuf {            // device small matrix + pinned staging
@@ -501,6 +506,8 @@ int refuse_slot_m(const char* name);     // the entries that serve A and B only:
 static inline bool has_precond(const E* e) { return e->op[DAV_OP_M].kind != DAV_KIND_NONE; }
 // ---- engine_sparse.hip -----------------------------------------------------------------------------------
 void sparse_release(E* e, OpDesc& o);
+void sparse_store_release(SparseStore& s);      // the arrays of one store (the caller has synchronised the stream)
+const char* kind_words(int kind);               // an operator kind in words, for the refusals that name it
 bool device_array(E* e, const void* p, const char* name, size_t bytes, std::string* why);
 // ---- engine_guess.hip ------------------------------------------------------------------------------------
 static inline void guess_drop(E* e) { e->guess_cols = 0; e->guess_tag = GUESS_NONE; }    // X is about to be written

@@ -19,11 +19,10 @@
 #include "davidson_hip_ext.h"
 #include "davidson_hip_herm.h"
 
-void sparse_release(E* e, OpDesc& o) {
-  SparseStore& s = o.sp;
-  if (!s.rp && !s.col && !s.val && !s.items && !s.longs && !s.part && !s.src && !s.doff && !s.dpos && !s.bdiag && !s.rbound && !s.dia_off && !s.dia_val)
-    return;
-  (void)hipStreamSynchronize(e->stream);         // applies in flight may still read the arrays
+static bool sparse_store_empty(const SparseStore& s) {
+  return !s.rp && !s.col && !s.val && !s.items && !s.longs && !s.part && !s.src && !s.doff && !s.dpos && !s.bdiag && !s.rbound && !s.dia_off && !s.dia_val;
+}
+void sparse_store_release(SparseStore& s) {
   pool_free(s.rp); pool_free(s.col); pool_free(s.val);
   pool_free(s.items); pool_free(s.longs); pool_free(s.part);
   pool_free(s.src); pool_free(s.doff); pool_free(s.dpos);
@@ -31,6 +30,31 @@ void sparse_release(E* e, OpDesc& o) {
   pool_free(s.rbound);
   pool_free(s.dia_off); pool_free(s.dia_val);
   s = SparseStore();
+}
+void sparse_release(E* e, OpDesc& o) {
+  if (sparse_store_empty(o.sp) && sparse_store_empty(o.sp2) && !o.fsai_ws) return;
+  (void)hipStreamSynchronize(e->stream);         // applies in flight may still read the arrays
+  sparse_store_release(o.sp);
+  sparse_store_release(o.sp2);                   // DAV_KIND_FSAI: the rows of G^T and the block between the two products
+  pool_free(o.fsai_ws);
+  o.fsai_ws = nullptr;
+  o.fsai_longest_row = o.fsai_longest_col = 0;
+}
+
+// the one table of the kinds in words: the refusals of BDPR, CHEB / LCHEB and davp_build_fsai that name what an operator is
+const char* kind_words(int kind) {
+  switch (kind) {
+    case DAV_KIND_NONE: return "not set";
+    case DAV_KIND_DENSE: return "a dense matrix";
+    case DAV_KIND_IDENTITY: return "the identity";
+    case DAV_KIND_HOST: return "a host callback";
+    case DAV_KIND_DEVICE: return "a device callback";
+    case DAV_KIND_CSR: return "a CSR matrix";
+    case DAV_KIND_BSR: return "a BSR matrix";
+    case DAV_KIND_DIA: return "a CSR matrix stored by diagonals";
+    case DAV_KIND_FSAI: return "a built FSAI preconditioner (DAV_KIND_FSAI)";
+    default: return "a generated operator";
+  }
 }
 
 namespace {
@@ -1010,6 +1034,8 @@ extern "C" int davh_set_operator_csr_dev(dav_handle_t e, int which, const void* 
 extern "C" int dav_keep_value_map(dav_handle_t e, int which, int on) {
   if (!e) return fail("dav_keep_value_map: null engine");
   if (which < 0 || which >= N_OPS) return fail("dav_keep_value_map: bad operator id");
+  if (on != 0 && e->op[which].kind == DAV_KIND_FSAI)
+    return fail(std::string("dav_keep_value_map: the operator is ") + kind_words(DAV_KIND_FSAI) + ": it has no value map to keep");
   e->keep_map[which] = on != 0 ? 1 : 0;
   return 0;
 }
@@ -1021,6 +1047,7 @@ int update_refuse(const char* name, const std::string& msg) { return fail(std::s
 // "" = the operator can take new values: CSR (also stored by diagonals) or BSR, set with its value map
 std::string not_updatable(const OpDesc& o) {
   if (o.kind == DAV_KIND_NONE) return "operator not set";
+  if (o.kind == DAV_KIND_FSAI) return std::string("the operator is ") + kind_words(o.kind) + ": a snapshot of A, B and sigma that takes no values (call davp_build_fsai again)";
   if (o.kind != DAV_KIND_CSR && o.kind != DAV_KIND_BSR && o.kind != DAV_KIND_DIA)
     return "the operator is not a CSR or BSR operator (only a sparse operator set after dav_keep_value_map(h, which, 1) takes new values)";
   if (!o.sp.src || !o.sp.doff || !o.sp.dpos)

@@ -291,6 +291,27 @@ int64_t coo_sort_small_rows();
 void launch_coo_mark(hipStream_t st, const void* row, int ri64, const void* col, int ci64, int64_t n, int64_t nnz, int base, int lower,
                      uint8_t* marks, unsigned long long* ndiag);
 
+// ---- factorized sparse approximate inverse (k_fsai.hip; davp_build_fsai) ------------------------------------------
+// rp / col: the canonical rows of a CSR operator whose local rows are the whole matrix (one rank), columns ascending.  A pattern is a CSR
+// index pair (offsets from 0, columns ascending, the row's own index last) of at most FSAI_MAX_ROW columns per row.
+constexpr int FSAI_MAX_ROW = 64;
+// level 1: count[i] = columns of P_1(i) (the distinct columns <= i of row i, and i); *bad (~0 first) = the smallest row with more than
+// FSAI_MAX_ROW of them.  The fill pass writes them behind the scanned counts prp.
+void launch_fsai_pattern1_count(hipStream_t st, const int64_t* rp, const int32_t* col, int64_t n, int64_t* count, unsigned long long* bad);
+void launch_fsai_pattern1_fill(hipStream_t st, const int64_t* rp, const int32_t* col, int64_t n, const int64_t* prp, int32_t* pcol);
+// the next level: the union of P_1(j) over the columns j of the previous level's row (qrp / qcol), by a merge over the sorted lists
+void launch_fsai_pattern_next_count(hipStream_t st, const int64_t* qrp, const int32_t* qcol, const int64_t* p1rp, const int32_t* p1col, int64_t n,
+                                    int64_t* count, unsigned long long* bad);
+void launch_fsai_pattern_next_fill(hipStream_t st, const int64_t* qrp, const int32_t* qcol, const int64_t* p1rp, const int32_t* p1col, int64_t n,
+                                   const int64_t* prp, int32_t* pcol);
+// info[0] = the longest row of the offsets rp[0..n], info[1] / info[2] = 1 where a row of at most 16 / of more entries exists; info is 0 first
+void launch_fsai_row_lengths(hipStream_t st, const int64_t* rp, int64_t n, unsigned long long* info);
+// the rows of G on the pattern prp / pcol: gval[prp[i] + p] = G(i, J_p) and grow[prp[i] + p] = i; brp = nullptr: B is the identity; *bad
+// (~0 first) = the smallest row with a pivot that is not finite or not > 0.  small / large: rows of at most 16 / of more columns exist
+void launch_fsai_rows(hipStream_t st, const int64_t* prp, const int32_t* pcol, int64_t n, const int64_t* arp, const int32_t* acol,
+                      const double* aval, const int64_t* brp, const int32_t* bcol, const double* bval, double sigma, bool small, bool large,
+                      double* gval, int32_t* grow, unsigned long long* bad);
+
 // ---- K1d': device build of a BSR operator (k_bsr_build.hip; dav_set_operator_bsr_dev) -----------------------------------------------
 // The index level is the CSR build above over the n / b block rows with the block source as payload.  Then the values move once:
 // val[q b^2 + k b + m] = entry (tr ? k : m, tr ? m : k) of input block p, for canonical block q with src[q] = p << 1 | tr; rowmaj: the

@@ -816,6 +816,30 @@ class CEngine:
                                                      vals.data_ptr() or None, base, CSR_LOWER if lower else CSR_FULL))
         self._saw_values(which, nnz, pairs=True)
 
+    def build_fsai(self, sigma=0.0, level=1):
+        """davp_build_fsai: the factorized sparse approximate inverse M = G^T G of A - sigma B on the pattern of tril(A)^level, level 1..3,
+        into slot OP_M (include/davidson_hip_precond.h has the definition).  A is the CSR operator of slot OP_A, B a CSR operator or the
+        identity, A - sigma B positive definite, one rank.  The engine's refusal is a DavidsonHipError; slot OP_M is then unset."""
+        self._saw_values(OP_M, None)
+        self._chk(self.lib.davp_build_fsai(self.h, float(sigma), int(level)))
+
+    def fsai_info(self):
+        """davp_fsai_info: (entries of G, longest row of G, longest row of G^T); zeros when slot OP_M holds no built preconditioner"""
+        nnz, row, col = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self.lib.davp_fsai_info(self.h, C.byref(nnz), C.byref(row), C.byref(col)))
+        return nnz.value, row.value, col.value
+
+    def fsai_factor(self, transposed=False):
+        """davp_fsai_get_factor: (indptr int64, indices int32, data float64) of G - transposed=True: of the store of G^T - as 0-based
+        CSR numpy arrays"""
+        nnz = self.fsai_info()[0]
+        rp = np.zeros(self.n + 1, dtype=np.int64)
+        ci = np.zeros(max(nnz, 1), dtype=np.int32)
+        vv = np.zeros(max(nnz, 1), dtype=np.float64)
+        self._chk(self.lib.davp_fsai_get_factor(self.h, int(bool(transposed)), rp.ctypes.data_as(C.c_void_p), ci.ctypes.data_as(C.c_void_p),
+                                                _dp(vv)))
+        return rp, ci[:nnz], vv[:nnz]
+
     def _saw_values(self, which, count, pairs=False):
         """the number of values the sparse set call of operator `which` saw (None: unknown - a refused call, or one not made here);
         pairs: they are complex (re, im) pairs (set_operator_csr_hermitian)"""

@@ -420,6 +420,28 @@ contains
     stat = int(st, c_int)
   end function fdh_engine_set_hermitian_device
 
+  !> engine_build_preconditioner(eng, sigma, level, stat): returns the engine's status, as fd_engine_set_sparse_device does
+  function fdp_engine_build_fsai(p, sigma, level) result(stat) bind(C, name="fdp_engine_build_fsai")
+    type(c_ptr), value :: p
+    real(c_double), value :: sigma
+    integer(c_int), value :: level
+    integer(c_int) :: stat
+    type(davidson_engine), pointer :: eng
+    integer :: st
+    call c_f_pointer(p, eng)
+    call engine_build_preconditioner(eng, sigma, int(level), st)
+    stat = int(st, c_int)
+  end function fdp_engine_build_fsai
+
+  !> engine_preconditioner_info(eng, nnz, longest_row, longest_col)
+  subroutine fdp_engine_fsai_info(p, nnz, longest_row, longest_col) bind(C, name="fdp_engine_fsai_info")
+    type(c_ptr), value :: p
+    integer(c_int64_t), intent(out) :: nnz, longest_row, longest_col
+    type(davidson_engine), pointer :: eng
+    call c_f_pointer(p, eng)
+    call engine_preconditioner_info(eng, nnz, longest_row, longest_col)
+  end subroutine fdp_engine_fsai_info
+
   !> engine_set_sparse(eng, which, a) with a bsr_matrix from C arrays numbered from `base` (values in Fortran order, as bsr_from_c)
   subroutine fd_engine_set_block_sparse(p, which, n, b, rp, col, vals, base, lower) bind(C, name="fd_engine_set_block_sparse")
     type(c_ptr), value :: p

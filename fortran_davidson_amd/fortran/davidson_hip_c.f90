@@ -241,6 +241,31 @@ module davidson_hip_c
        integer(c_int), value :: index_base, triangle
        integer(c_int) :: ierr
      end function
+     !> the factorized sparse approximate inverse of A - sigma B on the pattern of tril(A)^level into slot M (include/davidson_hip_precond.h)
+     function davp_build_fsai(h, sigma, level) bind(C, name="davp_build_fsai") result(ierr)
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: h
+       real(c_double), value :: sigma
+       integer(c_int), value :: level
+       integer(c_int) :: ierr
+     end function
+     !> entries of G, its longest row, the longest row of G^T (zeros when slot M holds no built preconditioner)
+     function davp_fsai_info(h, nnz, longest_row, longest_col) bind(C, name="davp_fsai_info") result(ierr)
+       import :: c_ptr, c_int, c_int64_t
+       type(c_ptr), value :: h
+       integer(c_int64_t), intent(out) :: nnz, longest_row, longest_col
+       integer(c_int) :: ierr
+     end function
+     !> G (transposed = 0) or G^T as 0-based CSR into the caller's arrays (n + 1, nnz, nnz)
+     function davp_fsai_get_factor(h, transposed, row_ptr, col_idx, vals) bind(C, name="davp_fsai_get_factor") result(ierr)
+       import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+       type(c_ptr), value :: h
+       integer(c_int), value :: transposed
+       integer(c_int64_t), intent(out) :: row_ptr(*)
+       integer(c_int32_t), intent(out) :: col_idx(*)
+       real(c_double), intent(out) :: vals(*)
+       integer(c_int) :: ierr
+     end function
      !> a BSR matrix from device arrays of the engine's device, built on the GPU (row_ptr_bits / col_bits: 32 or 64)
      function dav_set_operator_bsr_dev(h, which, block_size, block_row_ptr, row_ptr_bits, block_col_idx, col_bits, vals, index_base, &
           triangle, block_layout) bind(C, name="dav_set_operator_bsr_dev") result(ierr)

@@ -625,6 +625,26 @@ class DavidsonEngine:
         if keep_map:
             self._kept[which] = {"count": nnz, "b": 2, "fortran_blocks": False, "pairs": True, "diag_pos": diag_pos}
 
+    def build_preconditioner(self, sigma=0.0, level=1):
+        """The preconditioner M (slot 3) BUILT from the stored operators (Fortran: engine_build_preconditioner): the factorized sparse
+        approximate inverse G^T G of A - sigma B on the pattern of tril(A)^level (the power of the lower triangle), level 1, 2 or 3 - at most 64 entries per row of G, a
+        longer row is refused, never cut.  A was set by set_sparse / set_coo (CSR, not stored by diagonals), B the same way or not at
+        all; A - sigma B must be positive definite (sigma at or below the lowest eigenvalue wanted).  solve("DPR") and solve("GJD")
+        then apply it as they apply any M.  A snapshot of A, B and sigma: build again after update_values.  A refused build raises
+        DavidsonHipError and leaves slot 3 unset.  Returns (entries of G, longest row of G, longest row of G^T)."""
+        self._keep_map_forget(3)
+        st = self.lib.fdp_engine_build_fsai(self.p, float(sigma), int(level))
+        if st != 0:
+            raise DavidsonHipError(hip_lib().dav_last_error().decode())
+        nnz, row, col = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self.lib.fdp_engine_fsai_info(self.p, C.byref(nnz), C.byref(row), C.byref(col))
+        return nnz.value, row.value, col.value
+
+    def _keep_map_forget(self, which):
+        """what update_values and the method checks knew of operator `which` goes: it is no longer the sparse operator of a set call"""
+        self._note_blocks(which, None)
+        getattr(self, "_kept", {}).pop(which, None)
+
     def update_values(self, which, data):
         """New values of operator A (which=1), B (which=2) or M (which=3) on its kept pattern (Fortran: engine_update_sparse_values /
         engine_update_sparse_values_device): the operator was set by set_sparse / set_block_sparse with keep_map=True, and `data` is the
