@@ -182,6 +182,18 @@ PRECOND_FD = {
     "fdp_engine_fsai_info": (None, (ptr, ptr, ptr, ptr)),
 }
 
+# include/davidson_hip_bprecond.h: the block preconditioner the engine builds from stored BSR operators (prefix davq_) and its doors
+# (prefix fdq_); tests/test_bfsai_cpu.py compares both with the header and the Fortran sources
+BPRECOND = {
+    "davq_build_block_fsai": (i32, (ptr, f64, i32)),
+    "davq_block_fsai_info": (i32, (ptr, ptr, ptr, ptr, ptr)),
+    "davq_block_fsai_get_factor": (i32, (ptr, i32, ptr, ptr, ptr)),
+}
+BPRECOND_FD = {
+    "fdq_engine_build_block_fsai": (i32, (ptr, f64, i32)),
+    "fdq_engine_block_fsai_info": (None, (ptr, ptr, ptr, ptr, ptr)),
+}
+
 
 def apply(lib, table, optional=()):
     """Set restype and argtypes of every entry of `table` on `lib`.  An entry of `optional` that the library lacks is skipped; any

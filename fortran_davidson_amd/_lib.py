@@ -49,6 +49,7 @@ def hip_lib() -> C.CDLL:
         _abi.apply(lib, _abi.EXT)
         _abi.apply(lib, _abi.HERM)
         _abi.apply(lib, _abi.PRECOND)
+        _abi.apply(lib, _abi.BPRECOND)
         _hip = lib
         runtimes = hip_runtimes_mapped()
         if len(runtimes) > 1:
@@ -85,5 +86,6 @@ def fortran_lib() -> C.CDLL:
         _abi.apply(lib, _abi.EXT_FD)
         _abi.apply(lib, _abi.HERM_FD)
         _abi.apply(lib, _abi.PRECOND_FD)
+        _abi.apply(lib, _abi.BPRECOND_FD)
         _fortran = lib
     return _fortran

@@ -104,7 +104,8 @@ __device__ __forceinline__ double dav_harness_entry_poly(const double* __restric
 enum { DAV_KIND_NONE = 0, DAV_KIND_DENSE = 1, DAV_KIND_HASHED = 2, DAV_KIND_HARNESS = 3,
        DAV_KIND_IDENTITY = 4, DAV_KIND_HOST = 5, DAV_KIND_DEVICE = 6, DAV_KIND_CSR = 7, DAV_KIND_BSR = 8,
        DAV_KIND_DIA = 9 /* a CSR matrix stored by diagonals (DAV_CSR_DIAGONALS) */,
-       DAV_KIND_FSAI = 10 /* slot M only: the factorized sparse approximate inverse G^T G built by davp_build_fsai (two CSR stores) */ };
+       DAV_KIND_FSAI = 10 /* slot M only: the factorized sparse approximate inverse G^T G built by davp_build_fsai (two CSR stores) */,
+       DAV_KIND_BFSAI = 11 /* slot M only: the block factorized sparse approximate inverse built by davq_build_block_fsai (two BSR stores) */ };
 
 struct OpParams {          // passed by value to the matrix-free kernels
   int kind;

@@ -546,6 +546,25 @@ static int apply_fsai(E* e, int which, OpDesc& o, const double* src, int k, doub
   return 0;
 }
 
+// The built block preconditioner M = G^T G (DAV_KIND_BFSAI; engine_bfsai.hip): the steps of apply_fsai with the BSR
+// product (k_bsrmm.hip) over the two BSR stores, so the result equals, bit for bit, two applies of the two stores set as BSR operators.
+// The block between the products is the field of apply_fsai, allocated here at the first apply.
+static int apply_bfsai(E* e, int which, OpDesc& o, const double* src, int k, double* dst, bool timed) {
+  if (!o.fsai_ws) {
+    if (pool_malloc(&o.fsai_ws, sizeof(double) * (size_t)e->ldp * 64) != hipSuccess) {
+      (void)hipGetLastError();
+      o.fsai_ws = nullptr;
+      return fail("dav_apply: device memory for the intermediate block of the block FSAI preconditioner could not be allocated");
+    }
+  }
+  for (int c = 0; c < k; c += 64) {
+    const int kk = std::min(64, k - c);
+    CHK(apply_sparse(e, which, DAV_KIND_BSR, o.sp, src + (int64_t)c * e->ldp, kk, o.fsai_ws, timed));
+    CHK(apply_sparse(e, which, DAV_KIND_BSR, o.sp2, o.fsai_ws, kk, dst + (int64_t)c * e->ldp, timed));
+  }
+  return 0;
+}
+
 // Symmetric tiles, stored or generated.  A generated second operator whose tiles (partly) fit next to everything else is kept
 // resident for its longest block rows (configs[3]: B = the unit-diagonal generator next to a stored A): those rows run the stored
 // kernels - half the time per 16 columns of the generated sweep, a quarter in the 32- / 64-column launches - the others are generated
@@ -599,6 +618,7 @@ int apply_ptr(E* e, int which, const double* src, int k, double* dst, bool timed
   if (o.kind == DAV_KIND_DEVICE) return apply_device(e, which, o, src, k, dst, timed);
   if (o.kind == DAV_KIND_CSR || o.kind == DAV_KIND_BSR || o.kind == DAV_KIND_DIA) return apply_sparse(e, which, o.kind, o.sp, src, k, dst, timed);
   if (o.kind == DAV_KIND_FSAI) return apply_fsai(e, which, o, src, k, dst, timed);
+  if (o.kind == DAV_KIND_BFSAI) return apply_bfsai(e, which, o, src, k, dst, timed);
   if ((o.kind == DAV_KIND_DENSE || o.kind == DAV_KIND_HASHED || o.kind == DAV_KIND_HARNESS) && o.storage == 1)
     return apply_symmetric(e, which, o, src, k, dst, timed, inner);
   return apply_full_rows(e, which, o, src, k, dst, timed);

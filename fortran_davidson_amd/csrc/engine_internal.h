@@ -200,9 +200,10 @@ struct OpDesc {
   // streamed rows of a dense one; released with the engine
   double* lbound = nullptr;
   bool lbound_valid = false;
-  SparseStore sp;            // DAV_KIND_CSR / DAV_KIND_BSR / DAV_KIND_DIA; DAV_KIND_FSAI: the rows of G
+  SparseStore sp;            // DAV_KIND_CSR / DAV_KIND_BSR / DAV_KIND_DIA; DAV_KIND_FSAI / DAV_KIND_BFSAI: the (block) rows of G
   // DAV_KIND_FSAI (engine_fsai.hip): the rows of G^T as a second canonical CSR store, the block between the two products
   // (ldp x 64, allocated at the first apply) and what davp_fsai_info reports; all released with the operator
+  // DAV_KIND_BFSAI (engine_bfsai.hip): the same fields with two canonical BSR stores and the lengths in blocks
   SparseStore sp2;
   double* fsai_ws = nullptr;
   int64_t fsai_longest_row = 0, fsai_longest_col = 0;

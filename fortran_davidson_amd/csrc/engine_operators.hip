@@ -670,8 +670,8 @@ extern "C" int dav_set_operator_device(dav_handle_t e, int which, dav_device_app
 }
 
 extern "C" int dav_get_diagonal(dav_handle_t e, int which, double* out) {
-  if (e && which == DAV_OP_M && e->op[which].kind == DAV_KIND_FSAI)
-    return fail(std::string("dav_get_diagonal: the operator is ") + kind_words(DAV_KIND_FSAI) + ": no diagonal is kept for it");
+  if (e && which == DAV_OP_M && (e->op[which].kind == DAV_KIND_FSAI || e->op[which].kind == DAV_KIND_BFSAI))
+    return fail(std::string("dav_get_diagonal: the operator is ") + kind_words(e->op[which].kind) + ": no diagonal is kept for it");
   if (which < 0 || which >= N_OPS || e->diag_host[which].empty()) return fail("dav_get_diagonal: operator not set");
   std::memcpy(out, e->diag_host[which].data(), sizeof(double) * e->n);
   return 0;

@@ -35,7 +35,7 @@ void sparse_release(E* e, OpDesc& o) {
   if (sparse_store_empty(o.sp) && sparse_store_empty(o.sp2) && !o.fsai_ws) return;
   (void)hipStreamSynchronize(e->stream);         // applies in flight may still read the arrays
   sparse_store_release(o.sp);
-  sparse_store_release(o.sp2);                   // DAV_KIND_FSAI: the rows of G^T and the block between the two products
+  sparse_store_release(o.sp2);                   // DAV_KIND_FSAI / DAV_KIND_BFSAI: the rows of G^T and the block between the two products
   pool_free(o.fsai_ws);
   o.fsai_ws = nullptr;
   o.fsai_longest_row = o.fsai_longest_col = 0;
@@ -53,6 +53,7 @@ const char* kind_words(int kind) {
     case DAV_KIND_BSR: return "a BSR matrix";
     case DAV_KIND_DIA: return "a CSR matrix stored by diagonals";
     case DAV_KIND_FSAI: return "a built FSAI preconditioner (DAV_KIND_FSAI)";
+    case DAV_KIND_BFSAI: return "a built block FSAI preconditioner (DAV_KIND_BFSAI)";
     default: return "a generated operator";
   }
 }
@@ -1034,8 +1035,8 @@ extern "C" int davh_set_operator_csr_dev(dav_handle_t e, int which, const void* 
 extern "C" int dav_keep_value_map(dav_handle_t e, int which, int on) {
   if (!e) return fail("dav_keep_value_map: null engine");
   if (which < 0 || which >= N_OPS) return fail("dav_keep_value_map: bad operator id");
-  if (on != 0 && e->op[which].kind == DAV_KIND_FSAI)
-    return fail(std::string("dav_keep_value_map: the operator is ") + kind_words(DAV_KIND_FSAI) + ": it has no value map to keep");
+  if (on != 0 && (e->op[which].kind == DAV_KIND_FSAI || e->op[which].kind == DAV_KIND_BFSAI))
+    return fail(std::string("dav_keep_value_map: the operator is ") + kind_words(e->op[which].kind) + ": it has no value map to keep");
   e->keep_map[which] = on != 0 ? 1 : 0;
   return 0;
 }
@@ -1048,6 +1049,7 @@ int update_refuse(const char* name, const std::string& msg) { return fail(std::s
 std::string not_updatable(const OpDesc& o) {
   if (o.kind == DAV_KIND_NONE) return "operator not set";
   if (o.kind == DAV_KIND_FSAI) return std::string("the operator is ") + kind_words(o.kind) + ": a snapshot of A, B and sigma that takes no values (call davp_build_fsai again)";
+  if (o.kind == DAV_KIND_BFSAI) return std::string("the operator is ") + kind_words(o.kind) + ": a snapshot of A, B and sigma that takes no values (call davq_build_block_fsai again)";
   if (o.kind != DAV_KIND_CSR && o.kind != DAV_KIND_BSR && o.kind != DAV_KIND_DIA)
     return "the operator is not a CSR or BSR operator (only a sparse operator set after dav_keep_value_map(h, which, 1) takes new values)";
   if (!o.sp.src || !o.sp.doff || !o.sp.dpos)

@@ -312,6 +312,26 @@ void launch_fsai_rows(hipStream_t st, const int64_t* prp, const int32_t* pcol, i
                       const double* aval, const int64_t* brp, const int32_t* bcol, const double* bval, double sigma, bool small, bool large,
                       double* gval, int32_t* grow, unsigned long long* bad);
 
+// ---- block factorized sparse approximate inverse (k_bfsai.hip; davq_build_block_fsai) ------------------------------
+// The pattern is that of the section above over the nb block rows of a BSR operator of block size b (the four pattern launches serve the
+// block index arrays unchanged); a block row of m blocks makes s = m b scalar columns, at most BFSAI_MAX_COLS.
+constexpr int BFSAI_MAX_COLS = 64;
+// after a count pass: *bad = min(*bad, the smallest block row with count[i] * b > BFSAI_MAX_COLS)
+void launch_bfsai_cap(hipStream_t st, const int64_t* count, int64_t nb, int b, unsigned long long* bad);
+// info[0] = the longest block row of the offsets rp[0..nb], info[1] / info[2] = 1 where a block row of at most 16 / of more scalar columns
+// exists; info is 0 first
+void launch_bfsai_row_lengths(hipStream_t st, const int64_t* rp, int64_t nb, int b, unsigned long long* info);
+// the block rows of G on the pattern prp / pcol: gval[(prp[I] + q) b^2 + t b + r] = G(I b + t, J_q b + r) and grow[prp[I] + q] = I; brp =
+// nullptr: B is the identity; *bad (~0 first) = the smallest block row with a pivot that is not finite or not > 0
+void launch_bfsai_rows(hipStream_t st, const int64_t* prp, const int32_t* pcol, int64_t nb, int b, const int64_t* arp, const int32_t* acol,
+                       const double* aval, const int64_t* brp, const int32_t* bcol, const double* bval, double sigma, bool small, bool large,
+                       double* gval, int32_t* grow, unsigned long long* bad);
+// the block rows of G^T: count[c] += 1 per block of block column c (count is 0 first; launch_csr_build_scan makes the offsets trp of it),
+// then every block takes a slot of its block column (cursor is 0 first; slot holds nnzb values) and is copied there untouched
+void launch_bfsai_transpose_count(hipStream_t st, const int32_t* pcol, int64_t nnzb, int64_t* count);
+void launch_bfsai_transpose_fill(hipStream_t st, const int32_t* pcol, const int32_t* grow, const double* gval, int64_t nnzb, int b,
+                                 const int64_t* trp, int64_t* cursor, int64_t* slot, int32_t* tcol, double* tval);
+
 // ---- K1d': device build of a BSR operator (k_bsr_build.hip; dav_set_operator_bsr_dev) -----------------------------------------------
 // The index level is the CSR build above over the n / b block rows with the block source as payload.  Then the values move once:
 // val[q b^2 + k b + m] = entry (tr ? k : m, tr ? m : k) of input block p, for canonical block q with src[q] = p << 1 | tr; rowmaj: the

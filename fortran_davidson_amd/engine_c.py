@@ -840,6 +840,34 @@ class CEngine:
                                                 _dp(vv)))
         return rp, ci[:nnz], vv[:nnz]
 
+    def build_block_fsai(self, sigma=0.0, level=1):
+        """davq_build_block_fsai: the block factorized sparse approximate inverse M = G^T G of A - sigma B on the pattern of tril(A)^level
+        over the block index arrays, level 1..3, into slot OP_M (include/davidson_hip_bprecond.h has the definition).  A is the BSR
+        operator of slot OP_A (a Hermitian operator is one, b = 2), B a BSR operator of the same block size or the identity, A - sigma B
+        positive definite, one rank.  The engine's refusal is a DavidsonHipError; slot OP_M is then unset."""
+        self._saw_values(OP_M, None)
+        self._chk(self.lib.davq_build_block_fsai(self.h, float(sigma), int(level)))
+
+    def block_fsai_info(self):
+        """davq_block_fsai_info: (block size, blocks of G, longest block row of G, longest block row of G^T); zeros when slot OP_M
+        holds no built block preconditioner"""
+        b, nnzb, row, col = C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self.lib.davq_block_fsai_info(self.h, C.byref(b), C.byref(nnzb), C.byref(row), C.byref(col)))
+        return b.value, nnzb.value, row.value, col.value
+
+    def block_fsai_factor(self, transposed=False):
+        """davq_block_fsai_get_factor: (indptr int64, indices int32, data float64 (nnzb, b, b) row-major blocks) of G - transposed=True:
+        of the store of G^T - as 0-based BSR numpy arrays, as set_operator_bsr takes them"""
+        b, nnzb = self.block_fsai_info()[:2]
+        if b == 0:
+            self._chk(self.lib.davq_block_fsai_get_factor(self.h, int(bool(transposed)), None, None, None))
+        rp = np.zeros(self.n // b + 1, dtype=np.int64)
+        ci = np.zeros(max(nnzb, 1), dtype=np.int32)
+        vv = np.zeros((max(nnzb, 1), b, b), dtype=np.float64)
+        self._chk(self.lib.davq_block_fsai_get_factor(self.h, int(bool(transposed)), rp.ctypes.data_as(C.c_void_p),
+                                                      ci.ctypes.data_as(C.c_void_p), _dp(vv)))
+        return rp, ci[:nnzb], vv[:nnzb]
+
     def _saw_values(self, which, count, pairs=False):
         """the number of values the sparse set call of operator `which` saw (None: unknown - a refused call, or one not made here);
         pairs: they are complex (re, im) pairs (set_operator_csr_hermitian)"""

@@ -29,7 +29,7 @@ module davidson_device
        engine_set_identity, engine_set_device_operator, engine_comm_unique_id, engine_comm_init, &
        generalized_eigensolver_device, generalized_eigensolver_device_guess, device_solve_impl, davidson_device_loop, basis_capacity, default_max_dim, tick, verbose, davidson_free_buffers, &
        engine_set_initial_vectors, engine_set_initial_vectors_device, engine_keep_result_as_guess, stage_initial_vectors, &
-       engine_build_preconditioner, engine_preconditioner_info
+       engine_build_preconditioner, engine_preconditioner_info, engine_build_block_preconditioner, engine_block_preconditioner_info
 
 contains
 

@@ -442,6 +442,29 @@ contains
     call engine_preconditioner_info(eng, nnz, longest_row, longest_col)
   end subroutine fdp_engine_fsai_info
 
+  !> engine_build_block_preconditioner(eng, sigma, level, stat): returns the engine's status, as fd_engine_set_sparse_device does
+  function fdq_engine_build_block_fsai(p, sigma, level) result(stat) bind(C, name="fdq_engine_build_block_fsai")
+    type(c_ptr), value :: p
+    real(c_double), value :: sigma
+    integer(c_int), value :: level
+    integer(c_int) :: stat
+    type(davidson_engine), pointer :: eng
+    integer :: st
+    call c_f_pointer(p, eng)
+    call engine_build_block_preconditioner(eng, sigma, int(level), st)
+    stat = int(st, c_int)
+  end function fdq_engine_build_block_fsai
+
+  !> engine_block_preconditioner_info(eng, block_size, nnzb, longest_row, longest_col)
+  subroutine fdq_engine_block_fsai_info(p, block_size, nnzb, longest_row, longest_col) bind(C, name="fdq_engine_block_fsai_info")
+    type(c_ptr), value :: p
+    integer(c_int), intent(out) :: block_size
+    integer(c_int64_t), intent(out) :: nnzb, longest_row, longest_col
+    type(davidson_engine), pointer :: eng
+    call c_f_pointer(p, eng)
+    call engine_block_preconditioner_info(eng, block_size, nnzb, longest_row, longest_col)
+  end subroutine fdq_engine_block_fsai_info
+
   !> engine_set_sparse(eng, which, a) with a bsr_matrix from C arrays numbered from `base` (values in Fortran order, as bsr_from_c)
   subroutine fd_engine_set_block_sparse(p, which, n, b, rp, col, vals, base, lower) bind(C, name="fd_engine_set_block_sparse")
     type(c_ptr), value :: p

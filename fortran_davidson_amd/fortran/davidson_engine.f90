@@ -13,7 +13,7 @@ module davidson_engine_setup
        engine_set_correction_policy, engine_generate_diagonal_dominant, engine_set_hashed_operator, engine_set_harness_operator, &
        engine_set_identity, engine_set_device_operator, engine_comm_unique_id, engine_comm_init, davidson_free_buffers, &
        engine_set_initial_vectors, engine_set_initial_vectors_device, engine_keep_result_as_guess, engine_build_preconditioner, &
-       engine_preconditioner_info
+       engine_preconditioner_info, engine_build_block_preconditioner, engine_block_preconditioner_info
 
   !> Handle of a device-resident problem: operators A (and B) plus all work panels in HBM.
   type :: davidson_engine
@@ -343,6 +343,37 @@ contains
     integer(c_int64_t), intent(out) :: nnz, longest_row, longest_col
     call check_dav(davp_fsai_info(eng%h, nnz, longest_row, longest_col), "davp_fsai_info")
   end subroutine engine_preconditioner_info
+
+  !> The preconditioner M BUILT from stored BLOCK operators (include/davidson_hip_bprecond.h; DESIGN section 30): the block factorized
+  !> sparse approximate inverse G^T G of A - sigma B on the pattern of tril(A)^level over the block index arrays, level = 1 (default), 2 or
+  !> 3, into slot 3.  A is a BSR operator (engine_set_sparse with a bsr_matrix; engine_set_hermitian, block size 2), B a BSR operator of
+  !> the same block size or the identity, A - sigma B positive definite; one rank; a block row of G holds at most 64 scalar columns.  A
+  !> snapshot: call it again after new values.  stat present: a refused build returns its non-zero status here (dav_last_error says why;
+  !> slot 3 is then unset), otherwise the program stops with the engine's message.
+  subroutine engine_build_block_preconditioner(eng, sigma, level, stat)
+    type(davidson_engine), intent(inout) :: eng
+    real(dp), intent(in) :: sigma
+    integer, intent(in), optional :: level
+    integer, intent(out), optional :: stat
+    integer(c_int) :: ierr, lv
+    lv = 1_c_int
+    if (present(level)) lv = int(level, c_int)
+    ierr = davq_build_block_fsai(eng%h, real(sigma, c_double), lv)
+    if (present(stat)) then
+       stat = int(ierr)
+    else
+       call check_dav(ierr, "davq_build_block_fsai")
+    end if
+  end subroutine engine_build_block_preconditioner
+
+  !> Block size, blocks of G, its longest block row and the longest block row of G^T of the preconditioner
+  !> engine_build_block_preconditioner left in slot 3 (zeros when the slot holds something else)
+  subroutine engine_block_preconditioner_info(eng, block_size, nnzb, longest_row, longest_col)
+    type(davidson_engine), intent(in) :: eng
+    integer(c_int), intent(out) :: block_size
+    integer(c_int64_t), intent(out) :: nnzb, longest_row, longest_col
+    call check_dav(davq_block_fsai_info(eng%h, block_size, nnzb, longest_row, longest_col), "davq_block_fsai_info")
+  end subroutine engine_block_preconditioner_info
 
   !> The caller's OWN operator as a block apply on device memory: the device counterpart of the reference's matrix-free interface
   !> (src/davidson.f90:277-337 takes a procedure on host arrays).  `fn` = c_funloc of a bind(C) function with the signature

@@ -266,6 +266,33 @@ module davidson_hip_c
        real(c_double), intent(out) :: vals(*)
        integer(c_int) :: ierr
      end function
+     !> the block factorized sparse approximate inverse of A - sigma B, A a BSR operator, into slot M (include/davidson_hip_bprecond.h)
+     function davq_build_block_fsai(h, sigma, level) bind(C, name="davq_build_block_fsai") result(ierr)
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: h
+       real(c_double), value :: sigma
+       integer(c_int), value :: level
+       integer(c_int) :: ierr
+     end function
+     !> block size, blocks of G, its longest block row, the longest block row of G^T (zeros when slot M holds no built block preconditioner)
+     function davq_block_fsai_info(h, block_size, nnzb, longest_row, longest_col) bind(C, name="davq_block_fsai_info") result(ierr)
+       import :: c_ptr, c_int, c_int64_t
+       type(c_ptr), value :: h
+       integer(c_int), intent(out) :: block_size
+       integer(c_int64_t), intent(out) :: nnzb, longest_row, longest_col
+       integer(c_int) :: ierr
+     end function
+     !> G (transposed = 0) or G^T as 0-based BSR with row-major blocks into the caller's arrays (n / b + 1, nnzb, nnzb b b)
+     function davq_block_fsai_get_factor(h, transposed, block_row_ptr, block_col_idx, vals) bind(C, name="davq_block_fsai_get_factor") &
+          result(ierr)
+       import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+       type(c_ptr), value :: h
+       integer(c_int), value :: transposed
+       integer(c_int64_t), intent(out) :: block_row_ptr(*)
+       integer(c_int32_t), intent(out) :: block_col_idx(*)
+       real(c_double), intent(out) :: vals(*)
+       integer(c_int) :: ierr
+     end function
      !> a BSR matrix from device arrays of the engine's device, built on the GPU (row_ptr_bits / col_bits: 32 or 64)
      function dav_set_operator_bsr_dev(h, which, block_size, block_row_ptr, row_ptr_bits, block_col_idx, col_bits, vals, index_base, &
           triangle, block_layout) bind(C, name="dav_set_operator_bsr_dev") result(ierr)

@@ -640,6 +640,22 @@ class DavidsonEngine:
         self.lib.fdp_engine_fsai_info(self.p, C.byref(nnz), C.byref(row), C.byref(col))
         return nnz.value, row.value, col.value
 
+    def build_block_preconditioner(self, sigma=0.0, level=1):
+        """The preconditioner M (slot 3) BUILT from stored BLOCK operators (Fortran: engine_build_block_preconditioner): the block
+        factorized sparse approximate inverse G^T G of A - sigma B on the pattern of tril(A)^level taken over the block index arrays,
+        level 1, 2 or 3 - at most 64 scalar columns (64 // b blocks) per block row of G, a longer block row is refused, never cut.  A
+        was set by set_block_sparse or set_hermitian (b = 2), B the same way with the same block size or not at all; A - sigma B must be
+        positive definite.  solve("DPR") and solve("GJD") then apply it as they apply any M.  A snapshot of A, B and sigma: build again
+        after update_values.  A refused build raises DavidsonHipError and leaves slot 3 unset.  Returns (block size, blocks of G,
+        longest block row of G, longest block row of G^T)."""
+        self._keep_map_forget(3)
+        st = self.lib.fdq_engine_build_block_fsai(self.p, float(sigma), int(level))
+        if st != 0:
+            raise DavidsonHipError(hip_lib().dav_last_error().decode())
+        b, nnzb, row, col = C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self.lib.fdq_engine_block_fsai_info(self.p, C.byref(b), C.byref(nnzb), C.byref(row), C.byref(col))
+        return b.value, nnzb.value, row.value, col.value
+
     def _keep_map_forget(self, which):
         """what update_values and the method checks knew of operator `which` goes: it is no longer the sparse operator of a set call"""
         self._note_blocks(which, None)
